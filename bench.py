@@ -2,6 +2,8 @@
 """bench.py — PDHG iterations/s of the MI355X PDLP path on the BASELINE.json workload.
 
   python bench.py --gpus 1 --steps K --warmup W            (default: N=1, a few seconds)
+  python bench.py ... --dump-outputs DIR                   (+ the solver state after the last timed step, .npy)
+  python bench.py ... --full                               (+ roofline, per-kernel times, CPU baseline: about a minute)
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one accepted PDHG iteration (two SpMVs + the fused level-1 work +
@@ -11,7 +13,8 @@ counts.  The LP (synthetic 1M x 1M, 8M nnz, SURVEY §8d generator, seed 1) is
 formulated, scaled and uploaded before the timed region; the K timed steps run
 with everything resident in HBM.  With N > 1 the SAME LP is row-block sharded
 over the N GPUs (strong scaling) and the A'y partials are all-reduced with RCCL.
-Prints ONE JSON line (rank 0).
+Prints ONE JSON line (rank 0): `value` / `ms_per_step` are the K timed steps.
+A plain run does nothing else; --full adds what takes runs of its own.
 """
 import argparse
 import ctypes as C
@@ -189,6 +192,27 @@ def _reference_highs_fn(lib_path, solver_name):
     return fn
 
 
+DUMP_BYTES = 64 * 2**20  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(S, solver_name, out_dir):
+    """What the timed loop computed, as a caller of DeviceSolver.iterate reads it after the last step: the current primal
+    and dual iterates, the averaged (pdlp) or reflected (hipdlp) ones, and the step sizes, as DIR/<name>.npy in float64.
+    Where the vectors exceed DUMP_BYTES together, each keeps the same share of its entries, chosen by a fixed seed (the
+    sorted indices of np.random.default_rng(0).choice over its length), so that two builds dump the same entries."""
+    import numpy as np
+    pair = ("x_avg", "y_avg") if solver_name == "pdlp" else ("x_reflected", "y_reflected")
+    names = [("x", S.n), ("y", S.m), (pair[0], S.n), (pair[1], S.m)]
+    keep = min(1.0, (DUMP_BYTES - 4096) / (8.0 * sum(length for _, length in names)))  # (less .npy headers, steps)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, length in names:
+        v = S.get(name, length)
+        if keep < 1.0:
+            v = v[np.sort(np.random.default_rng(0).choice(length, int(keep * length), replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    np.save(os.path.join(out_dir, "steps.npy"), S.get("steps", 8))
+
+
 def cpu_baseline(sp_struct, cfg, limits, solver_name="pdlp"):
     """Reference CPU pdlp (single thread) on a bounded sample of the same LP, as SURVEY §8(d) prescribes: the same
     solve at TWO iteration limits, iterations/s = the slope between them — set-up and the start-up phase (a check at
@@ -235,11 +259,18 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="b")
-    ap.add_argument("--cpu-iters", type=int, default=None, help="CPU baseline sample size (0 disables)")
-    ap.add_argument("--kernels", action="store_true", help="also print per-kernel timings to stderr")
+    ap.add_argument("--cpu-iters", type=int, default=None, help="CPU baseline sample size (0 disables; with --full)")
+    ap.add_argument("--kernels", action="store_true", help="also print per-kernel timings to stderr (with --full)")
     ap.add_argument("--solver", choices=["pdlp", "hipdlp"], default="pdlp",
                     help="pdlp = the headline path (cuPDLP-C semantics); hipdlp = the reference's Halpern PDHG path")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: a window of whole check periods, the in-loop roofline and per-kernel times, "
+                         "the scaling model, the cross-rank check and the reference CPU baseline (single thread, tens of s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the solver state after the last timed step to DIR/<name>.npy (float64, <= 64 MB in all)")
     args = ap.parse_args()
+    if args.kernels and not args.full:
+        ap.error("--kernels is part of --full")
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -247,6 +278,8 @@ def main():
     if world != args.gpus:
         raise SystemExit("--gpus %d but WORLD_SIZE=%d: launch with `python -m torch.distributed.run --nproc-per-node %d "
                          "... bench.py --gpus %d`" % (args.gpus, world, args.gpus, args.gpus))
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs needs --gpus 1: with N > 1 a rank holds a block of the dual iterate only")
     cfg = CONFIGS[args.config]
 
     import torch
@@ -355,14 +388,55 @@ def main():
             el = float(tt.item())
         return r, el
 
-    # The K steps the flags ask for, timed exactly as the contract says.  `value` must carry the reference's check
-    # schedule (one check iteration in 40): when the K-step window is not a whole number of check periods starting
-    # on one (the driver's --steps 20 --warmup 5 covers iterations 45..65: no check at all), `value` comes from a
-    # second window of >= 400 iterations that is, and the K-step window is reported next to it.
+    # The K steps the flags ask for, right behind the warm-up: `value` and `ms_per_step` are this window.  The reference
+    # checks once in 40 iterations; a window of K steps holds floor(K / 40) or ceil(K / 40) of those checks (the driver's
+    # --steps 20 --warmup 5 covers iterations 45..65: none), a window of whole check periods exactly its share.
     win_start = PRE_ROLL + args.warmup
     kst, k_elapsed = timed(args.steps)
-    k_window = {"value": kst.iters / k_elapsed, "unit": "it/s", "iters": int(kst.iters), "checks": int(kst.checks),
-                "ms_per_step": k_elapsed * 1e3 / kst.iters, "window": "iterations %d..%d" % (win_start, win_start + int(kst.iters))}
+    if args.dump_outputs:
+        dump_outputs(S, args.solver, args.dump_outputs)
+
+    exchange = {0.0: "none", 1.0: "RCCL all-reduce of A'y", 2.0: "direct xGMI mesh (all-gather x+, reduce-scatter A'y+)",
+                3.0: "direct xGMI mesh, two all-gathers (x+ column slices, y+ row blocks; A'y from the rank's column block)"}[
+        float(S.stage("exchange")[0])]
+    out = {
+        "metric": "PDHG iterations/sec" if args.solver == "pdlp" else "PDHG iterations/sec (HiPDLP path)",
+        "value": kst.iters / k_elapsed, "unit": "it/s", "n_gpus": world,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": k_elapsed * 1e3 / kst.iters, "higher_is_better": True,
+        "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": cfg["name"], "m": m, "n": n, "nnz": nnz,
+                   "parallelism": "single GPU" if world == 1 else "row-block x%d, %s" % (world, exchange),
+                   "options": "presolve=off, kkt_tolerance=1e-4, adaptive step + restarts (reference defaults)"},
+        "trial_steps": int(kst.trials), "rejected_trials": int(kst.trials - kst.iters), "checks": int(kst.checks),
+        "trial_launches": int(S.stage("trial_launches")[0]) if args.solver == "pdlp" else 2,
+        # launches of one check iteration queued behind the trial batches (0: the host drives the checks and waits for them)
+        "check_launches": int(S.stage("check_launches")[0]) if args.solver == "pdlp" else None,
+        "restarts": int(kst.restarts), "setup_seconds": t_setup,
+        "exchange_fallback": exchange_fallback, "exchange": exchange if world > 1 else None,
+        "startup_ms_first_40": startup_ms,
+        "timed_window": "iterations %d..%d" % (win_start, win_start + int(kst.iters)), "timed_steps": int(kst.iters),
+    }
+    if cfg.get("qp"):
+        out["metric"] = "PDHG iterations/sec (QP prox path)"
+        out["parity"] = ("unpinned: the reference has no PDLP for QPs (HighsOptions.cpp:1178-1181); optimal objectives are "
+                         "pinned on the reference's QP solver for small instances (tests/golden/reference_qp.json)")
+    if args.solver == "hipdlp":
+        out["config"]["options"] = "presolve=off, kkt_tolerance=1e-4, Halpern restarts + PID primal weight (reference defaults)"
+
+    def finish():
+        S.close()
+        if rank == 0:
+            print(json.dumps(out))
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish()
+        return
+
+    # --full: everything below measures or checks around the headline, with runs of its own.  A window of whole check
+    # periods starting on one (>= 400 iterations): the K-step window when it is one, else a second window behind it.
     if win_start % 40 == 0 and args.steps % 40 == 0 and args.steps >= 400:
         st, elapsed, val_start = kst, k_elapsed, win_start
     else:
@@ -372,10 +446,11 @@ def main():
             pos += 40 - pos % 40
         st, elapsed = timed(max(400, (args.steps + 39) // 40 * 40))
         val_start = pos
+    out["whole_check_periods"] = {"value": st.iters / elapsed, "unit": "it/s", "ms_per_step": elapsed * 1e3 / st.iters,
+                                  "iters": int(st.iters), "checks": int(st.checks), "trial_steps": int(st.trials),
+                                  "restarts": int(st.restarts),
+                                  "window": "iterations %d..%d" % (val_start, val_start + int(st.iters))}
 
-    exchange = {0.0: "none", 1.0: "RCCL all-reduce of A'y", 2.0: "direct xGMI mesh (all-gather x+, reduce-scatter A'y+)",
-                3.0: "direct xGMI mesh, two all-gathers (x+ column slices, y+ row blocks; A'y from the rank's column block)"}[
-        float(S.stage("exchange")[0])]
     exchange_waits = None
     if world > 1 and exchange.startswith("direct"):
         # device-side wall-clock time a rank spent waiting for its peers' flags, per hot-loop exchange (rank 0's view)
@@ -460,26 +535,11 @@ def main():
             traffic_miss = traffic_miss * 128.0 if traffic_miss is not None and not persistent else None
         except Exception:
             traffic = traffic_miss = None
-    out = {
-        "metric": "PDHG iterations/sec" if args.solver == "pdlp" else "PDHG iterations/sec (HiPDLP path)",
-        "value": st.iters / elapsed, "unit": "it/s", "n_gpus": world,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_step, "higher_is_better": True,
-        "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": cfg["name"], "m": m, "n": n, "nnz": nnz,
-                   "parallelism": "single GPU" if world == 1 else "row-block x%d, %s" % (world, exchange),
-                   "options": "presolve=off, kkt_tolerance=1e-4, adaptive step + restarts (reference defaults)"},
-        "trial_steps": int(st.trials), "rejected_trials": int(st.trials - st.iters), "checks": int(st.checks),
-        "trial_launches": int(S.stage("trial_launches")[0]) if args.solver == "pdlp" else 2,
-        # launches of one check iteration queued behind the trial batches (0: the host drives the checks and waits for them)
-        "check_launches": int(S.stage("check_launches")[0]) if args.solver == "pdlp" else None,
-        "restarts": int(st.restarts), "setup_seconds": t_setup, "ranks_bit_identical": rank_consistent,
-        "exchange_fallback": exchange_fallback, "exchange": exchange if world > 1 else None, "exchange_waits": exchange_waits,
-        "startup_ms_first_40": startup_ms,
-        # `value` / `ms_per_step` / `checks`: this window — whole check periods of the reference's schedule
-        "timed_window": "iterations %d..%d" % (val_start, val_start + int(st.iters)), "timed_steps": int(st.iters),
-        "steps_note": "`steps` / `warmup` echo the flags; `value` and `ms_per_step` are over `timed_steps` iterations (whole check "
-                      "periods of the reference's schedule); the flags' own K-step window is `window_of_the_K_steps`",
-        "window_of_the_K_steps": k_window,
+    out.update({
+        "ranks_bit_identical": rank_consistent, "exchange_waits": exchange_waits,
+        "steps_note": "`steps` / `warmup` echo the flags; `value` and `ms_per_step` are over the `timed_steps` = K steps behind "
+                      "the warm-up; `whole_check_periods` is a window of whole check periods of the reference's schedule, on "
+                      "which the figures below are computed",
         "iter_algorithmic_bytes": b_iter,
         "iter_hbm_gbs": b_iter / (ms_step * 1e-3) / 1e9,
         "iter_hbm_frac_of_peak": b_iter / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS / world,
@@ -501,7 +561,7 @@ def main():
                                     ("spmv_aty_interact_decide_primal" if fused else "spmv_aty_interact"):
                                         {"ms": k_aty, "algorithmic_bytes": b_aty / world, "frac": b_aty / world / (k_aty * 1e-3) / 1e9 / HBM_PEAK_GBS}},
                      "isolated_relaunch_ms": {"spmv_ax_dual": iso_ax, "spmv_aty_interact": iso_aty}},
-    }
+    })
     if args.solver == "pdlp" and not cfg.get("qp"):
         # the model of DESIGN.md §6 for this LP, fed with THIS run's kernel times (us): the two SpMV launches re-launched in
         # isolation on one GPU (what a rank runs on its 1/G share; the fused A'y launch would carry the primal step, which the
@@ -520,12 +580,6 @@ def main():
                 out["scaling_model"]["G=%d" % G]["speedup_vs_this_run"] = one / out["scaling_model"]["G=%d" % G]["us_per_trial"]
         if world > 1:
             out["scaling_model"]["measured_us_per_trial"] = ms_step * 1e3 * st.iters / max(int(st.trials), 1)
-    if cfg.get("qp"):
-        out["metric"] = "PDHG iterations/sec (QP prox path)"
-        out["parity"] = ("unpinned: the reference has no PDLP for QPs (HighsOptions.cpp:1178-1181); optimal objectives are "
-                         "pinned on the reference's QP solver for small instances (tests/golden/reference_qp.json)")
-    if args.solver == "hipdlp":
-        out["config"]["options"] = "presolve=off, kkt_tolerance=1e-4, Halpern restarts + PID primal weight (reference defaults)"
     if (cfg.get("structured") or cfg.get("staircase")) and world == 1 and args.solver == "pdlp":
         # the dense linking rows (> 256 nonzeros) are cut into segment tasks that run as extra workgroups of the SAME
         # launch: what they add to the plain A x (they hold 20 % of the nonzeros of this LP)
@@ -549,13 +603,8 @@ def main():
             cb = cpu_baseline(sp_.struct, cfg, (lo, hi), args.solver)
             out["cpu_baseline"] = cb
             if cb:
-                out["speedup_vs_cpu_pdlp"] = out["value"] / cb["value"]
-    S.close()
-    if rank == 0:
-        print(json.dumps(out))
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+                out["speedup_vs_cpu_pdlp"] = out["whole_check_periods"]["value"] / cb["value"]
+    finish()
 
 
 if __name__ == "__main__":

@@ -25,7 +25,7 @@ def test_bench_two_ranks_one_device(world, solver_name, fused):
     port = 29700 + os.getpid() % 200 + world
     cmd = ["timeout", "400", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world),
-           "--config", "a", "--steps", "400", "--warmup", "80", "--solver", solver_name]
+           "--config", "a", "--steps", "400", "--warmup", "80", "--solver", solver_name, "--full"]
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
@@ -60,7 +60,7 @@ def test_bench_rccl_exchange_when_two_devices_are_visible():
         port = 29900 + os.getpid() % 45 + 45 * k  # (a port of its own per launch)
         cmd = ["timeout", "400", sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
                "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2",
-               "--config", "a", "--steps", "400", "--warmup", "80"]
+               "--config", "a", "--steps", "400", "--warmup", "80", "--full"]
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, cwd=ROOT)
         assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
         d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])

@@ -2,10 +2,11 @@
 own reader.  CPU only.
 
 tests/golden/reference_mps.json holds digests of what Highs_readModel of the reference builds for every MPS file
-of its check/instances and for the edge cases of tests/golden/mps_cases/ (make_golden_mps.py).  The reference's
-instance files exist in the build container only; the edge cases and everything derived from committed fixtures
-run anywhere."""
+of its check/instances and for the edge cases of tests/golden/mps_cases/ (make_golden_mps.py).  Those instance files
+are committed gzip-compressed under tests/golden/mps_instances/ and inflated into a temporary directory, so that the
+reader sees the same plain files; only the reference's own Catch2 cases need the reference tree itself."""
 import glob
+import gzip
 import hashlib
 import json
 import os
@@ -94,10 +95,11 @@ REF_KEYS = sorted(k for k in REF if k.startswith("ref/"))
 CASE_KEYS = sorted(k for k in REF if k.startswith("case/"))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_INSTANCES), reason="the reference's instance files exist in the build container only")
 @pytest.mark.parametrize("key", REF_KEYS)
-def test_reference_instances_read_as_the_reference_reads_them(key):
-    path = os.path.join(REF_INSTANCES, key[4:])
+def test_reference_instances_read_as_the_reference_reads_them(key, tmp_path):
+    with gzip.open(os.path.join(GOLD, "mps_instances", key[4:] + ".gz")) as f:
+        (tmp_path / key[4:]).write_bytes(f.read())
+    path = str(tmp_path / key[4:])
     for threads in (1, 3, 8):
         check_against_reference(path, key, threads)
 

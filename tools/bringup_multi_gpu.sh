@@ -6,7 +6,7 @@
 #   1 peers     device count, peer-access matrix                                  (tools/bringup_multi_gpu.py peers)
 #   2 mesh      HIP IPC arena mapping + the exchange's known-answer self-test + flag-hop latency + 200 sharded iterations
 #   3 rccl      ncclAllReduce with N ranks (torch.distributed, backend nccl = RCCL)
-#   4 bench     python bench.py --gpus 2 / 4 / .. / N (mesh -> mesh with fences -> the same with a kernel per exchange step -> RCCL
+#   4 bench     python bench.py --full --gpus 2 / 4 / .. / N (mesh -> mesh with fences -> the same with a kernel per exchange step -> RCCL
 #               fall-back chain inside bench.py):
 #               the N > 1 line carries ranks_bit_identical, exchange, exchange_fallback, exchange_waits per phase next to scaling_model
 # Nothing here needs the reference tree or the network.
@@ -40,7 +40,7 @@ done
 if [ "$NDEV" -ge 2 ]; then
   stage rccl 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29531 tools/bringup_multi_gpu.py rccl
   for W in $(seq 2 $N | awk '$1==2||$1==4||$1==8||$1=='$N); do
-    res=$(timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port 29532 bench.py --gpus $W --steps 20 --warmup 5 2>$OUT/bench_w$W.err | grep '^{' | tail -1)
+    res=$(timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $W --master-addr 127.0.0.1 --master-port 29532 bench.py --full --gpus $W --steps 20 --warmup 5 2>$OUT/bench_w$W.err | grep '^{' | tail -1)
     if [ -n "$res" ]; then echo "$res" > $OUT/bench_w$W.json
       say "$(echo "$res" | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps({'stage':'bench','ok':bool(d.get('ranks_bit_identical')),'world':d['n_gpus'],'value':d['value'],'ms_per_step':d['ms_per_step'],'exchange':d.get('exchange'),'exchange_fallback':d.get('exchange_fallback'),'exchange_waits':d.get('exchange_waits'),'model_us_per_trial':(d.get('scaling_model') or {}).get('G=%d'%d['n_gpus'],{}).get('us_per_trial'),'measured_us_per_trial':(d.get('scaling_model') or {}).get('measured_us_per_trial')}))")"
     else say "{\"stage\": \"bench\", \"ok\": false, \"world\": $W, \"error\": \"no JSON line; stderr in $OUT/bench_w$W.err\"}"; fi

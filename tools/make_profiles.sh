@@ -2,7 +2,7 @@
 # tools/make_profiles.sh ROUND — regenerates every file under profiles/ with ONE command on a GPU box
 # (run through gpurun; everything is written to gpurun_out/profiles_ROUND/, then copied to profiles/ by hand or
 # by `tools/make_profiles.sh ROUND collect` in the build container).
-#   bench lines     : python bench.py for the headline config (default flags and the driver's --steps 20 --warmup 5),
+#   bench lines     : python bench.py --full for the headline config (default flags and the driver's --steps 20 --warmup 5),
 #                     configs a / c / qp and the HiPDLP path
 #   kernel stats    : rocprofv3 --kernel-trace --stats of the headline bench command (N=1)
 #   PMC traffic     : FETCH_SIZE / WRITE_SIZE of the fused SpMV kernels, one counter per pass (never combined with
@@ -27,27 +27,27 @@ cd $R
 # carry THIS tree's counters in roofline.traffic (bench.py reads profiles/pmc_traffic.json)
 bash tools/pmc_traffic.sh $RND b a c d e f qp qpn > $OUT/pmc_traffic.log 2>&1
 cp $OUT/pmc_traffic.json $R/profiles/pmc_traffic.json
-python bench.py > $OUT/${RND}_bench_1M.json 2> $OUT/bench_1M.err
-python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/${RND}_bench_1M_driver_flags.json 2>> $OUT/bench_1M.err
-python bench.py --config a > $OUT/${RND}_bench_100k.json 2>> $OUT/bench_1M.err
-python bench.py --config c > $OUT/${RND}_bench_structured.json 2>> $OUT/bench_1M.err
-python bench.py --config d > $OUT/${RND}_bench_staircase_dense_columns.json 2>> $OUT/bench_1M.err
-python bench.py --config e > $OUT/${RND}_bench_heldout_tall.json 2>> $OUT/bench_1M.err
-python bench.py --config f > $OUT/${RND}_bench_heldout_powerlaw_band.json 2>> $OUT/bench_1M.err
-python bench.py --config qp > $OUT/${RND}_bench_qp.json 2>> $OUT/bench_1M.err
-python bench.py --config qpn > $OUT/${RND}_bench_qp_sparse_hessian.json 2>> $OUT/bench_1M.err
-python bench.py --solver hipdlp > $OUT/${RND}_bench_hipdlp_1M.json 2>> $OUT/bench_1M.err
+python bench.py --full > $OUT/${RND}_bench_1M.json 2> $OUT/bench_1M.err
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/${RND}_bench_1M_driver_flags.json 2>> $OUT/bench_1M.err
+python bench.py --full --config a > $OUT/${RND}_bench_100k.json 2>> $OUT/bench_1M.err
+python bench.py --full --config c > $OUT/${RND}_bench_structured.json 2>> $OUT/bench_1M.err
+python bench.py --full --config d > $OUT/${RND}_bench_staircase_dense_columns.json 2>> $OUT/bench_1M.err
+python bench.py --full --config e > $OUT/${RND}_bench_heldout_tall.json 2>> $OUT/bench_1M.err
+python bench.py --full --config f > $OUT/${RND}_bench_heldout_powerlaw_band.json 2>> $OUT/bench_1M.err
+python bench.py --full --config qp > $OUT/${RND}_bench_qp.json 2>> $OUT/bench_1M.err
+python bench.py --full --config qpn > $OUT/${RND}_bench_qp_sparse_hessian.json 2>> $OUT/bench_1M.err
+python bench.py --full --solver hipdlp > $OUT/${RND}_bench_hipdlp_1M.json 2>> $OUT/bench_1M.err
 for cfg in b c d e f qp; do  # per-block phase profile of the two slab launches of a trial (development buffer, 100 MHz wall clock)
   echo "== bench.py --config $cfg (PDLP_MI355X_SLAB_PROF=1)"
-  PDLP_MI355X_SLAB_PROF=1 python bench.py --config $cfg --cpu-iters 0 2>&1 >/dev/null | grep "slab launch"
+  PDLP_MI355X_SLAB_PROF=1 python bench.py --full --config $cfg --cpu-iters 0 2>&1 >/dev/null | grep "slab launch"
 done > $OUT/${RND}_slab_phase_profile.log
 python tools/solve_times.py > $OUT/${RND}_small_lp_times.log 2>&1
 python tools/small_loop.py 25fv47 80bau3b >> $OUT/${RND}_small_lp_times.log 2>&1
 ( cd /tmp; export TMPDIR=/tmp
-  rocprofv3 --kernel-trace --stats -d $OUT/trace -o t --output-format csv -- python $R/bench.py --steps 2000 --warmup 200 --cpu-iters 0 > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats -d $OUT/trace -o t --output-format csv -- python $R/bench.py --full --steps 2000 --warmup 200 --cpu-iters 0 > /dev/null 2>&1
   cp $OUT/trace/t_kernel_stats.csv $OUT/${RND}_bench_1M_kernel_stats.csv
   cp $OUT/trace/t_kernel_trace.csv $OUT/kernel_trace_1M.csv 2>/dev/null
-  rocprofv3 --kernel-trace --stats -d $OUT/trace_h -o t --output-format csv -- python $R/bench.py --solver hipdlp --cpu-iters 0 > /dev/null 2>&1
+  rocprofv3 --kernel-trace --stats -d $OUT/trace_h -o t --output-format csv -- python $R/bench.py --full --solver hipdlp --cpu-iters 0 > /dev/null 2>&1
   cp $OUT/trace_h/t_kernel_stats.csv $OUT/${RND}_bench_hipdlp_1M_kernel_stats.csv
 )
 python - <<PY

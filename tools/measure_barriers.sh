@@ -7,7 +7,7 @@ echo "80bau3b sweep barrier:"; PDLP_MI355X_HIER_BARRIER=0 python tools/small_loo
 echo "80bau3b hierarchical:"; PDLP_MI355X_HIER_BARRIER=1 python tools/small_loop.py 80bau3b 2>&1 | grep -v amdgpu.ids
 echo "25fv47 all XCDs, sweep / hierarchical:"; PDLP_MI355X_XCD_LOCAL=0 PDLP_MI355X_HIER_BARRIER=0 python tools/small_loop.py 25fv47 2>&1 | grep -v amdgpu.ids
 PDLP_MI355X_XCD_LOCAL=0 PDLP_MI355X_HIER_BARRIER=1 python tools/small_loop.py 25fv47 2>&1 | grep -v amdgpu.ids
-timeout 300 python bench.py --config a > $O/a_persistent.json 2> $O/a_persistent.err
+timeout 300 python bench.py --full --config a > $O/a_persistent.json 2> $O/a_persistent.err
 python - $O/a_persistent.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

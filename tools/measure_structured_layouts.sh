@@ -5,7 +5,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/r03i; mkdir -p $O
 for mode in auto 0; do
   if [ $mode = auto ]; then unset PDLP_MI355X_SLAB; else export PDLP_MI355X_SLAB=$mode; fi
-  timeout 300 python bench.py --config c > $O/c_$mode.json 2> $O/c_$mode.err
+  timeout 300 python bench.py --full --config c > $O/c_$mode.json 2> $O/c_$mode.err
   python - $O/c_$mode.json <<'PY'
 import json,sys
 d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -16,14 +16,14 @@ else
 fi
 line() { python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('$1', round(d['value']), round(d['ms_per_step']*1e3,2), {k:round(v['ms']*1e3,1) for k,v in d['roofline']['per_kernel'].items()})"; }
 for cfg in ${CONFIGS:-b c d a qp}; do
-  python bench.py --config $cfg --cpu-iters 0 2>$OUT/bench_$cfg.err | tee $OUT/bench_$cfg.json | line $cfg
+  python bench.py --full --config $cfg --cpu-iters 0 2>$OUT/bench_$cfg.err | tee $OUT/bench_$cfg.json | line $cfg
 done
 for cfg in ${PROF_CONFIGS:-b c d}; do
   echo "== bench.py --config $cfg (PDLP_MI355X_SLAB_PROF=1)"
-  PDLP_MI355X_SLAB_PROF=1 python bench.py --config $cfg --cpu-iters 0 2>&1 >/dev/null | grep "slab launch"
+  PDLP_MI355X_SLAB_PROF=1 python bench.py --full --config $cfg --cpu-iters 0 2>&1 >/dev/null | grep "slab launch"
 done | tee $OUT/slab_phase_profile.log
 if [ -n "${EXTRA_A:-}" ]; then
   echo "== config a forced onto the slab layout (fused 2-launch trial) vs the persistent loop"
-  PDLP_MI355X_SLAB=1 python bench.py --config a --cpu-iters 0 2>/dev/null | line a_slab_fused
-  PDLP_MI355X_SLAB=1 PDLP_MI355X_FUSED=0 python bench.py --config a --cpu-iters 0 2>/dev/null | line a_slab_3launch
+  PDLP_MI355X_SLAB=1 python bench.py --full --config a --cpu-iters 0 2>/dev/null | line a_slab_fused
+  PDLP_MI355X_SLAB=1 PDLP_MI355X_FUSED=0 python bench.py --full --config a --cpu-iters 0 2>/dev/null | line a_slab_3launch
 fi

@@ -14,16 +14,16 @@ if [ -z "${SKIP_TESTS:-}" ]; then
 fi
 line() { python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('$1', round(d['value']), round(d['ms_per_step']*1e3,2), {k:round(v['ms']*1e3,1) for k,v in d['roofline']['per_kernel'].items()})"; }
 for cfg in ${CONFIGS:-c d b}; do
-  python bench.py --config $cfg --cpu-iters 0 2>$OUT/bench_$cfg.err | tee $OUT/bench_$cfg.json | line $cfg
+  python bench.py --full --config $cfg --cpu-iters 0 2>$OUT/bench_$cfg.err | tee $OUT/bench_$cfg.json | line $cfg
   if [ $cfg != b ]; then
-    PDLP_MI355X_AFFINE_TASKS=0 python bench.py --config $cfg --cpu-iters 0 2>$OUT/bench_${cfg}_major_order.err | tee $OUT/bench_${cfg}_major_order.json | line ${cfg}_tasks_in_major_order
+    PDLP_MI355X_AFFINE_TASKS=0 python bench.py --full --config $cfg --cpu-iters 0 2>$OUT/bench_${cfg}_major_order.err | tee $OUT/bench_${cfg}_major_order.json | line ${cfg}_tasks_in_major_order
   fi
 done
 for cfg in ${PROF_CONFIGS:-c d}; do
   echo "== bench.py --config $cfg (PDLP_MI355X_SLAB_PROF=1)"
-  PDLP_MI355X_SLAB_PROF=1 python bench.py --config $cfg --cpu-iters 0 2>&1 >/dev/null | grep "slab launch"
+  PDLP_MI355X_SLAB_PROF=1 python bench.py --full --config $cfg --cpu-iters 0 2>&1 >/dev/null | grep "slab launch"
   echo "== the same, PDLP_MI355X_AFFINE_TASKS=0"
-  PDLP_MI355X_AFFINE_TASKS=0 PDLP_MI355X_SLAB_PROF=1 python bench.py --config $cfg --cpu-iters 0 2>&1 >/dev/null | grep "slab launch"
+  PDLP_MI355X_AFFINE_TASKS=0 PDLP_MI355X_SLAB_PROF=1 python bench.py --full --config $cfg --cpu-iters 0 2>&1 >/dev/null | grep "slab launch"
 done | tee $OUT/slab_phase_profile.log
 if [ -z "${SKIP_PMC:-}" ]; then
   bash tools/pmc_traffic.sh $TAG ${PMC_CONFIGS:-c d} > $OUT/pmc_traffic.log 2>&1

@@ -14,8 +14,8 @@ OUT=gpurun_out/$TAG; mkdir -p $OUT
 line() { python -c "import sys,json; d=json.loads(sys.stdin.readlines()[-1]); print('$1', round(d['value']), round(d['ms_per_step']*1e3,2), {k:round(v['ms']*1e3,1) for k,v in d['roofline']['per_kernel'].items()}, 'setup', round(d['setup_seconds'],3))"; }
 run() { # name cfg env...
   local name=$1 cfg=$2; shift 2
-  env "$@" python bench.py --config $cfg --cpu-iters 0 2>$OUT/$name.err | line $name
-  env "$@" PDLP_MI355X_SLAB_PROF=1 python bench.py --config $cfg --cpu-iters 0 2>&1 >/dev/null | grep "slab launch" | grep -E "fused" | grep -E "arrival|barrier|kernel"
+  env "$@" python bench.py --full --config $cfg --cpu-iters 0 2>$OUT/$name.err | line $name
+  env "$@" PDLP_MI355X_SLAB_PROF=1 python bench.py --full --config $cfg --cpu-iters 0 2>&1 >/dev/null | grep "slab launch" | grep -E "fused" | grep -E "arrival|barrier|kernel"
 }
 for cfg in $CFGS; do
   for rep in $(seq 1 ${REPS:-1}); do
