@@ -317,20 +317,12 @@ __global__ __launch_bounds__(kVecThreads) void k_long_groups(const LongMat L, co
 //            reference's summation order) and runs the epilogue.
 template <int EPI, int CHUNK>
 __global__ __launch_bounds__(kSpmvThreads) void k_spmv(const SpmvArgs a) {
-  if (EPI == kAtyFused && a.st->halted) {  // keep the two state slots identical while the queue drains
-    if (blockIdx.x == 0 && threadIdx.x < sizeof(DevState) / 4)
-      reinterpret_cast<uint32_t*>(a.stOut)[threadIdx.x] = reinterpret_cast<const uint32_t*>(a.st)[threadIdx.x];
-    return;
-  }
+  static_assert(EPI != kAtyFused, "the fused trial is slab-only (k_spmv_slab)");
   if (usesDevState(EPI) && a.st->halted) return;
   if ((EPI == kHalpernPrimal || EPI == kHalpernDual) && a.h.hs->halted) return;  // (HiPDLP's device-driven loop has ended)
   if (EPI == kPlain && !gateOpen(a.gate)) return;
   __shared__ double prod[CHUNK + CHUNK / 8 + 8];
   __shared__ double scratch[2][kSpmvThreads / kWave];
-  // kAtyFused (the 2-launch trial on the stream layout): reduction scratch of the decision and the state record
-  __shared__ double tscr[EPI == kAtyFused ? 4 : 1][kVecThreads / kWave];
-  __shared__ uint32_t shWords[EPI == kAtyFused ? (sizeof(DevState) + 3) / 4 : 1];
-  __shared__ int barVerdict;
 
   const int tid = threadIdx.x;
   Epi<EPI> epi(a);
@@ -359,10 +351,6 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv(const SpmvArgs a) {
     int qb = a.A.beg[rr] - p0;
     int qe = a.A.beg[rr + 1] - p0;
     Pre pre = epi.prefetch(vecIndex(rr));
-    // kAtyFused: what the NEXT primal step needs of this lane's first major and no decision can change (c, l, u)
-    Pre fix{0.0, 0.0, 0.0, 0.0, 0.0};
-    double keepX = 0.0, keepS = 0.0;  // x+ and (A'y+) of that major, for the step after an accepted trial
-    if (EPI == kAtyFused) { fix.a = ldStream(a.v.cost + rr); fix.b = ldStream(a.v.lower + rr); fix.c = ldStream(a.v.upper + rr); }
     // phase 1: kPer unit-stride loads of idx/val per lane, all issued before the
     // dependent gathers, so a wave keeps 3*kPer memory operations in flight
     const int last = cnt > 0 ? cnt - 1 : 0;  // idx/val carry one pad element
@@ -392,66 +380,8 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv(const SpmvArgs a) {
       }
       const double s = majorSum(prod, qb, qe);
       epi.apply(vecIndex(r), s, pre);
-      if (EPI == kAtyFused && r == rFirst) { keepX = pre.b; keepS = s; }
     }
-    if (EPI == kAtyFused) fix.d = ldStream(a.v.xSum + rr);  // in flight across the barrier and the decision
     epi.template finish<kSpmvThreads>(a.A.partOffset + blk, scratch);
-    if (EPI == kAtyFused) {
-      // ---- every block's partials in HBM -> decision (identical in every block) -> the next trial's primal step on the
-      // block's majors (pdlp_kernels.hip k_spmv_slab has the same tail) ----
-      DevState* sh = reinterpret_cast<DevState*>(shWords);
-      if (tid < kWave) {
-        const int nExp = a.A.nBlocks + (a.st->nTrials + 1 == a.faultTrial ? 1 : 0);
-        const int verdict = gridBarrier(a.bar, (int)blockIdx.x, nExp, (unsigned long long)a.st->nTrials + 1ull, tid, a.barLimit);
-        if (tid == 0) barVerdict = verdict;
-      }
-      if (tid >= kWave && tid - kWave < (int)(sizeof(DevState) / 4)) shWords[tid - kWave] = reinterpret_cast<const uint32_t*>(a.st)[tid - kWave];
-      __syncthreads();
-      if (barVerdict != kBarOk) {  // not every block of this launch was resident in time: the trial stays undecided (fusedBarrierFailed)
-        fusedBarrierFailed(a.stOut, shWords, barVerdict, blockIdx.x == 0, tid);
-        return;
-      }
-      const unsigned long long timedOut = tid == 0 ? __hip_atomic_load(a.bar + a.A.nBlocks, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
-      double dY2, dX2, inter;
-      trialSumsT<1>(a.partDY, a.nDY, a.part0, a.part1, a.nDX, tscr, dY2, dX2, inter);
-      if (tid == 0) {
-        decideUpdate<true>(sh, dX2, dY2, inter);
-        if (timedOut) sh->commError = 1;
-      }
-      __syncthreads();
-      const int halted = sh->halted, curN = sh->cur, accepted = sh->lastAccepted;
-      const double tau = sh->tau, avgWx = sh->avgWx;
-      if (blockIdx.x == 0 && tid < (int)(sizeof(DevState) / 4)) {  // pending = 0 (decideCore); avgWx: added to xSum below
-        uint32_t w = shWords[tid];
-        constexpr int kAvgWxWord = offsetof(DevState, avgWx) / 4;
-        if (!halted && (tid == kAvgWxWord || tid == kAvgWxWord + 1)) w = 0u;
-        reinterpret_cast<uint32_t*>(a.stOut)[tid] = w;
-      }
-      if (halted) return;
-      const double* __restrict__ xBase = a.v.x[curN];
-      const double* __restrict__ atyBase = a.v.aty[curN];
-      double* __restrict__ xOut = a.v.x[curN ^ 1];
-      for (int r = rFirst; r < r1; r += kSpmvThreads) {
-        double xb, ab, c, l, u, xs;
-        if (r == rFirst) {  // from registers (a rejected trial, 3 %, fetches x and A'y again)
-          xb = accepted ? keepX : ldStream(xBase + r); ab = accepted ? keepS : ldStream(atyBase + r);
-          c = fix.a; l = fix.b; u = fix.c; xs = fix.d;
-        } else {            // (more than 256 majors in the block: short columns)
-          xb = ldStream(xBase + r); ab = ldStream(atyBase + r);
-          c = ldStream(a.v.cost + r); l = ldStream(a.v.lower + r); u = ldStream(a.v.upper + r); xs = ldStream(a.v.xSum + r);
-        }
-        if (avgWx != 0.0) stStream(a.v.xSum + r, xs + avgWx * xb);  // deferred PDHG_Update_Average (step.c:437)
-        double t = xb;
-        t += (-tau) * c;
-        t += tau * ab;
-        if (a.v.qdiag) t = t / (1.0 + tau * ldStream(a.v.qdiag + r));
-        t = t < u ? t : u;
-        t = t > l ? t : l;
-        xOut[r] = t;  // gathered by the A x+ kernel: ordinary store
-      }
-      return;
-    }
-    return;
   }
 }
 
@@ -480,16 +410,17 @@ __global__ __launch_bounds__(kSpmvThreads) void k_spmv(const SpmvArgs a) {
 constexpr int kSlabSlots = 3;  // register pipeline depth (groups of 64 entries per wave)
 // TWO: register budget for two resident blocks per CU (8 waves per SIMD) — the extra blocks with the segment
 // tasks of the long majors then run NEXT to the streaming blocks instead of after them.
-// LATE (kAtyFused): the operands of the next primal step that no decision can change (c, l, u, xSum, q) are fetched behind
-// the block's ARRIVAL at the grid barrier instead of travelling with the stream, and for TWICE as many columns per thread
-// (the stream's registers are free by then): 8192 columns per block (4096 in the 64-register variant) are stepped from
-// registers behind the barrier, nothing but the stores left there (round 6: config c spent 13 us behind its barrier on
-// 8200 columns per block, half of them fetched there).
-#ifndef PDLP_TWO_EXTRA
-#define PDLP_TWO_EXTRA 0
-#endif
-template <int EPI, bool TWO, int NB, int GD, bool LATE = false, bool CC = false, bool ULO = false>
+// kAtyFused: the operands of the next primal step that no decision can change (c, l, u, xSum, q) are fetched behind the
+// block's ARRIVAL at the grid barrier, when the stream's registers are free.  In the 128-register variant (LATE = !TWO) for
+// TWICE as many columns per thread: 8192 columns per block (4096 in the 64-register variant) are stepped from registers
+// behind the barrier, nothing but the stores left there (round 6: config c spent 13 us behind its barrier on 8200 columns
+// per block, half of them fetched there).
+// CC, ULO (kAtyFused): see launchSpmvAtyFusedPrimal.
+template <int EPI, bool TWO, bool CC = false, bool ULO = false>
 __global__ __launch_bounds__(kSlabThreads, TWO ? 2 * kSlabThreads / 256 : kSlabThreads / 256) void k_spmv_slab(const SpmvArgs a) {
+  constexpr int NB = kSlabSlots;  // register pipeline slots
+  constexpr int GD = 1;           // gather distance (groups ahead of the accumulation)
+  constexpr bool LATE = EPI == kAtyFused && !TWO;
   if (EPI == kAtyFused && a.st->halted) {  // keep the two state slots identical while the queue drains
     if (blockIdx.x == 0 && threadIdx.x < sizeof(DevState) / 4)
       reinterpret_cast<uint32_t*>(a.stOut)[threadIdx.x] = reinterpret_cast<const uint32_t*>(a.st)[threadIdx.x];
@@ -559,27 +490,15 @@ __global__ __launch_bounds__(kSlabThreads, TWO ? 2 * kSlabThreads / 256 : kSlabT
     const int r = rBase + tid + k * kSlabThreads;
     pre[k] = epi.prefetch(r < rEnd ? r : rEnd - 1);
   }
-  // kAtyFused: the operands of the NEXT primal step that no decision can change (c, l, u, xSum) travel with the stream
-  // (not in the 64-register variant that leaves room for the task workgroups: there they are fetched behind the barrier)
-  constexpr bool kFixEarly = !TWO && !LATE;
-  // columns per thread stepped from registers: the kSlabPre whose epilogue operands travel with the stream, plus kExtra whose
-  // operands are fetched behind the arrival (LATE: as many again; the 64-register variant: PDLP_TWO_EXTRA, measured)
-  constexpr int kExtra = EPI != kAtyFused ? 0 : LATE ? kSlabPre : TWO ? PDLP_TWO_EXTRA : 0;
+  // kAtyFused: columns per thread stepped from registers: the kSlabPre whose epilogue operands travel with the stream, plus
+  // kExtra (LATE: as many again) whose x+ is fetched behind the arrival
+  constexpr int kExtra = LATE ? kSlabPre : 0;
   constexpr int kFixN = EPI == kAtyFused ? kSlabPre + kExtra : 1;
   Pre fix[kFixN];
   double xbLate[kExtra > 0 ? kExtra : 1];  // x+ of the extra columns (the first ones': pre[k].b)
   // bounds that ALL columns of this block share (IterVecs::colBlockUni): taken from two scalars instead of 8 / 16 bytes per column
   const int uniB = (EPI == kAtyFused && a.v.colBlockUni) ? ldUniform(a.v.colBlockUni + blk) : 0;
   const double lo0 = uniB ? ldUniform(a.v.colBlockBounds + 2 * blk) : 0.0, up0 = uniB ? ldUniform(a.v.colBlockBounds + 2 * blk + 1) : 0.0;  // (scalar registers)
-  if (EPI == kAtyFused && kFixEarly) {
-#pragma unroll
-    for (int k = 0; k < kSlabPre; ++k) {
-      const int r0_ = rBase + tid + k * kSlabThreads;
-      const int r = r0_ < rEnd ? r0_ : rEnd - 1;
-      fix[k].a = ldStream(a.v.cost + r); fix[k].b = ldStream(a.v.lower + r); fix[k].c = ldStream(a.v.upper + r);
-      fix[k].d = 0.0; fix[k].e = a.v.qdiag ? ldStream(a.v.qdiag + r) : 0.0;  // (QP: the diagonal of Q of the prox step)
-    }
-  }
 
   // Consume one 64-entry group of this wave: products to the wave's LDS strip, the first lane of each run of equal
   // local majors adds the run, left to right, onto the major's accumulator (ascending stretches one after the other
@@ -726,14 +645,7 @@ __global__ __launch_bounds__(kSlabThreads, TWO ? 2 * kSlabThreads / 256 : kSlabT
     gridArrive(a.bar, (int)blockIdx.x, (unsigned long long)a.st->nTrials + 1ull, lane);
     profStamp(4);  // (the block's published words have landed, its arrival word is on its way)
   }
-  if (EPI == kAtyFused && kFixEarly) {  // xSum of the own columns: in flight across the barrier and the decision
-#pragma unroll
-    for (int k = 0; k < kSlabPre; ++k) {
-      const int r0_ = rBase + tid + k * kSlabThreads;
-      fix[k].d = ldStream(a.v.xSum + (r0_ < rEnd ? r0_ : rEnd - 1));
-    }
-  }
-  if (EPI == kAtyFused && !kFixEarly) {
+  if (EPI == kAtyFused) {
     // (the stream's pipeline registers are free now — the operands of the next primal step are fetched here, in flight
     // across the grid barrier and the decision instead of behind them)
 #pragma unroll
@@ -844,9 +756,9 @@ __global__ __launch_bounds__(kSlabThreads, TWO ? 2 * kSlabThreads / 256 : kSlabT
         }
       }
     }
-    // (more columns per block than that: kTail columns' operands per round trip — two in the LATE variants, where this
-    // loop only sees blocks beyond 8192 / 4096 columns and the registers hold twice as many columns across the barrier)
-    constexpr int kTail = LATE ? 2 : TWO ? 3 : kSlabPre;
+    // (more columns per block than that: kTail columns' operands per round trip — two in the LATE variant, where this
+    // loop only sees blocks beyond 8192 columns and the registers hold twice as many columns across the barrier)
+    constexpr int kTail = LATE ? 2 : 3;
     for (int lr0 = tid + kFixN * kSlabThreads; rBase + lr0 < rEnd; lr0 += kTail * kSlabThreads) {
       double xb[kTail], ab[kTail], cc[kTail], ll[kTail], uu[kTail], xs[kTail], qq[kTail];
 #pragma unroll
@@ -1266,8 +1178,8 @@ void launchSpmv(const MatView& M, SpmvArgs a, hipStream_t s) {
     const dim3 grid(M.slab.nBlocks + (nTasks + M.lng.taskGroup - 1) / M.lng.taskGroup);  // one task group per extra workgroup
     // (gather distance 2 / 3 with 4 / 6 slots measured the same as (3, 1) on the random and on the structured LP, round 3)
     // segment tasks ride along: register budget for two resident blocks per CU, so that a task block runs NEXT to a streaming one
-    if (nTasks > 0) hipLaunchKernelGGL((k_spmv_slab<EPI, true, kSlabSlots, 1>), grid, dim3(kSlabThreads), lds, s, a);
-    else hipLaunchKernelGGL((k_spmv_slab<EPI, false, kSlabSlots, 1>), grid, dim3(kSlabThreads), lds, s, a);
+    if (nTasks > 0) hipLaunchKernelGGL((k_spmv_slab<EPI, true>), grid, dim3(kSlabThreads), lds, s, a);
+    else hipLaunchKernelGGL((k_spmv_slab<EPI, false>), grid, dim3(kSlabThreads), lds, s, a);
   } else if (M.csr.nBlocks > 0 || nTasks > 0) {
     const dim3 grid(M.csr.nBlocks + (nTasks + kSpmvThreads / kWave - 1) / (kSpmvThreads / kWave)), block(kSpmvThreads);
     if (M.csr.chunk == kChunkSmall) hipLaunchKernelGGL((k_spmv<EPI, kChunkSmall>), grid, block, 0, s, a);
@@ -1305,7 +1217,7 @@ int fusedCoTaskBlocks(const MatView& At, int device) {
   // task workgroup resident at once — where its LDS request fits twice
   if (!At.useSlab || At.lng.nTasks <= 0 || At.lng.contrib != nullptr || At.slab.nBlocks <= 0) return 0;
   int perCu = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_spmv_slab<kAtyFused, true, kSlabSlots, 1>, kSlabThreads, fusedLds(At)) != hipSuccess) return 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_spmv_slab<kAtyFused, true>, kSlabThreads, fusedLds(At)) != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
   const int groups = fusedTaskGroups(At);
   if (perCu < 2 || At.slab.nBlocks > cus || groups > cus) return 0;  // (one streaming block and at most one task workgroup per CU)
@@ -1313,63 +1225,51 @@ int fusedCoTaskBlocks(const MatView& At, int device) {
 }
 int fusedAtyBlocksResident(const MatView& At, int device) {
   (void)slabProf();  // (development buffer: allocated at set-up, never inside a stream capture)
-  // long columns: the slab kernel runs their segment tasks inside the fused launch (co-resident task workgroups,
-  // MatView::coTaskBlocks, or the streaming blocks themselves, SpmvArgs::inlineTasks); not the stream-layout kernel, and
+  // the fused trial runs on the slab layout only.  Long columns: the slab kernel runs their segment tasks inside the fused
+  // launch (co-resident task workgroups, MatView::coTaskBlocks, or the streaming blocks themselves, SpmvArgs::inlineTasks),
   // not beyond kLongSlotCap long columns (their contributions need the k_long_groups launch)
-  if (At.lng.nTasks > 0 && (!At.useSlab || At.lng.contrib != nullptr)) return 0;
+  if (!At.useSlab || At.slab.nBlocks <= 0 || (At.lng.nTasks > 0 && At.lng.contrib != nullptr)) return 0;
   int perCu = 0, cus = 0;
-  hipError_t e;
-  if (At.useSlab) {
-    if (At.slab.nBlocks <= 0) return 0;
-    e = At.coTaskBlocks > 0
-            ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_spmv_slab<kAtyFused, true, kSlabSlots, 1>, kSlabThreads, fusedLds(At))
-            : hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_spmv_slab<kAtyFused, false, kSlabSlots, 1, true>, kSlabThreads, fusedLds(At));
-  } else {
-    if (At.csr.nBlocks <= 0) return 0;
-    e = At.csr.chunk == kChunkSmall ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_spmv<kAtyFused, kChunkSmall>, kSpmvThreads, 0)
-                                    : hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_spmv<kAtyFused, kChunk>, kSpmvThreads, 0);
-  }
+  const hipError_t e = At.coTaskBlocks > 0
+                           ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_spmv_slab<kAtyFused, true>, kSlabThreads, fusedLds(At))
+                           : hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_spmv_slab<kAtyFused, false>, kSlabThreads, fusedLds(At));
   if (e != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
   return perCu * cus;
 }
-int fusedAtyBlocks(const MatView& At) { return At.useSlab ? At.slab.nBlocks + At.coTaskBlocks : At.csr.nBlocks; }
+int fusedAtyBlocks(const MatView& At) { return At.slab.nBlocks + At.coTaskBlocks; }
 void launchSpmvAtyFusedPrimal(const MatView& At, const IterVecs& v, const DevState* stIn, DevState* stOut,
                               const double* partDY, int32_t nDY, double* partDX, double* partInter, unsigned long long* bar,
                               hipStream_t s, int32_t timeoutMs, int32_t faultTrial) {
   SpmvArgs a{};
   a.barLimit = (unsigned long long)(timeoutMs > 0 ? timeoutMs : 1000) * 100000ull;
   a.faultTrial = faultTrial;
-  a.coTaskBlocks = At.useSlab && At.lng.nTasks > 0 ? At.coTaskBlocks : 0;
-  a.inlineTasks = At.useSlab && At.lng.nTasks > 0 && a.coTaskBlocks == 0 ? 1 : 0;
+  a.coTaskBlocks = At.lng.nTasks > 0 ? At.coTaskBlocks : 0;
+  a.inlineTasks = At.lng.nTasks > 0 && a.coTaskBlocks == 0 ? 1 : 0;
   a.touchTail = At.touchTail;
   a.st = stIn; a.v = v; a.part0 = partDX; a.part1 = partInter;
   a.stOut = stOut; a.partDY = partDY; a.nDY = nDY; a.nDX = At.nPartials; a.bar = bar;
-  if (At.useSlab && At.slab.nBlocks <= 512) a.prof = slabProf();
+  if (At.slab.nBlocks <= 512) a.prof = slabProf();
   a.xcdMap = At.xcdMap; a.L = At.lng; a.A = At.csr; a.S = At.slab;
   // (LATE — twice as many columns stepped from registers behind the barrier — in the 128-register variant only: in the
   // 64-register one, which carries the task workgroups, it spills and measured slower: config d 36.5 -> 41.2 us, round 6)
   // (CC — c, l, u of the primal step as ordinary loads where IterVecs::constCached says the Infinity Cache has room; ULO —
   // every column shares one lower bound, IterVecs::lowerUniform)
   const dim3 gridTwo(At.slab.nBlocks + a.coTaskBlocks), gridOne(At.slab.nBlocks), block(kSlabThreads);
-  const size_t lds = At.useSlab ? fusedLds(At) : 0;
+  const size_t lds = fusedLds(At);
   auto launchTwo = [&](auto cc, auto ulo) {
-    hipLaunchKernelGGL((k_spmv_slab<kAtyFused, true, kSlabSlots, 1, false, decltype(cc)::value, decltype(ulo)::value>), gridTwo, block, lds, s, a);
+    hipLaunchKernelGGL((k_spmv_slab<kAtyFused, true, decltype(cc)::value, decltype(ulo)::value>), gridTwo, block, lds, s, a);
   };
   auto launchOne = [&](auto cc, auto ulo) {
-    hipLaunchKernelGGL((k_spmv_slab<kAtyFused, false, kSlabSlots, 1, true, decltype(cc)::value, decltype(ulo)::value>), gridOne, block, lds, s, a);
+    hipLaunchKernelGGL((k_spmv_slab<kAtyFused, false, decltype(cc)::value, decltype(ulo)::value>), gridOne, block, lds, s, a);
   };
   auto pick = [&](auto&& launch) {
     using T = std::true_type; using F = std::false_type;
     if (v.constCached) { if (v.lowerUniform) launch(T{}, T{}); else launch(T{}, F{}); }
     else { if (v.lowerUniform) launch(F{}, T{}); else launch(F{}, F{}); }
   };
-  if (At.useSlab && a.coTaskBlocks > 0) pick(launchTwo);
-  else if (At.useSlab) pick(launchOne);
-  else if (At.csr.chunk == kChunkSmall)
-    hipLaunchKernelGGL((k_spmv<kAtyFused, kChunkSmall>), dim3(At.csr.nBlocks), dim3(kSpmvThreads), 0, s, a);
-  else
-    hipLaunchKernelGGL((k_spmv<kAtyFused, kChunk>), dim3(At.csr.nBlocks), dim3(kSpmvThreads), 0, s, a);
+  if (a.coTaskBlocks > 0) pick(launchTwo);
+  else pick(launchOne);
 }
 void launchSpmvAtyPartial(const MatView& At, const IterVecs& v, const DevState* st, double* out, hipStream_t s) {
   SpmvArgs a{};

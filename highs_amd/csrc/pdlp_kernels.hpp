@@ -303,11 +303,11 @@ void launchDecide(DevState* st, const double* partDY, int32_t nDY, const double*
                   int32_t nDX, const double* dyGlobal, hipStream_t s, bool onlyIfPending = false,
                   const double* partQ = nullptr, int32_t nQ = 0);
 
-// ---- fused trial (single GPU, either layout): 2 launches ------------------------------------------------------
+// ---- fused trial (single GPU, slab layout): 2 launches ----------------------------------------------------------
 // aty_next = A' y_next with the movement / interaction partials as above, then — inside the same launch — a grid
 // barrier, the accept/reject decision (every block re-reduces the partials in the fixed order of k_decide), and
-// the NEXT trial's primal step on the columns the block owns: x, x+, A'y are still in registers, A'y+ in LDS, and
-// c, l, u, xSum were fetched while the matrix streamed.  Reads *stIn, block 0 writes *stOut (the other slot).
+// the NEXT trial's primal step on the columns the block owns: x+ is still in registers, A'y+ in LDS, and c, l, u,
+// xSum were fetched behind the block's arrival at the barrier.  Reads *stIn, block 0 writes *stOut (the other slot).
 // Needs every block of the grid resident at once (one 1024-thread block per CU): fusedAtyBlocksResident() tells
 // how many the device takes; the solver falls back to the 3-launch trial otherwise.  bar: one zeroed 8-byte
 // arrival word per block + one timeout flag (a wait that does not end within ~1 s sets commError instead of

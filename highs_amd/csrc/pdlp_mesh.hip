@@ -361,49 +361,6 @@ __device__ __forceinline__ double orderedSum(const PeerPtrs& S, int j) {
   return s;
 }
 
-// aty+[slice] = sum_h partial_h[slice]; movement / interaction partials of the slice
-// (cupdlp_linalg.c:772-801).
-__global__ __launch_bounds__(kVecThreads) void k_mesh_reduce_interact(const IterVecs v, DevState* st,
-                                                                      const MeshArgs ma,
-                                                                      const double* __restrict__ partial,
-                                                                      double* partDX, double* partInter) {
-  const MeshView* __restrict__ mv = ma.v; (void)mv;
-  if (st->halted || dead(ma)) return;  // (k_mesh_wait ran before: flag P has arrived)
-  __shared__ double scratch[2][kVecThreads / kWave];
-  const int cur = st->cur, nxt = cur ^ 1;
-  PeerPtrs src;
-  reduceSources(ma, partial + mv->colOff[ma.g], src);
-  const double* __restrict__ xc = v.x[cur];
-  const double* __restrict__ xn = v.x[nxt];
-  const double* __restrict__ ac = v.aty[cur];
-  double* __restrict__ an = v.aty[nxt];
-  double a0 = 0.0, a1 = 0.0;
-  const int stride = gridDim.x * blockDim.x;
-  const int last = v.n - 1;
-  for (int j0 = blockIdx.x * blockDim.x + threadIdx.x; j0 < v.n; j0 += 4 * stride) {
-    double sv[4], dxv[4], acv[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int j = min(j0 + q * stride, last);
-      sv[q] = orderedSum(src, j);
-      dxv[q] = xc[j] - xn[j];
-      acv[q] = ac[j];
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {  // accumulation order: ascending j within the lane
-      const int j = j0 + q * stride;
-      if (j > last) break;
-      const double da = acv[q] - sv[q];
-      an[j] = sv[q];
-      a0 += dxv[q] * dxv[q];
-      a1 += dxv[q] * da;
-    }
-  }
-  const double t0 = blockSum<kVecThreads>(a0, scratch[0]);
-  const double t1 = blockSum<kVecThreads>(a1, scratch[1]);
-  if (threadIdx.x == 0) { partDX[blockIdx.x] = t0; partInter[blockIdx.x] = t1; }
-}
-
 // One block: local sums of the three partial arrays -> every rank's mailbox -> rank-ordered
 // totals -> the accept/reject decision (identical bits, hence identical decisions, everywhere).
 __global__ __launch_bounds__(kVecThreads) void k_mesh_decide(DevState* st, const MeshArgs ma,
@@ -671,8 +628,6 @@ int32_t meshConsumerBlocks(int64_t len) { return capped((len + 3) / 4, 1024); } 
 
 }  // namespace
 
-int32_t meshGrid(int64_t len) { return meshConsumerBlocks(len); }
-
 // ---- launchers (dmv = the view in device memory) --------------------------------------------
 void launchMeshPrimalStep(const IterVecs& vc, const DevState* st, const MeshArgs& dmv, hipStream_t s) {
   hipLaunchKernelGGL(k_mesh_primal_step, dim3(meshBlocks(vc.n)), dim3(kVecThreads), 0, s, vc, st, dmv);
@@ -682,15 +637,6 @@ void launchMeshWaitCopyX(const IterVecs& vf, const DevState* st, const MeshArgs&
   // (every block polls when the wait is fused: one block per CU at most)
   hipLaunchKernelGGL(k_mesh_wait_copy_x, dim3(dmv.fusedWait ? capped((vf.n + 3) / 4, 256) : meshConsumerBlocks(vf.n)), dim3(kVecThreads), 0,
                      s, vf, const_cast<DevState*>(st), dmv);
-}
-void launchMeshPushPartial(const double* partial, int32_t n, const DevState* st, const MeshArgs& dmv, hipStream_t s) {
-  hipLaunchKernelGGL(k_mesh_push_partial, dim3(meshBlocks(n)), dim3(kVecThreads), 0, s, partial, st, dmv, 0LL);
-}
-void launchMeshReduceInteract(const IterVecs& vc, const DevState* st, const MeshArgs& dmv, const double* partial,
-                              double* partDX, double* partInter, int32_t nBlocks, hipStream_t s) {
-  hipLaunchKernelGGL(k_mesh_wait, dim3(1), dim3(kWave), 0, s, const_cast<DevState*>(st), dmv, (int)kFlagP, 0LL);
-  hipLaunchKernelGGL(k_mesh_reduce_interact, dim3(nBlocks), dim3(kVecThreads), 0, s, vc, const_cast<DevState*>(st),
-                     dmv, partial, partDX, partInter);
 }
 void launchMeshDecide(DevState* st, const MeshArgs& dmv, const double* partDY, int32_t nDY, const double* partDX,
                       const double* partInter, int32_t nDX, hipStream_t s) {

@@ -14,13 +14,14 @@
 //
 // Per trial step (rank g owns row block [r0,r1) and column slice [c0,c1)):
 //   X: x+[c0:c1) is pushed into every peer's recvX      (all-gather of x+)
-//   P: the partial A_g' y+ slice of owner h is pushed into h's recvP[g]; h adds
-//      the G contributions in RANK ORDER                 (reduce-scatter of A'y+)
+//   Y: y+[r0:r1) is pushed into every peer's recvY      (all-gather of y+; flag P)
 //   S: {dX^2, dY^2, interaction} partials go to every peer's mailbox; every rank
 //      adds the G triples in rank order and takes the identical accept/reject
 //      decision                                          (all-reduce of 3 scalars)
 // All sums are in a fixed order, so every rank holds bit-identical x, step sizes
-// and control flow, run after run.
+// and control flow, run after run.  The sharded HiPDLP step uses the P mailbox for a reduce-scatter instead: the
+// partial A_g' y slice of owner h is pushed into h's recvP[g], and h adds the G contributions in RANK ORDER
+// (Mesh::reduceScatterCols).
 //
 // The reference has no counterpart: Ax_multi_gpu / ATy_multi_gpu are exit(1)
 // stubs (cupdlp_linalg.c:420-423,453-456).
@@ -47,7 +48,7 @@ struct MeshState {
   int32_t error;        // set by a kernel whose wait timed out (host turns it into an exception)
   int32_t pad_;
   uint32_t counter[4];  // "last block signals" tickets
-  // time spent waiting for the peers' flags in the hot loop, per exchange (X all-gather, P reduce-scatter,
+  // time spent waiting for the peers' flags in the hot loop, per exchange (X all-gather, P: Y all-gather,
   // S scalars): 100 MHz wall-clock ticks and number of waits (measurement only; bench.py reports them)
   unsigned long long waitTicks[3];
   unsigned long long waitCount[3];
@@ -148,15 +149,11 @@ class Mesh {
 // ---- hot-loop kernels (mesh flavour of enqueueTrial) -----------------------------
 // vc = column-sliced view of the iteration vectors (pointers offset by c0, n = c1-c0);
 // vf = the full-length view.
-int32_t meshGrid(int64_t len);  // grid size of the mesh kernels for a vector of `len`
 void launchMeshPrimalStep(const IterVecs& vc, const DevState* st, const MeshArgs& dmv, hipStream_t s);
 void launchMeshWaitCopyX(const IterVecs& vf, const DevState* st, const MeshArgs& dmv, hipStream_t s);
-void launchMeshPushPartial(const double* partial, int32_t n, const DevState* st, const MeshArgs& dmv, hipStream_t s);
-void launchMeshReduceInteract(const IterVecs& vc, const DevState* st, const MeshArgs& dmv, const double* partial,
-                              double* partDX, double* partInter, int32_t nBlocks, hipStream_t s);
 void launchMeshDecide(DevState* st, const MeshArgs& dmv, const double* partDY, int32_t nDY, const double* partDX,
                       const double* partInter, int32_t nDX, hipStream_t s);
-// "Two all-gathers" layout (row block for A x, column block for A'y): the dual step's y+[r0:r1) is pushed into
+// Row block for A x, column block for A'y: the dual step's y+[r0:r1) is pushed into
 // every peer's recvY (flag P stands for "Y" there), then recvY -> yNext outside the own rows.  yNextFull = the
 // full-length y of the next parity on this rank.
 void launchMeshPushY(const IterVecs& vf, const double* const yFull[2], const DevState* st, const MeshArgs& dmv, hipStream_t s);

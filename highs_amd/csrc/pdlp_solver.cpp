@@ -70,7 +70,7 @@ void DeviceMatrix::uploadPlans(const std::vector<int32_t>& hostBeg, int32_t nCsr
   LongPlan L;
   if (useSlab) {
     L = planSlabTasks(hostBeg, hostLongIdx, (int32_t)plan.longMajors.size(), longVecIndex, balanceTaskBlocks,
-                      affineTasks && hostLongIdx && tileOwner ? tileOwner : nullptr, tileLog2, slab.nBlocks, taskGroup);
+                      hostLongIdx && tileOwner ? tileOwner : nullptr, tileLog2, slab.nBlocks, taskGroup);
   } else {
     taskGroup = kSpmvThreads / 64;
     L = planLong(hostBeg, plan.longMajors, longVecIndex ? vecIdx.data() : nullptr, taskGroup);
@@ -111,7 +111,6 @@ void DeviceMatrix::upload(const Compressed& cIn, int32_t nMajor_, int32_t nMinor
   nMajor = nMajor_;
   nnz = cIn.beg.empty() ? 0 : cIn.beg[nMajor_];
   useSlab = chooseSlab(sw.slab, nMajor_, nMinor_);
-  affineTasks = sw.affineTasks != 0;
   const Compressed* c = &cIn;
   SlabLayout L;
   std::vector<int8_t> tileOwner;
@@ -160,7 +159,6 @@ void DeviceMatrix::buildFromDevice(DeviceCsrData& M, const DevSwitches& sw, hipS
   nMajor = M.nMajor;
   nnz = M.nnz;
   useSlab = chooseSlab(sw.slab, M.nMajor, M.nMinor);
-  affineTasks = sw.affineTasks != 0;
   std::vector<int32_t> hostBeg, hostLongMap, hostLongIdx;
   std::vector<int8_t> tileOwner;
   int32_t tileLog2 = 0;
@@ -338,10 +336,6 @@ DevSwitches DevSwitches::fromEnv() {
     const char* e = devEnv(name);
     return e ? atoi(e) : dflt;
   };
-  auto devStr = [](const char* name) {
-    const char* e = devEnv(name);
-    return std::string(e ? e : "");
-  };
   w.gpuSetup = num("PDLP_MI355X_GPU_SETUP", -1);
   w.fused = num("PDLP_MI355X_FUSED", -1);
   w.persistent = num("PDLP_MI355X_PERSISTENT", -1);
@@ -357,10 +351,7 @@ DevSwitches DevSwitches::fromEnv() {
   w.xcdMap = dev("PDLP_MI355X_XCD_MAP", -1);
   w.slabPace = dev("PDLP_MI355X_SLAB_PACE", -1);
   w.slabTune = dev("PDLP_MI355X_SLAB_TUNE", 1);
-  w.affineTasks = dev("PDLP_MI355X_AFFINE_TASKS", 1);
-  w.fusedStream = dev("PDLP_MI355X_FUSED_STREAM", 0);
   w.fusedCoTasks = dev("PDLP_MI355X_FUSED_COTASKS", -1);
-  w.uniformBounds = dev("PDLP_MI355X_UNIFORM_BOUNDS", 1);
   w.constCached = dev("PDLP_MI355X_CONST_CACHED", -1);
   w.touchTail = dev("PDLP_MI355X_TOUCH_TAIL", 1);
   w.xcdLocal = dev("PDLP_MI355X_XCD_LOCAL", -1);
@@ -371,7 +362,6 @@ DevSwitches DevSwitches::fromEnv() {
   w.fault = dev("PDLP_MI355X_FAULT", 0);
   if (w.fault) fprintf(stderr, "pdlp_mi355x: PDLP_MI355X_FAULT=%d is set — a TEST hook that makes a barrier launch time out on purpose; "
                                "this solve will stall for the barrier timeout and continue on the slower plain-launch path\n", w.fault);
-  w.meshLayout = devStr("PDLP_MI355X_MESH_LAYOUT");
   return w;
 }
 
@@ -508,12 +498,12 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
     gpuPrepare(P, doScale, stream_, devProb);
     sumCost2_ = devProb.sumCost2;
     sumRhs2_ = devProb.sumRhs2;
-    // A rank keeps only its shard (round 6): in the two-all-gathers layout of the mesh exchange both operands of a rank
-    // are CONTIGUOUS pieces of the two orientations that the device-side set-up has just built (rows [r0, r1) of A by rows,
-    // columns [c0, c1) of A by columns), so they are cut on the device (uploadShardFromDevice below) and nothing but the
-    // row starts (4 bytes per row, for the row partition) and the scale vectors crosses PCIe.  The RCCL exchange and the
-    // round-1 mesh layout need the transpose of the row slab: the whole form comes to the host as before.
-    shardOnDevice_ = sw_.exchange != "rccl" && sw_.meshLayout != "partial";
+    // A rank keeps only its shard (round 6): in the mesh exchange's layout both operands of a rank are CONTIGUOUS pieces
+    // of the two orientations that the device-side set-up has just built (rows [r0, r1) of A by rows, columns [c0, c1)
+    // of A by columns), so they are cut on the device (uploadShardFromDevice below) and nothing but the row starts
+    // (4 bytes per row, for the row partition) and the scale vectors crosses PCIe.  The RCCL exchange needs the
+    // transpose of the row slab: the whole form comes to the host as before.
+    shardOnDevice_ = sw_.exchange != "rccl";
     if (shardOnDevice_) {
       F_ = StandardForm();
       F_.n = devProb.n; F_.m = devProb.m; F_.n0 = devProb.n0; F_.nEqs = devProb.nEqs; F_.nnz = devProb.nnz;
@@ -610,7 +600,6 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
       shardOnDevice_ = false;
     }
     if (meshMode_) {
-      colblock_ = sw_.meshLayout != "partial";
       if (shardOnDevice_ && (c0_ != mesh_->c0() || c1_ != mesh_->c1())) throw std::runtime_error("pdlp_mi355x: column slices of the shard cut and of the exchange differ");
       c0_ = mesh_->c0();
       c1_ = mesh_->c1();
@@ -624,8 +613,7 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
       comm_ = new Comm(rank_, world_, id128);
     }
     log(1, "Row-block sharded over %d GPUs, exchange: %s\n", world_,
-        !meshMode_ ? "RCCL all-reduce" : colblock_ ? "direct xGMI mesh, two all-gathers (x+ slices, y+ row blocks)"
-                                                   : "direct xGMI mesh, all-gather of x+ and reduce-scatter of the A'y partials");
+        meshMode_ ? "direct xGMI mesh, two all-gathers (x+ slices, y+ row blocks)" : "RCCL all-reduce");
   } else {
     r0_ = 0;
     r1_ = F_.m;
@@ -644,16 +632,16 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
               (int)M->useSlab, M->slabWidthLog2, M->estRunLen, M->useSlab ? M->slab.nBlocks : M->nBlocks, M->xcdMap ? "contiguous" : "round robin", M->noPace ? "free-running waves" : "paced",
               M->nLong, M->nTasks, M->taskGroup);
   // 2-launch trial where the A' y grid is resident all at once (grid barrier inside the kernel); PDLP_MI355X_FUSED=0 forces
-  // 3 launches.  Slab layout (one block per CU): on by default, 140.0 -> 135.0 us per iteration at 1M x 1M.  Stream
-  // layout: off by default — measured in round 3 the barrier + decision tail costs what the separate launch did
-  // (100k x 100k: 33.1 us fused vs 32.1; 25fv47: 19.5 vs 20.2); PDLP_MI355X_FUSED_STREAM=1 turns it on.
+  // 3 launches.  Slab layout only (one block per CU): 140.0 -> 135.0 us per iteration at 1M x 1M.  On the stream layout
+  // the barrier + decision tail cost what the separate launch did (round 3: 100k x 100k 33.1 us fused vs 32.1; 25fv47
+  // 19.5 vs 20.2), and that variant has been removed.
   if (!sharded_) {
     // (long columns: their segment tasks as workgroups of the fused launch, resident next to its streaming blocks, where
     // two 1024-thread blocks per CU fit — PDLP_MI355X_FUSED_COTASKS=0 keeps the task passes inside the streaming blocks)
     dAt_.fusedCoTasks = sw_.fusedCoTasks != 0 ? fusedCoTaskBlocks(dAt_.view(), opt_.device) : 0;
     dAt_.touchTail = sw_.touchTail != 0 ? 1 : 0;
     const MatView at = dAt_.view();
-    const bool allowed = at.useSlab ? sw_.fused != 0 : sw_.fusedStream != 0;
+    const bool allowed = at.useSlab && sw_.fused != 0;
     fused_ = allowed && !hasQoff_ && fusedAtyBlocks(at) > 0 && fusedAtyBlocksResident(at, opt_.device) >= fusedAtyBlocks(at);
     // Netlib-class LPs (both operands below 2^18 nonzeros, stream layout, no long majors): the whole trial batch is one
     // persistent launch with grid barriers between the phases (pdlp_small.hip); PDLP_MI355X_PERSISTENT=0 turns it off
@@ -683,7 +671,7 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
       hierBar_ = !smallChunks || (sw_.hierBarrier >= 0 ? sw_.hierBarrier != 0 : g > 64);
     }
     if (fused_) gridBar_.alloc(gridBarWords(fusedAtyBlocks(at)));
-    if (fused_ && at.useSlab && sw_.uniformBounds != 0) {
+    if (fused_) {
       // bounds that all columns of a block of the fused launch share (x >= 0 without an upper bound is the rule): two scalars
       // per block instead of 8 / 16 bytes per column in the launch's bandwidth-bound tail (IterVecs::colBlockUni)
       colBlockUni_.alloc((size_t)at.slab.nBlocks);
@@ -716,10 +704,9 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
     checkSmall_ = persistent_ && smallGrid_ <= 64 && sw_.checkSmall != 0 && checkSmallResident(dA_.view(), at, opt_.device) >= smallGrid_;
     if (checkSmall_) checkBar_.alloc((size_t)smallGrid_ + 8);
   }
-  // check iterations on the device (single GPU; the sharded paths issue their check collectives from the host)
-  // check iterations on the device: single GPU, and (round 5) the row-block sharded solve in the two-all-gathers layout of the
-  // mesh exchange — its check collectives are enqueued with the check's kernels instead of being driven from the host
-  devCheck_ = (!sharded_ || (meshMode_ && colblock_)) && sw_.deviceCheck != 0;
+  // check iterations on the device: single GPU, and (round 5) the row-block sharded solve over the mesh exchange — its check
+  // collectives are enqueued with the check's kernels instead of being driven from the host (RCCL: from the host)
+  devCheck_ = (!sharded_ || meshMode_) && sw_.deviceCheck != 0;
   reset();
   // the trial-batch graph is part of the setup, not of the first iterations
   if (useGraph_ && !persistent_ && (!sharded_ || meshMode_)) captureGraph();
@@ -754,7 +741,7 @@ void Solver::uploadProblem() {
     Compressed csrSlab, cscSlab;
     extractSlab(F_, r0_, r1_, csrSlab, cscSlab);
     dA_.upload(csrSlab, mLoc_, n, sw_, stream_);
-    if (colblock_) {  // A'y operand: the columns this rank owns, over ALL rows (rows ascending, as on one GPU)
+    if (meshMode_) {  // A'y operand: the columns this rank owns, over ALL rows (rows ascending, as on one GPU)
       Compressed cb;
       const int32_t b = F_.cscSorted.beg[c0_], e = F_.cscSorted.beg[c1_];
       cb.beg.resize((size_t)nLoc_ + 1);
@@ -892,8 +879,8 @@ void Solver::uploadShardFromDevice(DeviceProblem& D) {
 
 void Solver::allocIterates() {
   const int32_t n = F_.n;
-  yLen_ = colblock_ ? F_.m : mLoc_;
-  yOff_ = colblock_ ? r0_ : 0;
+  yLen_ = meshMode_ ? F_.m : mLoc_;
+  yOff_ = meshMode_ ? r0_ : 0;
   for (int k = 0; k < 2; ++k) {
     x_[k].alloc(n); y_[k].alloc(yLen_); ax_[k].alloc(mLoc_); aty_[k].alloc(n);
     x_[k].zero(stream_); y_[k].zero(stream_); ax_[k].zero(stream_); aty_[k].zero(stream_);
@@ -949,7 +936,7 @@ void Solver::allocIterates() {
   if (vecsCol_.qdiag) vecsCol_.qdiag += c0_;
   vecsCol_.n = nLoc_;
   vecsAty_ = vecsCol_;
-  if (colblock_)  // the column-block A'y kernel gathers from the FULL y of the next parity
+  if (meshMode_)  // the column-block A'y kernel gathers from the FULL y of the next parity
     for (int k = 0; k < 2; ++k) vecsAty_.y[k] = y_[k].get();
   PDLP_HIP(hipStreamSynchronize(stream_));
 }
@@ -1039,17 +1026,12 @@ void Solver::deviceAx(const double* x, double* axLocal) { launchSpmvPlain(dA_.vi
 void Solver::deviceATy(const double* yLocal, double* aty) {
   if (!sharded_) {
     launchSpmvPlain(dAt_.view(), yLocal, aty, stream_);
-  } else if (meshMode_ && colblock_) {
+  } else if (meshMode_) {
     // yLocal is this rank's rows inside a full-length vector: all-gather the rows, own columns of A'y from the
-    // column block, all-gather of the slices (full vector everywhere, as the other layouts leave it)
+    // column block, all-gather of the slices (full vector everywhere, as the RCCL path leaves it)
     double* full = const_cast<double*>(yLocal) - yOff_;
     mesh_->allGather(full, true, stream_);
     launchSpmvPlain(dAt_.view(), full, aty + c0_, stream_);
-    mesh_->allGather(aty, false, stream_);
-  } else if (meshMode_) {
-    // reduce-scatter of the partials to the column owners, then all-gather: full vector everywhere
-    launchSpmvPlain(dAt_.view(), yLocal, commBuf_.get(), stream_);
-    mesh_->reduceScatterCols(commBuf_.get(), aty, stream_);
     mesh_->allGather(aty, false, stream_);
   } else {
     launchSpmvPlain(dAt_.view(), yLocal, commBuf_.get(), stream_);
@@ -1195,10 +1177,8 @@ void Solver::profCollect(int32_t realTrials) {
 
 void Solver::enqueueTrial() {
   if (meshMode_) {
-    // direct-exchange sequence (pdlp_mesh.hpp): X all-gather, P reduce-scatter, S scalars
+    // direct-exchange sequence (pdlp_mesh.hpp): X all-gather, Y all-gather, S scalars
     const MeshArgs& mv = mesh_->args();
-    double* buf = commBuf_.get();
-    const int32_t nb = meshGrid(std::max(nLoc_, 1));  // consumer grid: ~4 slice elements per thread
     const bool oneLaunch = mv.fusedWait == 2;  // every rank on a GPU of its own: an exchange is one kernel (five launches per trial)
     if (oneLaunch) {
       double* xFull[2] = {x_[0].get(), x_[1].get()};
@@ -1208,24 +1188,17 @@ void Solver::enqueueTrial() {
       launchMeshWaitCopyX(vecs_, dst(), mv, stream_);
     }
     launchSpmvAxDual(dA_.view(), vecs_, dst(), partDY_.get(), stream_);
-    if (colblock_) {
-      // Y all-gather of the dual step's rows, then A'y+ on the own COLUMNS from the column block: every column is
-      // summed over all rows in the single-GPU order; no n-length partial is written, pushed and re-reduced
-      double* yFull[2] = {y_[0].get(), y_[1].get()};
-      if (oneLaunch) {
-        launchMeshY(yFull, F_.m, dst(), mv, stream_);
-      } else {
-        launchMeshPushY(vecs_, yFull, dst(), mv, stream_);
-        launchMeshWaitCopyY(yFull, F_.m, dst(), mv, stream_);
-      }
-      launchSpmvAtyInteract(dAt_.view(), vecsAty_, dst(), partDX_.get(), partInter_.get(), stream_);
-      launchMeshDecide(dst(), mv, partDY_.get(), dA_.nPartials(), partDX_.get(), partInter_.get(), dAt_.nPartials(), stream_);
-      return;
+    // Y all-gather of the dual step's rows, then A'y+ on the own COLUMNS from the column block: every column is
+    // summed over all rows in the single-GPU order; no n-length partial is written, pushed and re-reduced
+    double* yFull[2] = {y_[0].get(), y_[1].get()};
+    if (oneLaunch) {
+      launchMeshY(yFull, F_.m, dst(), mv, stream_);
+    } else {
+      launchMeshPushY(vecs_, yFull, dst(), mv, stream_);
+      launchMeshWaitCopyY(yFull, F_.m, dst(), mv, stream_);
     }
-    launchSpmvAtyPartial(dAt_.view(), vecs_, dst(), buf, stream_);
-    launchMeshPushPartial(buf, F_.n, dst(), mv, stream_);
-    launchMeshReduceInteract(vecsCol_, dst(), mv, buf, partDX_.get(), partInter_.get(), nb, stream_);
-    launchMeshDecide(dst(), mv, partDY_.get(), dA_.nPartials(), partDX_.get(), partInter_.get(), nb, stream_);
+    launchSpmvAtyInteract(dAt_.view(), vecsAty_, dst(), partDX_.get(), partInter_.get(), stream_);
+    launchMeshDecide(dst(), mv, partDY_.get(), dA_.nPartials(), partDX_.get(), partInter_.get(), dAt_.nPartials(), stream_);
     return;
   }
   if (persistent_) {
@@ -1433,7 +1406,7 @@ void Solver::computeResiduals() {
   if (meshMode_) {
     mesh_->checkError(stream_);
     mesh_->verifyReplicated(x_[c].get(), F_.n, stream_);  // every rank gathers from ITS copy of x
-    if (colblock_) mesh_->verifyReplicated(y_[c].get(), F_.m, stream_);  // ... and, in this layout, from its copy of y
+    mesh_->verifyReplicated(y_[c].get(), F_.m, stream_);  // ... and from its copy of y
   }
 
   auto fill = [&](Residuals& r, const double* rs, const double* cs) {
@@ -1514,7 +1487,7 @@ void Solver::restartIterate() {
   if (!toCurrent) {
     pFeasLR_ = avg_.pFeas; dFeasLR_ = avg_.dFeas; gapLR_ = avg_.gap;
     PDLP_HIP(hipMemcpyAsync(x_[c].get(), xAvg_.get(), sizeof(double) * n, hipMemcpyDeviceToDevice, stream_));
-    PDLP_HIP(hipMemcpyAsync(y_[c].get(), yAvg_.get(), sizeof(double) * yLen_, hipMemcpyDeviceToDevice, stream_));  // (colblock: the full, all-gathered average)
+    PDLP_HIP(hipMemcpyAsync(y_[c].get(), yAvg_.get(), sizeof(double) * yLen_, hipMemcpyDeviceToDevice, stream_));  // (mesh: the full, all-gathered average)
     PDLP_HIP(hipMemcpyAsync(ax_[c].get(), axAvg_.get(), sizeof(double) * mLoc_, hipMemcpyDeviceToDevice, stream_));
     PDLP_HIP(hipMemcpyAsync(aty_[c].get(), atyAvg_.get(), sizeof(double) * n, hipMemcpyDeviceToDevice, stream_));
     if (hasQoff_) PDLP_HIP(hipMemcpyAsync(nx_[c].get(), nxAvg_.get(), sizeof(double) * n, hipMemcpyDeviceToDevice, stream_));
@@ -1770,7 +1743,7 @@ void Solver::doSolveDevice(bool terminate, int32_t target) {
     if (meshMode_) {  // (sharded: the exchange's error flag and the checksum guard of the replicated iterates, once per round)
       mesh_->checkError(stream_);
       mesh_->verifyReplicated(x_[s.cur].get(), F_.n, stream_);
-      if (colblock_) mesh_->verifyReplicated(y_[s.cur].get(), F_.m, stream_);
+      mesh_->verifyReplicated(y_[s.cur].get(), F_.m, stream_);
     }
     processRecords(terminate, iterLim, logSinceHeader);
     bool over = false;  // a check of this round has ended the solve (everything queued behind it was a no-op)
@@ -2095,10 +2068,10 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
       put(0, -1.0);
     }
   } else if (name == "trial_launches") {  // kernels per trial step of the hot loop (2 = fused decision + primal step)
-    // mesh, two all-gathers: 9 with single-block wait kernels, 7 with consumers that wait themselves, 5 with an exchange
-    // per launch (fusedWait 0 / 1 / 2); round-1 layout: 9 / 8
+    // mesh: 9 with single-block wait kernels, 7 with consumers that wait themselves, 5 with an exchange per launch
+    // (fusedWait 0 / 1 / 2)
     const int fw = meshMode_ ? mesh_->args().fusedWait : 0;
-    put(0, meshMode_ ? (colblock_ ? 9.0 - 2.0 * fw : 9.0 - (fw ? 1.0 : 0.0)) : sharded_ ? 7.0 : persistent_ ? 0.0 : fused_ ? 2.0 : 3.0);  // 0: one persistent launch per batch
+    put(0, meshMode_ ? 9.0 - 2.0 * fw : sharded_ ? 7.0 : persistent_ ? 0.0 : fused_ ? 2.0 : 3.0);  // 0: one persistent launch per batch
   } else if (name == "trial_barriers") {  // grid barriers per trial of the persistent loop (0: no persistent loop)
     put(0, !persistent_ ? 0.0 : primalInA_ ? 2.0 : 3.0);
   } else if (name == "check_launches") {  // kernels of one device-driven check iteration (1: the one-launch form of small LPs;
@@ -2110,8 +2083,8 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     put(0, (double)barrierFallbacks_);
   } else if (name == "uniform_bound_columns") {  // columns whose lower / upper bound the fused launch takes from a scalar of their block
     put(0, (double)uniLowerCols_); put(1, (double)uniUpperCols_);
-  } else if (name == "exchange") {  // 0 = not sharded, 1 = RCCL all-reduce, 2 = direct xGMI mesh (partials), 3 = mesh, two all-gathers
-    put(0, !sharded_ ? 0.0 : !meshMode_ ? 1.0 : colblock_ ? 3.0 : 2.0);
+  } else if (name == "exchange") {  // 0 = not sharded, 1 = RCCL all-reduce, 3 = direct xGMI mesh, two all-gathers (2 was the removed partials layout)
+    put(0, !sharded_ ? 0.0 : !meshMode_ ? 1.0 : 3.0);
   } else if (name == "residuals") {
     computeAverage();
     computeResiduals();
@@ -2146,7 +2119,7 @@ double Solver::timeKernel(const std::string& name, int32_t reps) {
     if (name == "spmv_ax") launchSpmvAxDual(dA_.view(), vecs_, dst(), partDY_.get(), stream_);
     else if (name == "spmv_aty") {
       if (!sharded_) launchSpmvAtyInteract(dAt_.view(), vecs_, dst(), partDX_.get(), partInter_.get(), stream_);
-      else if (colblock_) launchSpmvAtyInteract(dAt_.view(), vecsAty_, dst(), partDX_.get(), partInter_.get(), stream_);
+      else if (meshMode_) launchSpmvAtyInteract(dAt_.view(), vecsAty_, dst(), partDX_.get(), partInter_.get(), stream_);
       else launchSpmvAtyPartial(dAt_.view(), vecs_, dst(), commBuf_.get(), stream_);
     } else if (name == "primal_step") launchPrimalStep(vecs_, dst(), stream_);
     else if (name == "decide_primal") {  // (pending is set by the kernel itself: from the second launch on it decides too)

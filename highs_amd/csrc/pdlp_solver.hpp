@@ -26,17 +26,15 @@ struct DevSwitches {
   int slabW = 0;          // PDLP_MI355X_SLAB_W: log2 of the slab width (development)
   int xcdMap = -1, slabPace = -1;
   int slabTune = 1;       // PDLP_MI355X_SLAB_TUNE=0 (development): the slab width by rule only, no timing of narrower slabs
-  int affineTasks = 1;  // XCD-affine deal of the slab layout's segment tasks (0: (major, segment) order; A/B measurements)
   int fusedCoTasks = -1;  // PDLP_MI355X_FUSED_COTASKS: 0 = the fused trial's streaming blocks run the long columns' task passes themselves
   int touchTail = 1;      // PDLP_MI355X_TOUCH_TAIL=0 (development): no touching of the tail columns' operands in front of the fused trial's barrier
-  int uniformBounds = 1;  // PDLP_MI355X_UNIFORM_BOUNDS=0 (development): the fused trial loads l and u of every column even where a block's columns share them
   int constCached = -1;   // PDLP_MI355X_CONST_CACHED=0|1 (development): c, l, u of the primal step non-temporal / ordinary loads (default: by size)
-  int fused = -1, fusedStream = 0, persistent = -1, xcdLocal = -1, hierBarrier = -1, deviceCheck = -1, checkSmall = -1;
+  int fused = -1, persistent = -1, xcdLocal = -1, hierBarrier = -1, deviceCheck = -1, checkSmall = -1;
   int primalInA = -1;     // PDLP_MI355X_PRIMAL_IN_A: the persistent loop without its P phase (pdlp_small.hip PINA); -1 = where measured faster
   int barrierTimeoutMs = 1000;  // PDLP_MI355X_BARRIER_TIMEOUT_MS: how long a grid barrier / roll call waits for missing workgroups
   int fault = 0;          // PDLP_MI355X_FAULT (tests): 1 = the first persistent launch expects one workgroup too many,
                           // 2 = the 12th fused trial's barrier expects one block too many (both then time out and fall back)
-  std::string exchange, meshLayout;
+  std::string exchange;
   static DevSwitches fromEnv();
 };
 
@@ -54,7 +52,6 @@ struct DeviceMatrix {
   // slab layout: size the task workgroups so that every CU gets one (uploadPlans).  Off for the operand whose tasks the
   // fused trial runs inside its streaming blocks (already spread evenly; full groups of 16 keep long columns in LDS)
   bool balanceTaskBlocks = true;
-  bool affineTasks = true;  // slab layout: XCD-affine deal of the segment tasks (PDLP_MI355X_DEV_AFFINE_TASKS=0: (major, segment) order)
   int32_t majorCost = kSlabMajorCostRows;  // slab partition: work of a major besides its entries (the owner sets kSlabMajorCostCols on its transposed operand)
   int32_t fusedCoTasks = 0;  // MatView::coTaskBlocks (the fused trial's task workgroups), decided by the solver at set-up
   int32_t touchTail = 1;     // MatView::touchTail
@@ -191,18 +188,17 @@ class Solver : public SolverBase {
   // well, [c0_, c1_)) or, as the fallback, RCCL all-reduce with replicated column work
   Mesh* mesh_ = nullptr;
   bool meshMode_ = false;
-  // Mesh layouts (PDLP_MI355X_MESH_LAYOUT): "colblock" (default) = row block for A x, column block A[:, c0:c1) for
-  // A'y, two all-gathers per trial (x+ slices, y+ row blocks), no n-length partial; "partial" = the round-1 layout
-  // (transpose of the row block, all-gather of x+ and reduce-scatter of the A_g'y partials).  With colblock every
-  // rank keeps y, yAvg (and the power method's work vector) at FULL length m; yOff_ = r0_ is where its rows sit.
-  bool colblock_ = false;
+  // Mesh layout: row block for A x, column block A[:, c0:c1) for A'y, two all-gathers per trial (x+ slices, y+ row
+  // blocks), no n-length partial.  Every rank then keeps y, yAvg (and the power method's work vector) at FULL length m;
+  // yOff_ = r0_ is where its rows sit.  (The round-1 layout — all-gather of x+, reduce-scatter of the A'y partials — has
+  // been removed.)
   int32_t yOff_ = 0, yLen_ = 0;
   double* yl(int k) const { return y_[k].get() + yOff_; }
   double* yAvgl() const { return yAvg_.get() + yOff_; }
   double* tmpMl() const { return tmpM_.get() + yOff_; }
   int32_t c0_ = 0, c1_ = 0, nLoc_ = 0;
   IterVecs vecsCol_{};  // vecs_ restricted to the own column slice
-  IterVecs vecsAty_{};  // colblock layout: vecsCol_ with the FULL-length y (what the column-block A'y kernel gathers from)
+  IterVecs vecsAty_{};  // mesh layout: vecsCol_ with the FULL-length y (what the column-block A'y kernel gathers from)
   // device
   hipStream_t stream_ = nullptr;
   DeviceMatrix dA_, dAt_;

@@ -205,8 +205,8 @@ def test_mesh_exchange_pattern_matches_unsharded_oracle(world):
     assert sl[0][0] == 0 and all(sl[i][1] == sl[i + 1][0] for i in range(world - 1))
 
 
-def _colblock_worker(rank, world, port, ret):
-    """The DEFAULT mesh layout of round 3 (pdlp_solver.cpp colblock_): rank g owns the row block [r0,r1) for A x and the
+def _column_block_worker(rank, world, port, ret):
+    """The mesh layout of round 3 (pdlp_solver.cpp, meshMode_): rank g owns the row block [r0,r1) for A x and the
     column block [c0,c1) of the WHOLE matrix for A'y.  A trial = primal step on the own columns, all-gather of x+, dual
     step on the own rows, all-gather of y+, A'y+ of the own columns over ALL rows (every column summed as one GPU sums
     it: rows ascending — no partial sums, no reduce-scatter), three scalars added in rank order.  Same data and same
@@ -307,5 +307,5 @@ def test_two_all_gathers_layout_matches_unsharded_oracle_bit_for_bit(world):
     mgr = mp.Manager()
     ret = mgr.dict()
     port = 33500 + (os.getpid() % 2000) + world
-    mp.spawn(_colblock_worker, args=(world, port, ret), nprocs=world, join=True)
+    mp.spawn(_column_block_worker, args=(world, port, ret), nprocs=world, join=True)
     assert len(ret) == world and all(ret.values())

@@ -32,8 +32,8 @@ def _run_ranks(world, case, tmp_path, extra_env=None, must_finish=None):
         # Eight rank processes FOLDED onto one device plus this pytest process (which holds a used HIP context) need more
         # hardware queues than the device maps at once (three per process by default): the scheduler then time-slices the
         # processes, and a rank that spins on a peer which is switched out runs into the exchange's time-out —
-        # 6 of 10 runs on the round-6 box (tools/r6_flake.sh; 0 of 10 without the ninth process, 0 of 10 with one queue per
-        # rank).  A property of folding, not of the exchange: on a node every rank has a device of its own.
+        # 6 of 10 runs on the round-6 box (profiles/r06_development_measurements.md; 0 of 10 without the ninth process, 0 of
+        # 10 with one queue per rank).  A property of folding, not of the exchange: on a node every rank has a device of its own.
         env.setdefault("GPU_MAX_HW_QUEUES", "1")
     env.update(extra_env or {})
     outs = [str(tmp_path / f"r{r}.npz") for r in range(world)]
