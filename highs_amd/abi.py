@@ -9,6 +9,8 @@ import ctypes as C
 import numpy as np
 
 c_i32p = C.POINTER(C.c_int32)
+c_i64p = C.POINTER(C.c_int64)
+INT32_MAX = 2**31 - 1
 c_f64p = C.POINTER(C.c_double)
 
 # termination codes, cuPDLP-C termination_code (cupdlp_defs.h:61-68)
@@ -221,11 +223,14 @@ def _ptr(a, ty):
 
 
 class ProblemHandle:
-    """Owns the numpy buffers a pdlp_problem_t points to."""
+    """Owns the numpy buffers a pdlp_problem_t points to.  Column starts above INT32_MAX (an int64 array) stay 64-bit:
+    `wide` is set, struct.a_start is NULL and `a_start` is the array the *_wide entries take instead."""
 
     def __init__(self, lp, start=None):
         self.lp = lp
-        self.a_start = _i32(lp.a_start)
+        st = np.asarray(lp.a_start)
+        self.wide = st.size > 0 and int(st.max()) > INT32_MAX
+        self.a_start = np.ascontiguousarray(st, dtype=np.int64) if self.wide else _i32(st)
         self.a_index = _i32(lp.a_index)
         self.a_value = _f64(lp.a_value)
         self.col_cost = _f64(lp.col_cost)
@@ -237,7 +242,7 @@ class ProblemHandle:
         P.num_col = int(lp.num_col)
         P.num_row = int(lp.num_row)
         P.num_nz = int(self.a_start[lp.num_col])
-        P.a_start = _ptr(self.a_start, c_i32p)
+        P.a_start = None if self.wide else _ptr(self.a_start, c_i32p)
         P.a_index = _ptr(self.a_index, c_i32p)
         P.a_value = _ptr(self.a_value, c_f64p)
         P.col_cost = _ptr(self.col_cost, c_f64p)

@@ -92,6 +92,80 @@ int pdlp_mi355x_create_sharded(const pdlp_problem_t* P, const pdlp_params_t* opt
   });
 }
 
+}  // extern "C"
+
+namespace {
+// Devices pdlp_mi355x_solve shards over: opt->num_devices, or PDLP_MI355X_DEVICES when that is 0.
+int solveDevices(const pdlp_params_t* opt) {
+  int G = opt ? opt->num_devices : 0;
+  if (G <= 0) {
+    const char* e = getenv("PDLP_MI355X_DEVICES");
+    G = e ? atoi(e) : 1;
+  }
+  return G;
+}
+
+// The caller's problem with its 64-bit column starts checked and narrowed into `start` (P.a_start points there).  No HIP
+// call happens here, so malformed input gets its own message on a machine without a GPU too.  Every solver path indexes
+// the formulated matrix with 32-bit offsets: more than INT32_MAX nonzeros are refused, naming the path that refuses.
+struct NarrowedProblem {
+  pdlp_problem_t P;
+  std::vector<int32_t> start;
+};
+void narrowProblem(const pdlp_problem_t* P, const int64_t* a_start64, const pdlp_params_t* opt, int devices,
+                   NarrowedProblem& out) {
+  if (!P || !a_start64 || !opt) throw std::runtime_error("null argument");
+  if (P->num_col < 0 || P->num_row < 0) throw std::runtime_error("negative dimensions");
+  const int32_t n = P->num_col;
+  if (a_start64[0] != 0) throw std::runtime_error("a_start64[0] must be 0, is " + std::to_string(a_start64[0]));
+  for (int32_t j = 0; j < n; ++j)
+    if (a_start64[j + 1] < a_start64[j])
+      throw std::runtime_error("a_start64 decreases at column " + std::to_string(j) + ": a_start64[" + std::to_string(j) +
+                               "] = " + std::to_string(a_start64[j]) + ", a_start64[" + std::to_string(j + 1) + "] = " +
+                               std::to_string(a_start64[j + 1]));
+  if (a_start64[n] != P->num_nz)
+    throw std::runtime_error("a_start64[num_col] = " + std::to_string(a_start64[n]) + " differs from num_nz = " +
+                             std::to_string(P->num_nz));
+  const int64_t kMax = std::numeric_limits<int32_t>::max();
+  if (P->num_nz > kMax) {
+    const std::string has = "; this problem has " + std::to_string(P->num_nz) + " nonzeros";
+    if (opt->algorithm == 1)
+      throw std::runtime_error("pdlp_mi355x: the HiPDLP path (algorithm = 1) takes at most INT32_MAX = 2147483647 nonzeros" + has);
+    if (devices > 1)
+      throw std::runtime_error("pdlp_mi355x: sharded solves (num_devices > 1) take at most INT32_MAX = 2147483647 nonzeros" + has);
+    throw std::runtime_error("pdlp_mi355x: the device path indexes the formulated matrix with 32-bit offsets, at most "
+                             "INT32_MAX = 2147483647 nonzeros" + has);
+  }
+  out.P = *P;
+  out.start.assign(a_start64, a_start64 + n + 1);  // 0 <= a_start64[j] <= num_nz <= INT32_MAX: exact
+  out.P.a_start = out.start.data();
+  pdlp::validateProblem(out.P);  // row indices in range, arrays present
+}
+}  // namespace
+
+extern "C" {
+
+int pdlp_mi355x_create_wide(const pdlp_problem_t* P, const int64_t* a_start64, const pdlp_params_t* opt,
+                            pdlp_mi355x_solver_t** out) {
+  NarrowedProblem np;
+  const int rc = guarded([&] {
+    if (!out) throw std::runtime_error("null argument");
+    *out = nullptr;
+    narrowProblem(P, a_start64, opt, 1, np);
+  });
+  return rc != 0 ? rc : pdlp_mi355x_create(&np.P, opt, out);
+}
+
+int pdlp_mi355x_solve_wide(const pdlp_problem_t* P, const int64_t* a_start64, const pdlp_params_t* opt,
+                           pdlp_result_t* R) {
+  NarrowedProblem np;
+  const int rc = guarded([&] {
+    if (!R) throw std::runtime_error("null argument");
+    narrowProblem(P, a_start64, opt, solveDevices(opt), np);
+  });
+  return rc != 0 ? rc : pdlp_mi355x_solve(&np.P, opt, R);
+}
+
 int pdlp_mi355x_run(pdlp_mi355x_solver_t* s, pdlp_result_t* R) {
   return guarded([&] {
     if (!s || !s->impl) throw std::runtime_error("null solver");
@@ -181,11 +255,7 @@ void solveSharded(const pdlp_problem_t& P, const pdlp_params_t& opt, int G, pdlp
 }  // namespace
 
 int pdlp_mi355x_solve(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R) {
-  int G = opt ? opt->num_devices : 0;
-  if (G <= 0) {
-    const char* e = getenv("PDLP_MI355X_DEVICES");
-    G = e ? atoi(e) : 1;
-  }
+  const int G = solveDevices(opt);
   if (G > 1) {
     return guarded([&] {
       if (!P || !opt || !R) throw std::runtime_error("null argument");

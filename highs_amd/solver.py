@@ -42,6 +42,7 @@ EXPORTS = [
     "pdlp_mi355x_host_slab_layout", "pdlp_mi355x_free_slab_layout", "pdlp_mi355x_det_exp_log",
     "pdlp_mi355x_host_task_plan", "pdlp_mi355x_free_task_plan",
     "pdlp_mi355x_read_mps", "pdlp_mi355x_read_mps_timed", "pdlp_mi355x_free_mps_model",
+    "pdlp_mi355x_create_wide", "pdlp_mi355x_solve_wide",
 ]
 
 
@@ -66,6 +67,8 @@ def lib():
         L.pdlp_mi355x_default_params.argtypes = [pO]
         L.pdlp_mi355x_solve.argtypes = [pP, pO, pR]
         L.pdlp_mi355x_create.argtypes = [pP, pO, C.POINTER(H)]
+        L.pdlp_mi355x_solve_wide.argtypes = [pP, abi.c_i64p, pO, pR]
+        L.pdlp_mi355x_create_wide.argtypes = [pP, abi.c_i64p, pO, C.POINTER(H)]
         L.pdlp_mi355x_create_sharded.argtypes = [pP, pO, C.c_int32, C.c_int32, C.c_void_p, C.POINTER(H)]
         L.pdlp_mi355x_run.argtypes = [H, pR]
         L.pdlp_mi355x_destroy.argtypes = [H]
@@ -207,16 +210,28 @@ def model_status_from_term(term_code, num_iter, iter_limit, rc=0):
     return kUnknown
 
 
-def solveLpCupdlp(lp: HighsLp, start=None, solve_fn=None, **options):
+def _solve_once(P, params, R, solve_fn, solve_wide_fn):
+    """pdlp_mi355x_solve, or pdlp_mi355x_solve_wide when the column starts go beyond INT32_MAX (abi.ProblemHandle.wide).
+    solve_fn / solve_wide_fn stand in for the two entries."""
+    if not P.wide:
+        return (solve_fn or lib().pdlp_mi355x_solve)(C.byref(P.struct), C.byref(params), C.byref(R.struct))
+    if solve_fn is not None and solve_wide_fn is None:
+        raise ValueError("the column starts go beyond INT32_MAX: solve_fn takes 32-bit starts, pass solve_wide_fn")
+    fn = solve_wide_fn or lib().pdlp_mi355x_solve_wide
+    return fn(C.byref(P.struct), P.a_start.ctypes.data_as(abi.c_i64p), C.byref(params), C.byref(R.struct))
+
+
+def solveLpCupdlp(lp: HighsLp, start=None, solve_fn=None, solve_wide_fn=None, **options):
     """Solve `lp` with the MI355X PDLP path.  Keyword options use the HiGHS
     option names: kkt_tolerance, primal_feasibility_tolerance (primal_tol),
     pdlp_iteration_limit, pdlp_features_off, time_limit, log_level, ...
-    `solve_fn` lets the tests run the same marshalling against the oracle."""
+    An int64 `lp.a_start` with values above INT32_MAX goes through pdlp_mi355x_solve_wide.
+    `solve_fn` lets the tests run the same marshalling against the oracle; `solve_wide_fn`
+    stands in for the wide entry the same way."""
     params = options.pop("params", None) or abi.default_params(**options)
     P = abi.ProblemHandle(lp, start)
     R = abi.ResultHandle(lp.num_col, lp.num_row)
-    fn = solve_fn or lib().pdlp_mi355x_solve
-    rc = fn(C.byref(P.struct), C.byref(params), C.byref(R.struct))
+    rc = _solve_once(P, params, R, solve_fn, solve_wide_fn)
     ms = model_status_from_term(R.term_code, R.num_iter, params.iter_limit, rc)
     sol = HighsSolution(R.col_value, R.col_dual, R.row_value, R.row_dual, bool(R.value_valid), bool(R.dual_valid))
     info = kkt_measures(lp, sol.col_value, sol.col_dual, sol.row_value, sol.row_dual) if rc == 0 else {}
@@ -235,18 +250,18 @@ def run_model_file(path, solver="pdlp", threads=0, **options):
     return out, lp, info
 
 
-def solveLpHiPdlp(lp: HighsLp, solve_fn=None, **options):
+def solveLpHiPdlp(lp: HighsLp, solve_fn=None, solve_wide_fn=None, **options):
     """Mirror of the reference's second PDLP entry point, solveLpHiPdlp (highs/pdlp/HiPdlpWrapper.cpp:26-141):
     restarted Halpern PDHG.  Same option names as HiGHS (kkt_tolerance / pdlp_optimality_tolerance ->
     gap_tol, pdlp_iteration_limit, time_limit, pdlp_features_off, pdlp_scaling_mode, pdlp_ruiz_iterations,
-    pdlp_step_size_strategy); status map of HiPdlpWrapper.cpp:99-128."""
+    pdlp_step_size_strategy); status map of HiPdlpWrapper.cpp:99-128.  Column starts above INT32_MAX go to
+    pdlp_mi355x_solve_wide as in solveLpCupdlp (which refuses them on this path)."""
     options = dict(options)
     options["solver"] = "hipdlp"
     params = options.pop("params", None) or abi.default_params(**options)
     P = abi.ProblemHandle(lp)
     R = abi.ResultHandle(lp.num_col, lp.num_row)
-    fn = solve_fn or lib().pdlp_mi355x_solve
-    rc = fn(C.byref(P.struct), C.byref(params), C.byref(R.struct))
+    rc = _solve_once(P, params, R, solve_fn, solve_wide_fn)
     if rc != 0:
         ms = kSolveError
     elif R.term_code == abi.TERM_OPTIMAL:
@@ -271,7 +286,12 @@ class DeviceSolver:
             self._keep = abi.ProblemHandle(lp)
             problem_struct = self._keep.struct
         self.h = C.c_void_p()
-        if world > 1:
+        if self._keep is not None and self._keep.wide:  # 64-bit column starts (create_sharded takes 32-bit ones only)
+            if world > 1:
+                raise ValueError("sharded solves take 32-bit column starts")
+            rc = lib().pdlp_mi355x_create_wide(C.byref(problem_struct), self._keep.a_start.ctypes.data_as(abi.c_i64p),
+                                               C.byref(self.params), C.byref(self.h))
+        elif world > 1:
             rc = lib().pdlp_mi355x_create_sharded(C.byref(problem_struct), C.byref(self.params), rank, world,
                                                   unique_id, C.byref(self.h))
         else:

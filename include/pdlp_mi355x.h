@@ -29,7 +29,7 @@
  * cupdlp glbopts.h:250-256) and pdlp_mi355x_last_error().
  *
  * Arithmetic is fp64, indices are int32 (cupdlp_int / HighsInt default,
- * glbopts.h:258-263).
+ * glbopts.h:258-263); the *_wide entries also take 64-bit column starts.
  */
 #ifndef PDLP_MI355X_H_
 #define PDLP_MI355X_H_
@@ -177,6 +177,18 @@ int pdlp_mi355x_create(const pdlp_problem_t* P, const pdlp_params_t* opt,
                        pdlp_mi355x_solver_t** out);
 int pdlp_mi355x_run(pdlp_mi355x_solver_t* s, pdlp_result_t* R);
 void pdlp_mi355x_destroy(pdlp_mi355x_solver_t* s);
+
+/* The same two entries with 64-bit column starts (HighsInt = int64_t builds, or any caller whose matrix
+ * starts are 64-bit): a_start64[num_col+1] replaces P->a_start, which is ignored and may be NULL; every
+ * other field keeps its meaning.  a_start64 is checked on the host before any HIP call: a_start64[0] == 0,
+ * never decreasing, a_start64[num_col] == num_nz, and every row index in range.  A problem that passes
+ * behaves exactly as through pdlp_mi355x_create / pdlp_mi355x_solve.  The device path indexes the
+ * formulated matrix with 32-bit offsets, so a problem with more than INT32_MAX nonzeros is refused with
+ * a message that names the count, the limit and the path (algorithm, num_devices) that refused it. */
+int pdlp_mi355x_create_wide(const pdlp_problem_t* P, const int64_t* a_start64,
+                            const pdlp_params_t* opt, pdlp_mi355x_solver_t** out);
+int pdlp_mi355x_solve_wide(const pdlp_problem_t* P, const int64_t* a_start64,
+                           const pdlp_params_t* opt, pdlp_result_t* R);
 
 /* ---- measurement / parity hooks (device-resident state) ----------------
  * These exist so that tests and bench.py can drive and observe the hot loop
