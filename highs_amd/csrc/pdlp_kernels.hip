@@ -64,6 +64,9 @@ struct SpmvArgs {
   // development (PDLP_MI355X_SLAB_PROF=1): per block {launches, ticks to the end of the stream, to the end of the epilogue, to
   // the barrier's end, to the kernel's end} of the slab launches kDualStep / kAtyFused, 100 MHz wall clock
   unsigned long long* prof;
+  // kQxInteract: the vector N gathers from, by parity.  One GPU: v.x.  A rank of the mesh layout holds the rows [c0, c1) of N:
+  // it gathers from the full-length x+, while v (the own column slice) takes the epilogue's reads and writes at c0 + r
+  const double* gx[2];
 };
 
 // The major-local epilogue fused into both SpMV kernels: what happens to (A v)_r once it is known.
@@ -107,7 +110,8 @@ struct Epi {
   // the gathered vector
   __device__ __forceinline__ const double* input() const {
     if (EPI == kPlain) return a.in;
-    if (EPI == kDualStep || EPI == kQxInteract) return a.v.x[nxt];
+    if (EPI == kDualStep) return a.v.x[nxt];
+    if (EPI == kQxInteract) return a.gx[nxt];
     if (EPI == kHalpernPrimal) return a.h.yc;
     if (EPI == kHalpernDual) return a.h.rx;
     return a.v.y[nxt];
@@ -1303,9 +1307,12 @@ void launchDecide(DevState* st, const double* partDY, int32_t nDY, const double*
   hipLaunchKernelGGL(k_decide, dim3(1), dim3(kVecThreads), 0, s, st, partDY, nDY, partDX, partInter, nDX, dyGlobal,
                      onlyIfPending ? 1 : 0, partQ, nQ);
 }
-void launchSpmvQxInteract(const MatView& N, const IterVecs& v, const DevState* st, double* partQ, hipStream_t s) {
+void launchSpmvQxInteract(const MatView& N, const IterVecs& v, const DevState* st, double* partQ, hipStream_t s,
+                          const double* const xFull[2]) {
   SpmvArgs a{};
   a.st = st; a.v = v; a.part0 = partQ;
+  a.gx[0] = xFull ? xFull[0] : v.x[0];
+  a.gx[1] = xFull ? xFull[1] : v.x[1];
   launchSpmv<kQxInteract>(N, a, s);
 }
 void launchDecidePrimal(const IterVecs& v, const DevState* stIn, DevState* stOut, const double* partDY, int32_t nDY,

@@ -282,8 +282,11 @@ void launchHalpernDual(const MatView& A, const HalpernVecs& h, hipStream_t s);
 void launchDecidePrimal(const IterVecs& v, const DevState* stIn, DevState* stOut, const double* partDY, int32_t nDY,
                         const double* partDX, const double* partInter, int32_t nDX, hipStream_t s,
                         const double* partQ = nullptr, int32_t nQ = 0);
-// QP with off-diagonal Hessian entries: nx_next = N x_next fused with the partials of dx . N dx (the third SpMV of a trial)
-void launchSpmvQxInteract(const MatView& N, const IterVecs& v, const DevState* st, double* partQ, hipStream_t s);
+// QP with off-diagonal Hessian entries: nx_next = N x_next fused with the partials of dx . N dx (the third SpMV of a trial).
+// xFull (nullptr: v.x) = the vectors N gathers from, by parity.  A mesh rank passes its rows [c0, c1) of N, the full-length
+// x and v = the own column slice, whose x / nx the epilogue reads and writes at major index r.
+void launchSpmvQxInteract(const MatView& N, const IterVecs& v, const DevState* st, double* partQ, hipStream_t s,
+                          const double* const xFull[2] = nullptr);
 void launchPrimalStep(const IterVecs& v, const DevState* st, hipStream_t s);
 // ax_next = A x_next fused with the dual step; writes per-block sum (dy)^2 to partDY[block]
 void launchSpmvAxDual(const MatView& A, const IterVecs& v, const DevState* st, double* partDY, hipStream_t s);

@@ -170,7 +170,8 @@ __global__ __launch_bounds__(kWave) void k_mesh_wait(DevState* st, const MeshArg
 
 // ---- hot loop ------------------------------------------------------------------------
 // x+ = clamp(x - tau (c - A'y), l, u) on the own column slice (cupdlp_step.c:16-40), stored
-// locally and pushed into every peer's recvX.
+// locally and pushed into every peer's recvX.  NX: QP with off-diagonal Hessian entries (v.nx set; an LP keeps its code).
+template <bool NX>
 __device__ __forceinline__ void primalStepAndPush(const IterVecs& v, const DevState* st, const MeshArgs& ma) {
   const MeshView* __restrict__ mv = ma.v; (void)mv;
   const int cur = st->cur, nxt = cur ^ 1;
@@ -199,6 +200,7 @@ __device__ __forceinline__ void primalStepAndPush(const IterVecs& v, const DevSt
       double t = xv[q];
       t += (-tau) * cv[q];
       t += tau * av[q];
+      if (NX) t += (-tau) * v.nx[cur][j];  // explicit gradient term of the off-diagonal part of Q (k_primal_step's order)
       if (v.qdiag) t = t / (1.0 + tau * v.qdiag[j]);  // QP prox step (diagonal Q)
       t = t < uv[q] ? t : uv[q];
       t = t > lv[q] ? t : lv[q];
@@ -230,11 +232,12 @@ __device__ __forceinline__ void copyOthers(const double* __restrict__ src, doubl
   }
 }
 
+template <bool NX>
 __global__ __launch_bounds__(kVecThreads) void k_mesh_primal_step(const IterVecs v, const DevState* st,
                                                                   const MeshArgs ma) {
   if (st->halted || dead(ma)) return;
   const long long e = ma.ms->seq + 1;
-  primalStepAndPush(v, st, ma);
+  primalStepAndPush<NX>(v, st, ma);
   lastBlockSignal(ma, kFlagX, e, 0);
 }
 
@@ -252,13 +255,14 @@ __global__ __launch_bounds__(kVecThreads) void k_mesh_wait_copy_x(const IterVecs
 // peers' epochs and copies its share of their slices.  vc = the own column slice, xFull = the two full-length iterates.
 // No block waits for anything before ITS pushes are out and a grid of at most 256 workgroups of 256 threads is resident
 // at once on a device of its own, so the waits cannot keep a producer off the CUs.
+template <bool NX>
 __global__ __launch_bounds__(kVecThreads) void k_mesh_primal_x(const IterVecs vc, double* __restrict__ x0Full,
                                                                double* __restrict__ x1Full, int nFull, DevState* st,
                                                                const MeshArgs ma) {
   const MeshView* __restrict__ mv = ma.v; (void)mv;
   if (st->halted || dead(ma)) return;
   const long long e = ma.ms->seq + 1;
-  primalStepAndPush(vc, st, ma);
+  primalStepAndPush<NX>(vc, st, ma);
   lastBlockSignal(ma, kFlagX, e, 0);
   if (!waitPeers(ma, kFlagX, e)) { fail(ma, st); return; }
   copyOthers(recvX(ma, ma.g), (st->cur ^ 1) ? x1Full : x0Full, mv->colOff[ma.g], mv->colOff[ma.g + 1], nFull);
@@ -363,15 +367,19 @@ __device__ __forceinline__ double orderedSum(const PeerPtrs& S, int j) {
 
 // One block: local sums of the three partial arrays -> every rank's mailbox -> rank-ordered
 // totals -> the accept/reject decision (identical bits, hence identical decisions, everywhere).
+// QP (with off-diagonal Hessian entries): the partials of dx . N dx over the own columns (partQ) are the fourth scalar of the
+// mailbox, summed in rank order like the other three.
+template <bool QP>
 __global__ __launch_bounds__(kVecThreads) void k_mesh_decide(DevState* st, const MeshArgs ma,
                                                              const double* __restrict__ partDY, int nDY,
                                                              const double* __restrict__ partDX,
-                                                             const double* __restrict__ partInter, int nDX) {
+                                                             const double* __restrict__ partInter, int nDX,
+                                                             const double* __restrict__ partQ, int nQ) {
   const MeshView* __restrict__ mv = ma.v; (void)mv;
   if (st->halted) return;
   if (dead(ma)) { fail(ma, st); return; }  // lets the host loop stop
   const long long e = ma.ms->seq + 1;
-  __shared__ double scratch[3][kVecThreads / kWave];
+  __shared__ double scratch[QP ? 4 : 3][kVecThreads / kWave];
   const int tid = threadIdx.x;
   auto laneSum = [&](const double* __restrict__ p, int count) {
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
@@ -384,29 +392,37 @@ __global__ __launch_bounds__(kVecThreads) void k_mesh_decide(DevState* st, const
     return (s0 + s1) + (s2 + s3);
   };
   double vY = laneSum(partDY, nDY), vX = laneSum(partDX, nDX), vI = laneSum(partInter, nDX);
+  double vQ = QP ? laneSum(partQ, nQ) : 0.0;
   vY = waveSum(vY); vX = waveSum(vX); vI = waveSum(vI);
+  if (QP) vQ = waveSum(vQ);
   const int lane = tid & (kWave - 1), w = tid / kWave;
-  if (lane == 0) { scratch[0][w] = vY; scratch[1][w] = vX; scratch[2][w] = vI; }
+  if (lane == 0) { scratch[0][w] = vY; scratch[1][w] = vX; scratch[2][w] = vI; if (QP) scratch[QP ? 3 : 0][w] = vQ; }
   __syncthreads();
   if (tid == 0) {
-    double dY2 = 0.0, dX2 = 0.0, inter = 0.0;
+    double dY2 = 0.0, dX2 = 0.0, inter = 0.0, qint = 0.0;
 #pragma unroll
-    for (int i = 0; i < kVecThreads / kWave; ++i) { dY2 += scratch[0][i]; dX2 += scratch[1][i]; inter += scratch[2][i]; }
+    for (int i = 0; i < kVecThreads / kWave; ++i) {
+      dY2 += scratch[0][i]; dX2 += scratch[1][i]; inter += scratch[2][i];
+      if (QP) qint += scratch[QP ? 3 : 0][i];  // (the LP instantiation has three rows)
+    }
     for (int h = 0; h < ma.G; ++h) {
       double* box = mailAt(ma, h, true, ma.g);
       sysStore(box + 0, dX2); sysStore(box + 1, dY2); sysStore(box + 2, inter);
+      if (QP) sysStore(box + 3, qint);
     }
     drainStores();
     signalPeers(ma, kFlagS, e);
   }
   if (!waitPeers(ma, kFlagS, e)) { fail(ma, st); return; }
   if (tid != 0) return;
-  double dX2 = 0.0, dY2 = 0.0, inter = 0.0;
+  double dX2 = 0.0, dY2 = 0.0, inter = 0.0, qint = 0.0;
   for (int h = 0; h < ma.G; ++h) {
     const double* box = mailAt(ma, ma.g, true, h);
     dX2 += sysLoad(box + 0); dY2 += sysLoad(box + 1); inter += sysLoad(box + 2);
+    if (QP) qint += sysLoad(box + 3);
   }
-  decideUpdate(st, dX2, dY2, inter);
+  if (QP) decideUpdate(st, dX2, dY2, inter, qint);
+  else decideUpdate(st, dX2, dY2, inter);
   ma.ms->seq = e;
 }
 
@@ -630,7 +646,8 @@ int32_t meshConsumerBlocks(int64_t len) { return capped((len + 3) / 4, 1024); } 
 
 // ---- launchers (dmv = the view in device memory) --------------------------------------------
 void launchMeshPrimalStep(const IterVecs& vc, const DevState* st, const MeshArgs& dmv, hipStream_t s) {
-  hipLaunchKernelGGL(k_mesh_primal_step, dim3(meshBlocks(vc.n)), dim3(kVecThreads), 0, s, vc, st, dmv);
+  if (vc.nx[0]) hipLaunchKernelGGL(k_mesh_primal_step<true>, dim3(meshBlocks(vc.n)), dim3(kVecThreads), 0, s, vc, st, dmv);
+  else hipLaunchKernelGGL(k_mesh_primal_step<false>, dim3(meshBlocks(vc.n)), dim3(kVecThreads), 0, s, vc, st, dmv);
 }
 void launchMeshWaitCopyX(const IterVecs& vf, const DevState* st, const MeshArgs& dmv, hipStream_t s) {
   if (!dmv.fusedWait) hipLaunchKernelGGL(k_mesh_wait, dim3(1), dim3(kWave), 0, s, const_cast<DevState*>(st), dmv, (int)kFlagX, 0LL);
@@ -639,8 +656,9 @@ void launchMeshWaitCopyX(const IterVecs& vf, const DevState* st, const MeshArgs&
                      s, vf, const_cast<DevState*>(st), dmv);
 }
 void launchMeshDecide(DevState* st, const MeshArgs& dmv, const double* partDY, int32_t nDY, const double* partDX,
-                      const double* partInter, int32_t nDX, hipStream_t s) {
-  hipLaunchKernelGGL(k_mesh_decide, dim3(1), dim3(kVecThreads), 0, s, st, dmv, partDY, nDY, partDX, partInter, nDX);
+                      const double* partInter, int32_t nDX, hipStream_t s, const double* partQ, int32_t nQ) {
+  if (partQ) hipLaunchKernelGGL(k_mesh_decide<true>, dim3(1), dim3(kVecThreads), 0, s, st, dmv, partDY, nDY, partDX, partInter, nDX, partQ, nQ);
+  else hipLaunchKernelGGL(k_mesh_decide<false>, dim3(1), dim3(kVecThreads), 0, s, st, dmv, partDY, nDY, partDX, partInter, nDX, partQ, nQ);
 }
 
 void launchMeshPushY(const IterVecs& vf, const double* const yFull[2], const DevState* st, const MeshArgs& dmv, hipStream_t s) {
@@ -654,8 +672,9 @@ void launchMeshWaitCopyY(double* const yFull[2], int32_t m, const DevState* st, 
 
 // fusedWait == 2: the X / Y exchange of a trial in one launch each (see k_mesh_primal_x)
 void launchMeshPrimalX(const IterVecs& vc, double* const xFull[2], int32_t nFull, DevState* st, const MeshArgs& dmv, hipStream_t s) {
-  hipLaunchKernelGGL(k_mesh_primal_x, dim3(capped((std::max(nFull, 1) + 3) / 4, 256)), dim3(kVecThreads), 0, s, vc, xFull[0], xFull[1], nFull,
-                     st, dmv);
+  const dim3 grid(capped((std::max(nFull, 1) + 3) / 4, 256));
+  if (vc.nx[0]) hipLaunchKernelGGL(k_mesh_primal_x<true>, grid, dim3(kVecThreads), 0, s, vc, xFull[0], xFull[1], nFull, st, dmv);
+  else hipLaunchKernelGGL(k_mesh_primal_x<false>, grid, dim3(kVecThreads), 0, s, vc, xFull[0], xFull[1], nFull, st, dmv);
 }
 void launchMeshY(double* const yFull[2], int32_t m, DevState* st, const MeshArgs& dmv, hipStream_t s) {
   hipLaunchKernelGGL(k_mesh_y, dim3(capped((std::max(m, 1) + 3) / 4, 256)), dim3(kVecThreads), 0, s, yFull[0], yFull[1], m, st, dmv);

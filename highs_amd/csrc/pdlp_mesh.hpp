@@ -17,7 +17,8 @@
 //   Y: y+[r0:r1) is pushed into every peer's recvY      (all-gather of y+; flag P)
 //   S: {dX^2, dY^2, interaction} partials go to every peer's mailbox; every rank
 //      adds the G triples in rank order and takes the identical accept/reject
-//      decision                                          (all-reduce of 3 scalars)
+//      decision                                          (all-reduce of 3 scalars;
+//      4 for a QP with off-diagonal Hessian entries: dx . N dx over the own columns)
 // All sums are in a fixed order, so every rank holds bit-identical x, step sizes
 // and control flow, run after run.  The sharded HiPDLP step uses the P mailbox for a reduce-scatter instead: the
 // partial A_g' y slice of owner h is pushed into h's recvP[g], and h adds the G contributions in RANK ORDER
@@ -151,8 +152,9 @@ class Mesh {
 // vf = the full-length view.
 void launchMeshPrimalStep(const IterVecs& vc, const DevState* st, const MeshArgs& dmv, hipStream_t s);
 void launchMeshWaitCopyX(const IterVecs& vf, const DevState* st, const MeshArgs& dmv, hipStream_t s);
+// partQ / nQ (QP with off-diagonal Hessian entries): the own columns' partials of dx . N dx, a fourth mailbox scalar
 void launchMeshDecide(DevState* st, const MeshArgs& dmv, const double* partDY, int32_t nDY, const double* partDX,
-                      const double* partInter, int32_t nDX, hipStream_t s);
+                      const double* partInter, int32_t nDX, hipStream_t s, const double* partQ = nullptr, int32_t nQ = 0);
 // Row block for A x, column block for A'y: the dual step's y+[r0:r1) is pushed into
 // every peer's recvY (flag P stands for "Y" there), then recvY -> yNext outside the own rows.  yNextFull = the
 // full-length y of the next parity on this rank.

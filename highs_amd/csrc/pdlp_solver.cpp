@@ -471,10 +471,7 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   gpuSetup_ = nnzIn >= 200000;
   if (sw_.gpuSetup >= 0) gpuSetup_ = sw_.gpuSetup != 0;
   hasQoff_ = hessianHasOffDiagonal(P);
-  if (hasQoff_) {
-    gpuSetup_ = false;  // the off-diagonal part of Q is scaled with the columns on the host (pdlp_host.cpp applyScaling)
-    if (sharded_) throw std::runtime_error("pdlp_mi355x: a Hessian with off-diagonal entries is solved on one GPU (num_devices = 1)");
-  }
+  if (hasQoff_) gpuSetup_ = false;  // the off-diagonal part of Q is scaled with the columns on the host (pdlp_host.cpp applyScaling)
   // sharded: every rank still prepares the WHOLE problem (Ruiz scaling couples all rows and columns) but does it on
   // its device and copies the result back once; only the row-block cut and the upload of its shard stay on the host
   const bool shardedGpuSetup = sharded_ && gpuSetup_;
@@ -625,7 +622,7 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   // block -> XCD assignment of the two operands (x_ / y_ are zero here: any input will do)
   tuneXcdMap(dA_, sw_, x_[0].get(), ax_[0].get(), stream_);
   tuneXcdMap(dAt_, sw_, y_[0].get(), sharded_ ? commBuf_.get() : aty_[0].get(), stream_);
-  if (hasQoff_) tuneXcdMap(dQ_, sw_, x_[0].get(), nx_[0].get(), stream_);
+  if (hasQoff_) tuneXcdMap(dQ_, sw_, x_[0].get(), nx_[0].get() + c0_, stream_);
   if (devEnv("PDLP_MI355X_SLAB_PROF") && rank_ == 0)  // (development: what the set-up chose, next to the per-block phase profile)
     for (const DeviceMatrix* M : {&dA_, &dAt_})
       fprintf(stderr, "slab operand %s: slab %d (width 2^%d, estimated run length %.1f), blocks %d, XCD map %s, %s, long majors %d, tasks %d in workgroups of %d\n", M == &dA_ ? "A" : "A'",
@@ -766,7 +763,19 @@ void Solver::uploadProblem() {
     if (F_.qoff.beg.empty()) log(1, "Quadratic objective (diagonal Hessian): proximal primal step\n");
   }
   if (!F_.qoff.beg.empty()) {
-    dQ_.upload(F_.qoff, n, n, sw_, stream_);
+    if (meshMode_) {
+      // mesh layout: the rows [c0, c1) of N — N is symmetric, so these are the columns of N x+ that the rank's primal
+      // step needs — over ALL columns: gathered from the full-length x, written to the own slice
+      Compressed qb;
+      const int32_t b = F_.qoff.beg[c0_], e = F_.qoff.beg[c1_];
+      qb.beg.resize((size_t)nLoc_ + 1);
+      for (int32_t j = 0; j <= nLoc_; ++j) qb.beg[j] = F_.qoff.beg[c0_ + j] - b;
+      qb.idx.assign(F_.qoff.idx.begin() + b, F_.qoff.idx.begin() + e);
+      qb.val.assign(F_.qoff.val.begin() + b, F_.qoff.val.begin() + e);
+      dQ_.upload(qb, nLoc_, n, sw_, stream_);
+    } else {  // one GPU, and the RCCL exchange: every rank steps all n columns, so it keeps the whole N
+      dQ_.upload(F_.qoff, n, n, sw_, stream_);
+    }
     log(1, "Quadratic objective (%lld off-diagonal Hessian entries): proximal step on the diagonal, explicit Q x term for the rest\n",
         (long long)F_.qoff.beg[n]);
     F_.qoff = Compressed();
@@ -932,6 +941,10 @@ void Solver::allocIterates() {
   vecs_.constCached = sw_.constCached >= 0 ? (sw_.constCached != 0) : constCached(dA_.nnz, n);
   vecsCol_ = vecs_;
   for (int k = 0; k < 2; ++k) { vecsCol_.x[k] += c0_; vecsCol_.aty[k] += c0_; }
+  // N x (QP with off-diagonal Hessian entries): nx_ and nxAvg_ are n long on every rank, but in the mesh layout only the own
+  // columns [c0, c1) are computed and valid (each rank holds the rows [c0, c1) of N); nothing reads the rest
+  if (hasQoff_)
+    for (int k = 0; k < 2; ++k) vecsCol_.nx[k] += c0_;
   vecsCol_.xSum += c0_; vecsCol_.cost += c0_; vecsCol_.lower += c0_; vecsCol_.upper += c0_;
   if (vecsCol_.qdiag) vecsCol_.qdiag += c0_;
   vecsCol_.n = nLoc_;
@@ -1125,7 +1138,7 @@ void Solver::initVariables() {
   launchProjectBounds(x_[0].get(), lower_.get(), upper_.get(), n, stream_);
   deviceAx(x_[0].get(), ax_[0].get());
   deviceATy(yl(0), aty_[0].get());
-  if (hasQoff_) launchSpmvPlain(dQ_.view(), x_[0].get(), nx_[0].get(), stream_);
+  if (hasQoff_) launchSpmvPlain(dQ_.view(), x_[0].get(), nx_[0].get() + c0_, stream_);
   xSum_.zero(stream_); ySum_.zero(stream_); xAvg_.zero(stream_); yAvg_.zero(stream_);
   launchProjectBounds(xSum_.get(), lower_.get(), upper_.get(), n, stream_);  // :583-584
   launchProjectBounds(xAvg_.get(), lower_.get(), upper_.get(), n, stream_);
@@ -1180,13 +1193,16 @@ void Solver::enqueueTrial() {
     // direct-exchange sequence (pdlp_mesh.hpp): X all-gather, Y all-gather, S scalars
     const MeshArgs& mv = mesh_->args();
     const bool oneLaunch = mv.fusedWait == 2;  // every rank on a GPU of its own: an exchange is one kernel (five launches per trial)
+    double* xFull[2] = {x_[0].get(), x_[1].get()};
     if (oneLaunch) {
-      double* xFull[2] = {x_[0].get(), x_[1].get()};
       launchMeshPrimalX(vecsCol_, xFull, F_.n, dst(), mv, stream_);
     } else {
       launchMeshPrimalStep(vecsCol_, dst(), mv, stream_);
       launchMeshWaitCopyX(vecs_, dst(), mv, stream_);
     }
+    // QP with off-diagonal Hessian entries: N x+ on the own columns (rows [c0, c1) of N, gathered from the full x+) and the
+    // partials of dx . N dx — the decision sums them over the ranks as a fourth scalar
+    if (hasQoff_) launchSpmvQxInteract(dQ_.view(), vecsCol_, dst(), partQ_.get(), stream_, xFull);
     launchSpmvAxDual(dA_.view(), vecs_, dst(), partDY_.get(), stream_);
     // Y all-gather of the dual step's rows, then A'y+ on the own COLUMNS from the column block: every column is
     // summed over all rows in the single-GPU order; no n-length partial is written, pushed and re-reduced
@@ -1198,7 +1214,8 @@ void Solver::enqueueTrial() {
       launchMeshWaitCopyY(yFull, F_.m, dst(), mv, stream_);
     }
     launchSpmvAtyInteract(dAt_.view(), vecsAty_, dst(), partDX_.get(), partInter_.get(), stream_);
-    launchMeshDecide(dst(), mv, partDY_.get(), dA_.nPartials(), partDX_.get(), partInter_.get(), dAt_.nPartials(), stream_);
+    launchMeshDecide(dst(), mv, partDY_.get(), dA_.nPartials(), partDX_.get(), partInter_.get(), dAt_.nPartials(), stream_,
+                     hasQoff_ ? partQ_.get() : nullptr, hasQoff_ ? dQ_.nPartials() : 0);
     return;
   }
   if (persistent_) {
@@ -1276,7 +1293,10 @@ void Solver::enqueueTrial() {
   comm_->allReduceSum(buf, (size_t)F_.n + 1, stream_);
   const int32_t nb = vecBlocks(F_.n);
   launchInteract(vecs_, dst(), buf, partDX_.get(), partInter_.get(), nb, stream_);
-  launchDecide(dst(), nullptr, 0, partDX_.get(), partInter_.get(), nb, buf + F_.n, stream_);
+  // QP with off-diagonal Hessian entries: every rank holds the whole N and x+, so N x+ and dx . N dx need no exchange
+  if (hasQoff_) launchSpmvQxInteract(dQ_.view(), vecs_, dst(), partQ_.get(), stream_);
+  launchDecide(dst(), nullptr, 0, partDX_.get(), partInter_.get(), nb, buf + F_.n, stream_, false, hasQoff_ ? partQ_.get() : nullptr,
+               hasQoff_ ? dQ_.nPartials() : 0);
 }
 
 // The batch of kGraphTrials (even) trials as one hipGraph.  Capturing enqueues nothing; the state-slot
@@ -1381,7 +1401,8 @@ void Solver::computeAverage() {
   if (meshMode_) mesh_->allGather(xAvg_.get(), false, stream_);
   deviceAx(xAvg_.get(), axAvg_.get());
   deviceATy(yAvgl(), atyAvg_.get());
-  if (hasQoff_) launchSpmvPlain(dQ_.view(), xAvg_.get(), nxAvg_.get(), stream_);
+  // (mesh: after the all-gather above, so that the rows [c0, c1) of N gather from the whole average)
+  if (hasQoff_) launchSpmvPlain(dQ_.view(), xAvg_.get(), nxAvg_.get() + c0_, stream_);
 }
 
 // PDHG_Compute_Residuals + PDHG_Compute_Infeas_Residuals (cupdlp_solver.c:433-529)
@@ -1396,7 +1417,7 @@ void Solver::computeResiduals() {
   // both iterates per pass (shared vectors read once), one reduction launch for all 30 quantities
   launchRowStats2(vecs_, CheckGate(), c, axAvg_.get(), yAvgl(), rowScale_.get(), sc, part + (size_t)kStatRowCur * statStride_, statStride_,
                   nbM, stream_);
-  launchColStats2(vecsCol_, CheckGate(), c, atyAvg_.get() + co, xAvg_.get() + co, colScale_.get() + co, hasQoff_ ? nxAvg_.get() : nullptr,
+  launchColStats2(vecsCol_, CheckGate(), c, atyAvg_.get() + co, xAvg_.get() + co, colScale_.get() + co, hasQoff_ ? nxAvg_.get() + co : nullptr,
                   sc, slackPos_.get() + co, slackNeg_.get() + co, slackPosAvg_.get() + co, slackNegAvg_.get() + co,
                   part + (size_t)kStatColCur * statStride_, statStride_, nbN, stream_);
   launchFinalReduce2(part, statStride_, 2 * kRowStats, nbM, 2 * kColStats, nbN, statOut_.get(), CheckGate(), stream_);
@@ -1614,14 +1635,15 @@ void Solver::enqueueCheckDevice() {
     launchFlushScale(vecsCol_, g, 0, 0.0, 0.0, 1.0, 1.0, xAvg_.get() + co, yAvgl(), stream_);
     mesh_->allGather(xAvg_.get(), false, stream_);
     launchSpmvPlain(dA_.view(), xAvg_.get(), axAvg_.get(), stream_, g);
+    if (hasQoff_) launchSpmvPlain(dQ_.view(), xAvg_.get(), nxAvg_.get() + co, stream_, g);  // N xAvg on the own columns
     mesh_->allGather(yAvg_.get(), true, stream_);  // (yAvgl() = this rank's rows inside the full-length vector)
     launchSpmvPlain(dAt_.view(), yAvg_.get(), atyAvg_.get() + co, stream_, g);
     mesh_->allGather(atyAvg_.get(), false, stream_);
     launchRowStats2(vecs_, g, 0, axAvg_.get(), yAvgl(), rowScale_.get(), sc, part + (size_t)kStatRowCur * statStride_, statStride_, nbM,
                     stream_);
-    launchColStats2(vecsCol_, g, 0, atyAvg_.get() + co, xAvg_.get() + co, colScale_.get() + co, nullptr, sc, slackPos_.get() + co,
-                    slackNeg_.get() + co, slackPosAvg_.get() + co, slackNegAvg_.get() + co, part + (size_t)kStatColCur * statStride_,
-                    statStride_, nbN, stream_);
+    launchColStats2(vecsCol_, g, 0, atyAvg_.get() + co, xAvg_.get() + co, colScale_.get() + co, hasQoff_ ? nxAvg_.get() + co : nullptr, sc,
+                    slackPos_.get() + co, slackNeg_.get() + co, slackPosAvg_.get() + co, slackNegAvg_.get() + co,
+                    part + (size_t)kStatColCur * statStride_, statStride_, nbN, stream_);
     mesh_->reduce2AllReduce(part, statStride_, 2 * kRowStats, nbM, 2 * kColStats, nbN, statOut_.get(), g, stream_);
     CheckRecord* rec = hostRing_ + (checkSeq_ % kRingSlots);
     rec->ran = 0;
@@ -1631,7 +1653,8 @@ void Solver::enqueueCheckDevice() {
     double* as[2] = {aty_[0].get(), aty_[1].get()};
     double* ys[2] = {y_[0].get(), y_[1].get()};
     launchRestartCopyFull(st, dCtl_.get(), xs, as, ys, xAvg_.get(), atyAvg_.get(), yAvg_.get(), F_.n, yLen_, stream_);
-    const RestartVecs rv{xAvg_.get() + co, yAvgl(), axAvg_.get(), atyAvg_.get() + co, nullptr, xLast_.get() + co, yLast_.get()};
+    const RestartVecs rv{xAvg_.get() + co, yAvgl(), axAvg_.get(), atyAvg_.get() + co, hasQoff_ ? nxAvg_.get() + co : nullptr,
+                         xLast_.get() + co, yLast_.get()};  // (nx: valid on the own columns only, see allocIterates)
     launchRestartVec(vecsCol_, st, dCtl_.get(), rv, partDX_.get(), nbN, partRestartY_.get(), nbM, stream_);
     // the two norms of the primal-weight update: this rank's partials -> one scalar each (reduceScalar's kernel) -> summed
     // over the ranks in rank order -> k_restart_finish takes them as partial arrays of length one
@@ -2070,15 +2093,17 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
   } else if (name == "trial_launches") {  // kernels per trial step of the hot loop (2 = fused decision + primal step)
     // mesh: 9 with single-block wait kernels, 7 with consumers that wait themselves, 5 with an exchange per launch
     // (fusedWait 0 / 1 / 2)
+    // (+1 for a sharded QP with off-diagonal Hessian entries: N x+ with the partials of dx . N dx)
     const int fw = meshMode_ ? mesh_->args().fusedWait : 0;
-    put(0, meshMode_ ? 9.0 - 2.0 * fw : sharded_ ? 7.0 : persistent_ ? 0.0 : fused_ ? 2.0 : 3.0);  // 0: one persistent launch per batch
+    const double qx = sharded_ && hasQoff_ ? 1.0 : 0.0;
+    put(0, meshMode_ ? 9.0 - 2.0 * fw + qx : sharded_ ? 7.0 + qx : persistent_ ? 0.0 : fused_ ? 2.0 : 3.0);  // 0: one persistent launch per batch
   } else if (name == "trial_barriers") {  // grid barriers per trial of the persistent loop (0: no persistent loop)
     put(0, !persistent_ ? 0.0 : primalInA_ ? 2.0 : 3.0);
   } else if (name == "check_launches") {  // kernels of one device-driven check iteration (1: the one-launch form of small LPs;
     // sharded: 12 gated kernels + three all-gathers of 4 launches + two scalar all-reduces = 26, with an exchange per
     // launch (fusedWait 2) 9 gated kernels + three all-gathers + the two reductions with their all-reduces = 14;
-    // 0: the host drives the checks)
-    put(0, !devCheck_ ? 0.0 : sharded_ ? (mesh_ && mesh_->args().fusedWait == 2 ? 14.0 : 26.0) : persistent_ && checkSmall_ ? 1.0 : 10.0);
+    // 0: the host drives the checks; +1 for a sharded QP with off-diagonal Hessian entries: N xAvg)
+    put(0, !devCheck_ ? 0.0 : sharded_ ? (mesh_ && mesh_->args().fusedWait == 2 ? 14.0 : 26.0) + (hasQoff_ ? 1.0 : 0.0) : persistent_ && checkSmall_ ? 1.0 : 10.0);
   } else if (name == "barrier_fallbacks") {  // times a launch with grid barriers gave up and the loop went on with plain launches
     put(0, (double)barrierFallbacks_);
   } else if (name == "uniform_bound_columns") {  // columns whose lower / upper bound the fused launch takes from a scalar of their block
