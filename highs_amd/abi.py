@@ -73,7 +73,7 @@ class PdlpParams(C.Structure):
         ("ruiz_iterations", C.c_int32),     # pdlp_ruiz_iterations
         ("step_size_strategy", C.c_int32),  # pdlp_step_size_strategy: 0 fixed, else PID
         ("num_devices", C.c_int32),         # pdlp_mi355x_solve: shard over this many devices of the process
-        ("reserved2", C.c_int32),
+        ("updatable", C.c_int32),           # create: keep what pdlp_mi355x_update replays (per-pass scale factors, row kinds)
         ("log_callback", C.c_void_p),       # void (*)(void* ctx, int level, const char* text); NULL = stdout
         ("log_ctx", C.c_void_p),
     ]
@@ -103,6 +103,23 @@ class PdlpResult(C.Structure):
         ("setup_seconds", C.c_double),
         ("solve_seconds", C.c_double),
         ("reserved_d", C.c_double * 4),
+    ]
+
+
+class PdlpUpdate(C.Structure):
+    """pdlp_update_t (include/pdlp_mi355x.h): new data for a held solver; NULL = unchanged."""
+    _fields_ = [
+        ("col_cost", c_f64p),
+        ("col_lower", c_f64p),
+        ("col_upper", c_f64p),
+        ("row_lower", c_f64p),
+        ("row_upper", c_f64p),
+        ("offset", C.c_double),
+        ("has_offset", C.c_int32),
+        ("reserved", C.c_int32),
+        ("start_col_value", c_f64p),
+        ("start_row_value", c_f64p),
+        ("start_row_dual", c_f64p),
     ]
 
 
@@ -199,6 +216,8 @@ def default_params(**kw):
             p.algorithm = {"pdlp": 0, "hipdlp": 1}[v]
         elif k in ("pdlp_scaling_mode", "pdlp_ruiz_iterations", "pdlp_step_size_strategy"):
             setattr(p, k[5:], int(v))
+        elif k == "updatable":
+            p.updatable = 1 if v else 0
         elif k == "device_reduction_order":
             # ORACLE ONLY: sum the reductions in the HIP kernels' order (oracle/pdlp_oracle.c, GPU-ORDER)
             p.reserved[0] = 1 if v else 0
@@ -286,3 +305,34 @@ class ResultHandle:
 
     def __getattr__(self, k):
         return getattr(self.__dict__["struct"], k)
+
+
+class UpdateHandle:
+    """Owns the numpy buffers a pdlp_update_t points to.  None = unchanged; `start` is a dict with col_value, row_value
+    and row_dual (all three) or None for a cold start.  Partial input (one row bound, part of a start) is passed on as it
+    is: the library refuses it with its own message."""
+
+    def __init__(self, col_cost=None, col_lower=None, col_upper=None, row_lower=None, row_upper=None, offset=None, start=None):
+        U = PdlpUpdate()
+        self._keep = []
+
+        def put(name, a):
+            if a is None:
+                return
+            a = _f64(a)
+            self._keep.append(a)
+            setattr(U, name, _ptr(a, c_f64p))
+
+        put("col_cost", col_cost)
+        put("col_lower", col_lower)
+        put("col_upper", col_upper)
+        put("row_lower", row_lower)
+        put("row_upper", row_upper)
+        if offset is not None:
+            U.offset = float(offset)
+            U.has_offset = 1
+        if start is not None:
+            put("start_col_value", start.get("col_value"))
+            put("start_row_value", start.get("row_value"))
+            put("start_row_dual", start.get("row_dual"))
+        self.struct = U

@@ -15,6 +15,7 @@
 #include "pdlp_halpern.hpp"
 #include "pdlp_mps.hpp"
 #include "pdlp_solver.hpp"
+#include "pdlp_update.hpp"
 #include "pdlp_detmath.h"
 
 struct pdlp_mi355x_solver {
@@ -173,6 +174,14 @@ int pdlp_mi355x_run(pdlp_mi355x_solver_t* s, pdlp_result_t* R) {
   });
 }
 
+int pdlp_mi355x_update(pdlp_mi355x_solver_t* s, const pdlp_update_t* u) {
+  return guarded([&] {
+    if (!s || !s->impl) throw std::runtime_error("pdlp_mi355x_update: null solver");
+    if (!u) throw std::runtime_error("pdlp_mi355x_update: null update");
+    s->impl->update(*u);
+  });
+}
+
 void pdlp_mi355x_destroy(pdlp_mi355x_solver_t* s) {
   if (!s) return;
   try {
@@ -318,29 +327,51 @@ int pdlp_mi355x_time_kernel(pdlp_mi355x_solver_t* s, const char* kernel, int32_t
   });
 }
 
+namespace {
+// host_prepare, optionally followed by the host restatement of an update (u != nullptr)
+void hostPrepare(const pdlp_problem_t* P, const pdlp_params_t* opt, const pdlp_update_t* u, pdlp_prepared_t* out) {
+  memset(out, 0, sizeof(*out));
+  pdlp::StandardForm F;
+  if (opt->algorithm == 1) {  // HiPDLP form: rhs = row lower bounds (row upper bounds are not exported)
+    pdlp::formulateHipdlp(*P, F);
+    if (!(opt->features_off & PDLP_FEATURE_SCALING_OFF))
+      pdlp::scaleHipdlp(F, opt->scaling_mode & 1, opt->scaling_mode & 4, opt->scaling_mode & 2, opt->ruiz_iterations);
+  } else {
+    pdlp::formulate(*P, F);
+    F.keepPasses = u != nullptr;
+    if (!(opt->features_off & PDLP_FEATURE_SCALING_OFF)) pdlp::scale(F);
+    if (u) pdlp::hostReplayUpdate(*u, F);
+  }
+  pdlp::finalize(F);
+  out->n = F.n; out->m = F.m; out->n_eqs = F.nEqs; out->n_orig = F.n0; out->nnz = F.nnz;
+  out->csr_beg = dupVec(F.csr.beg); out->csr_idx = dupVec(F.csr.idx); out->csr_val = dupVec(F.csr.val);
+  out->csc_beg = dupVec(F.cscSorted.beg); out->csc_idx = dupVec(F.cscSorted.idx); out->csc_val = dupVec(F.cscSorted.val);
+  out->cost = dupVec(F.cost); out->rhs = dupVec(F.rhs); out->lower = dupVec(F.lower); out->upper = dupVec(F.upper);
+  out->col_scale = dupVec(F.colScale); out->row_scale = dupVec(F.rowScale);
+  out->row_kind = dupVec(F.rowKind); out->row_new_idx = dupVec(F.rowNewIdx);
+  out->norm_cost = F.normCost; out->norm_rhs = F.normRhs; out->mat_norm_inf = F.matNormInf;
+  out->spmv_blocks_ax = pdlp::planStream(F.csr.beg, F.m, pdlp::spmvChunkFor(F.nnz), pdlp::kMaxMajorsPerBlock).nBlocks;
+  out->spmv_blocks_aty = pdlp::planStream(F.cscSorted.beg, F.n, pdlp::spmvChunkFor(F.nnz), pdlp::kMaxMajorsPerBlock).nBlocks;
+}
+}  // namespace
+
 int pdlp_mi355x_host_prepare(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_prepared_t* out) {
   return guarded([&] {
     if (!P || !opt || !out) throw std::runtime_error("null argument");
-    memset(out, 0, sizeof(*out));
-    pdlp::StandardForm F;
-    if (opt->algorithm == 1) {  // HiPDLP form: rhs = row lower bounds (row upper bounds are not exported)
-      pdlp::formulateHipdlp(*P, F);
-      if (!(opt->features_off & PDLP_FEATURE_SCALING_OFF))
-        pdlp::scaleHipdlp(F, opt->scaling_mode & 1, opt->scaling_mode & 4, opt->scaling_mode & 2, opt->ruiz_iterations);
-    } else {
-      pdlp::formulate(*P, F);
-      if (!(opt->features_off & PDLP_FEATURE_SCALING_OFF)) pdlp::scale(F);
-    }
-    pdlp::finalize(F);
-    out->n = F.n; out->m = F.m; out->n_eqs = F.nEqs; out->n_orig = F.n0; out->nnz = F.nnz;
-    out->csr_beg = dupVec(F.csr.beg); out->csr_idx = dupVec(F.csr.idx); out->csr_val = dupVec(F.csr.val);
-    out->csc_beg = dupVec(F.cscSorted.beg); out->csc_idx = dupVec(F.cscSorted.idx); out->csc_val = dupVec(F.cscSorted.val);
-    out->cost = dupVec(F.cost); out->rhs = dupVec(F.rhs); out->lower = dupVec(F.lower); out->upper = dupVec(F.upper);
-    out->col_scale = dupVec(F.colScale); out->row_scale = dupVec(F.rowScale);
-    out->row_kind = dupVec(F.rowKind); out->row_new_idx = dupVec(F.rowNewIdx);
-    out->norm_cost = F.normCost; out->norm_rhs = F.normRhs; out->mat_norm_inf = F.matNormInf;
-    out->spmv_blocks_ax = pdlp::planStream(F.csr.beg, F.m, pdlp::spmvChunkFor(F.nnz), pdlp::kMaxMajorsPerBlock).nBlocks;
-    out->spmv_blocks_aty = pdlp::planStream(F.cscSorted.beg, F.n, pdlp::spmvChunkFor(F.nnz), pdlp::kMaxMajorsPerBlock).nBlocks;
+    hostPrepare(P, opt, nullptr, out);
+  });
+}
+
+int pdlp_mi355x_host_prepare_updated(const pdlp_problem_t* P, const pdlp_params_t* opt, const pdlp_update_t* u,
+                                     pdlp_prepared_t* out) {
+  return guarded([&] {
+    if (!P || !opt || !out) throw std::runtime_error("null argument");
+    if (!u) throw std::runtime_error("pdlp_mi355x_update: null update");
+    // the refusals of pdlp_mi355x_update that depend on how the solver was created
+    if (opt->algorithm == 1) throw std::runtime_error("pdlp_mi355x_update: HiPDLP solvers (algorithm = 1) do not take updates");
+    if (!opt->updatable)
+      throw std::runtime_error("pdlp_mi355x_update: the solver was not created for updates (pdlp_params_t.updatable = 0)");
+    hostPrepare(P, opt, u, out);
   });
 }
 
@@ -443,6 +474,7 @@ int64_t pdlp_mi355x_sizeof(int32_t which) {
     case 5: return sizeof(pdlp_slab_layout_t);
     case 6: return sizeof(pdlp_mps_model_t);
     case 7: return sizeof(pdlp_task_plan_t);
+    case 8: return sizeof(pdlp_update_t);
     default: return -1;
   }
 }

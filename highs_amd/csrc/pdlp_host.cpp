@@ -184,12 +184,7 @@ void formulate(const pdlp_problem_t& P, StandardForm& F) {
   F.rowNewIdx.resize(m);
   int32_t nSlack = 0, nEq = 0;
   for (int32_t i = 0; i < m; ++i) {
-    const bool lo = P.row_lower[i] > -kBoundInf, up = P.row_upper[i] < kBoundInf;
-    RowKind k;
-    if (lo && up && P.row_lower[i] == P.row_upper[i]) k = kRowEq;
-    else if (lo && !up) k = kRowGeq;
-    else if (!lo && up) k = kRowLeq;
-    else k = kRowBound;
+    const int32_t k = rowKindOf(P.row_lower[i], P.row_upper[i]);
     F.rowKind[i] = k;
     if (k == kRowEq || k == kRowBound) ++nEq;
     if (k == kRowBound) ++nSlack;
@@ -261,14 +256,27 @@ void formulate(const pdlp_problem_t& P, StandardForm& F) {
 
   // Termination norms are those of the UNSCALED formulated data (Init_Scaling
   // runs before PDHG_Scale_Data, CupdlpWrapper.cpp:110 vs :153).
-  double s = 0.0;
-  for (double v : F.cost) s += v * v;
-  F.normCost = std::sqrt(s);
-  s = 0.0;
-  for (double v : F.rhs) s += v * v;
-  F.normRhs = std::sqrt(s);
+  F.normCost = unscaledNormCost(P.col_cost, n0, F.sense);
+  F.normRhs = unscaledNormRhs(P.row_lower, P.row_upper, F.rowKind.data(), m);
   F.colScale.assign(F.n, 1.0);
   F.rowScale.assign(m, 1.0);
+}
+
+double unscaledNormCost(const double* colCost, int32_t n0, double costSense) {
+  double s = 0.0;
+  for (int32_t j = 0; j < n0; ++j) { const double v = colCost[j] * costSense; s += v * v; }
+  return std::sqrt(s);  // slack costs are 0
+}
+
+double unscaledNormRhs(const double* rowLower, const double* rowUpper, const int32_t* rowKind, int32_t m) {
+  double s = 0.0;  // permuted order: equality-type rows first (slack rows have rhs 0), then inequalities
+  for (int32_t i = 0; i < m; ++i)
+    if (rowKind[i] == kRowEq) s += rowLower[i] * rowLower[i];
+    else if (rowKind[i] == kRowBound || rowKind[i] == kRowFree) s += 0.0;
+  for (int32_t i = 0; i < m; ++i)
+    if (rowKind[i] == kRowLeq) s += (-rowUpper[i]) * (-rowUpper[i]);
+    else if (rowKind[i] == kRowGeq) s += rowLower[i] * rowLower[i];
+  return std::sqrt(s);
 }
 
 namespace {
@@ -296,6 +304,12 @@ void applyScaling(StandardForm& F, const std::vector<double>& cs, const std::vec
     for (int32_t p = A.beg[j]; p < A.beg[j + 1]; ++p) A.val[p] = (A.val[p] / rs[A.idx[p]]) / c;
   }
 }
+void keepPass(StandardForm& F, const std::vector<double>& cs, const std::vector<double>& rs) {
+  if (!F.keepPasses) return;
+  F.csPass.insert(F.csPass.end(), cs.begin(), cs.end());
+  F.rsPass.insert(F.rsPass.end(), rs.begin(), rs.end());
+  ++F.nPass;
+}
 }  // namespace
 
 void scale(StandardForm& F, int ruizTimes, double pcAlpha) {
@@ -315,6 +329,7 @@ void scale(StandardForm& F, int ruizTimes, double pcAlpha) {
     }
     for (int32_t i = 0; i < F.m; ++i) rs[i] = rs[i] == 0.0 ? 1.0 : std::sqrt(rs[i]);
     applyScaling(F, cs, rs);
+    keepPass(F, cs, rs);
   }
   // Pock-Chambolle (cupdlp_pc_scaling :174-231).  The reference fixes alpha=1
   // (Init_Scaling :409), for which pow(|a|,alpha) and pow(s,1/alpha) are exact
@@ -340,6 +355,7 @@ void scale(StandardForm& F, int ruizTimes, double pcAlpha) {
     std::fill(cs.begin(), cs.end(), 1.0);
   }
   applyScaling(F, cs, rs);
+  keepPass(F, cs, rs);
   F.scaled = true;
 }
 

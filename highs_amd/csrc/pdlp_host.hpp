@@ -27,6 +27,21 @@ void logLineV(const pdlp_params_t& opt, int level, const char* fmt, va_list ap);
 
 enum RowKind : int32_t { kRowEq = 0, kRowLeq = 1, kRowGeq = 2, kRowBound = 3 };  // cupdlp_defs.h types
 
+#if defined(__HIPCC__)
+#define PDLP_HOSTDEV __host__ __device__
+#else
+#define PDLP_HOSTDEV
+#endif
+// The kind of a row of the cuPDLP-C form from its bounds (CupdlpWrapper.cpp:316-343; beyond +-1e20 is infinite): ranged
+// AND free rows are kRowBound.  formulate() and the update path (pdlp_update.hpp, host and device) share it.
+PDLP_HOSTDEV inline int32_t rowKindOf(double lower, double upper) {
+  const bool lo = lower > -1e20, up = upper < 1e20;
+  if (lo && up && lower == upper) return kRowEq;
+  if (lo && !up) return kRowGeq;
+  if (!lo && up) return kRowLeq;
+  return kRowBound;
+}
+
 // Sparse matrix in compressed form; "major" is rows for CSR, columns for CSC.
 struct Compressed {
   std::vector<int32_t> beg;   // [nMajor+1]
@@ -53,6 +68,12 @@ struct StandardForm {
   std::vector<int32_t> rowNewIdx;  // original row -> permuted row
   std::vector<double> colScale, rowScale;
   bool scaled = false;
+  // Updatable solvers (pdlp_update.hpp): scale() also keeps the factors of every pass, pass-major — csPass[p * n + j],
+  // rsPass[p * m + i] — because cost, bounds and rhs take them one pass at a time and the accumulated colScale / rowScale
+  // do not give the same bits
+  bool keepPasses = false;
+  int32_t nPass = 0;
+  std::vector<double> csPass, rsPass;
   double offset = 0.0, sense = 1.0;
   double normCost = 0.0, normRhs = 0.0;  // of the unscaled formulated data
   double matNormInf = 0.0;               // max |a_ij| of the (scaled) matrix
@@ -69,6 +90,11 @@ void extractDiagonalHessian(const pdlp_problem_t& P, double sense, int32_t n, st
 void extractHessian(const pdlp_problem_t& P, double sense, int32_t n, std::vector<double>& qdiag, Compressed& qoff);
 bool hessianHasOffDiagonal(const pdlp_problem_t& P);
 void formulate(const pdlp_problem_t& P, StandardForm& F);
+// ||c||_2 and ||b||_2 of the UNSCALED formulated data, summed left to right as Init_Scaling does (cupdlp_scaling.c:395-425):
+// the costs of the original columns with the sense (slack costs are 0); the right-hand side in the PERMUTED row order,
+// equality-type rows first, then inequalities.  Shared by formulate(), the device-side set-up and the update path.
+double unscaledNormCost(const double* colCost, int32_t n0, double costSense);
+double unscaledNormRhs(const double* rowLower, const double* rowUpper, const int32_t* rowKind, int32_t m);
 void scale(StandardForm& F, int ruizTimes = 10, double pcAlpha = 1.0);
 void finalize(StandardForm& F);  // CSR + row-sorted CSC + matNormInf
 

@@ -445,19 +445,8 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
   kind.download(D.rowKind.data(), m, s);
   rowNew.download(D.rowNewIdx.data(), m, s);
   PDLP_HIP(hipStreamSynchronize(s));
-  {
-    double sc = 0.0;
-    for (int32_t j = 0; j < n0; ++j) { const double v = P.col_cost[j] * costSense; sc += v * v; }
-    D.normCost = std::sqrt(sc);  // slack costs are 0
-    double sr = 0.0;  // permuted order: equality-type rows first, then inequalities
-    for (int32_t i = 0; i < m; ++i)
-      if (D.rowKind[i] == kRowEq) sr += P.row_lower[i] * P.row_lower[i];
-      else if (D.rowKind[i] == kRowBound || D.rowKind[i] == kRowFree) sr += 0.0;
-    for (int32_t i = 0; i < m; ++i)
-      if (D.rowKind[i] == kRowLeq) sr += (-P.row_upper[i]) * (-P.row_upper[i]);
-      else if (D.rowKind[i] == kRowGeq) sr += P.row_lower[i] * P.row_lower[i];
-    D.normRhs = std::sqrt(sr);
-  }
+  D.normCost = unscaledNormCost(P.col_cost, n0, costSense);
+  D.normRhs = unscaledNormRhs(P.row_lower, P.row_upper, D.rowKind.data(), m);
 
   // A by rows (ascending column): stable sort of the column-major entries by row
   transposeOnDevice(cscCol.get(), cscIdx.get(), cscVal.get(), nnz, m, n, s, D.A);
@@ -523,6 +512,8 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
     DeviceArray<double> cs, rs;
     cs.alloc(n);
     rs.alloc(m);
+    constexpr int kPasses = 11;  // Ruiz x 10 + Pock-Chambolle
+    if (D.keepPasses) { D.csPass.alloc((size_t)kPasses * n); D.rsPass.alloc((size_t)kPasses * m); }
     auto pass = [&](bool sum) {
       if (sum) {
         hipLaunchKernelGGL(k_major_reduce<true>, dim3(gridFor(n)), dim3(kT), 0, s, cscBeg.get(), cscVal.get(), n, cs.get());
@@ -538,6 +529,11 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
                          cs.get(), nnz, cscVal.get());
       hipLaunchKernelGGL(k_scale_vals, dim3(gridFor(nnz)), dim3(kT), 0, s, D.A.major.get(), D.A.idx.get(), rs.get(),
                          cs.get(), nnz, D.A.val.get());
+      if (D.keepPasses) {
+        if (n > 0) PDLP_HIP(hipMemcpyAsync(D.csPass.get() + (size_t)D.nPass * n, cs.get(), sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+        if (m > 0) PDLP_HIP(hipMemcpyAsync(D.rsPass.get() + (size_t)D.nPass * m, rs.get(), sizeof(double) * m, hipMemcpyDeviceToDevice, s));
+        ++D.nPass;
+      }
     };
     for (int it = 0; it < 10; ++it) pass(false);
     pass(true);

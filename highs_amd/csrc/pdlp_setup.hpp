@@ -48,6 +48,11 @@ struct DeviceProblem {
   std::vector<double> hColScale, hRowScale;
   double normCost = 0, normRhs = 0, matNormInf = 0;
   double sumCost2 = 0, sumRhs2 = 0;  // left-to-right sums of the SCALED c, b (PDHG_Init_Step_Sizes)
+  // Updatable solvers (set keepPasses before gpuPrepare; cuPDLP-C form only): the scale factors of every pass, pass-major
+  // as StandardForm::csPass / rsPass, copied device-to-device out of the pass's temporaries
+  bool keepPasses = false;
+  int32_t nPass = 0;
+  DeviceArray<double> csPass, rsPass;
 };
 
 // Options of the HiPDLP form (pdlp_host.hpp formulateHipdlp / scaleHipdlp); nullptr = cuPDLP-C form.

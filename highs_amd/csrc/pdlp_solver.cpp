@@ -477,7 +477,10 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   const bool shardedGpuSetup = sharded_ && gpuSetup_;
   if (sharded_) gpuSetup_ = false;
   const bool doScale = !(opt_.features_off & PDLP_FEATURE_SCALING_OFF);
+  updatable_ = opt_.updatable != 0 && !sharded_;  // (a sharded solver refuses updates: nothing to keep)
   DeviceProblem devProb;
+  devProb.keepPasses = updatable_;
+  F_.keepPasses = updatable_;
   if (gpuSetup_) {
     // formulate + scale + both orientations on the device; F_ keeps only the host-side bookkeeping
     gpuPrepare(P, doScale, stream_, devProb);
@@ -491,6 +494,7 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
     F_.rowScale = std::move(devProb.hRowScale);
     sumCost2_ = devProb.sumCost2;
     sumRhs2_ = devProb.sumRhs2;
+    if (updatable_) keepForUpdates(&devProb);
   } else if (shardedGpuSetup) {
     gpuPrepare(P, doScale, stream_, devProb);
     sumCost2_ = devProb.sumCost2;
@@ -519,8 +523,10 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
     }
   } else {
     formulate(P, F_);
+    F_.keepPasses = updatable_;  // (formulate starts from a fresh form)
     if (doScale) scale(F_);
     finalize(F_);
+    if (updatable_) keepForUpdates(nullptr);
     sumCost2_ = 0.0;
     for (double v : F_.cost) sumCost2_ += v * v;
     sumRhs2_ = 0.0;
@@ -532,22 +538,8 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
            "faster than the reference's CPU pdlp\n", (long long)F_.nnz);
 
   // hot start in formulated+scaled space (PDHG_PreSolve, cupdlp_solver.c:1217-1279)
-  if (P.start_value_valid && P.start_dual_valid && P.start_col_value && P.start_row_value && P.start_row_dual) {
-    startX_.assign(F_.n, 0.0);
-    startY_.assign(F_.m, 0.0);
-    int32_t j = 0;
-    for (; j < F_.n0; ++j) startX_[j] = P.start_col_value[j];
-    for (int32_t i = 0; i < F_.m; ++i) {
-      const double mu = F_.rowKind[i] == kRowLeq ? -1.0 : 1.0;
-      startY_[F_.rowNewIdx[i]] = F_.sense * mu * P.start_row_dual[i];
-      if (F_.rowKind[i] == kRowBound) startX_[j++] = P.start_row_value[i];
-    }
-    if (F_.scaled) {
-      for (int32_t k = 0; k < F_.n; ++k) startX_[k] *= F_.colScale[k];
-      for (int32_t k = 0; k < F_.m; ++k) startY_[k] *= F_.rowScale[k];
-    }
-    hasStart_ = true;
-  }
+  if (P.start_value_valid && P.start_dual_valid && P.start_col_value && P.start_row_value && P.start_row_dual)
+    setHotStart(P.start_col_value, P.start_row_value, P.start_row_dual);
   // cuPDLP treats "either flag set" as has_variables (cupdlp_solver.c:1465) but
   // only fills x,y when both are; with one flag the start is the zero vector.
 
@@ -673,28 +665,7 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
       // per block instead of 8 / 16 bytes per column in the launch's bandwidth-bound tail (IterVecs::colBlockUni)
       colBlockUni_.alloc((size_t)at.slab.nBlocks);
       colBlockBounds_.alloc((size_t)at.slab.nBlocks * 2);
-      launchBlockBounds(lower_.get(), upper_.get(), at.slab.waveBeg, at.slab.nBlocks, colBlockUni_.get(), colBlockBounds_.get(), stream_);
-      std::vector<int32_t> uni((size_t)at.slab.nBlocks);
-      std::vector<double> bnd((size_t)at.slab.nBlocks * 2);
-      colBlockUni_.download(uni.data(), uni.size(), stream_);
-      colBlockBounds_.download(bnd.data(), bnd.size(), stream_);
-      PDLP_HIP(hipStreamSynchronize(stream_));
-      bool allLower = true;  // (bit patterns: the kernel's ULO instantiation takes ONE scalar for all columns)
-      for (size_t b = 0; b < uni.size(); ++b) allLower = allLower && (uni[b] & 1) && memcmp(&bnd[2 * b], &bnd[0], sizeof(double)) == 0;
-      {  // (for bench.py's needed bytes: how many columns' lower / upper bounds the fused launch does not load)
-        std::vector<int32_t> wb((size_t)at.slab.nBlocks * kSlabWavesPerBlock + 1);
-        PDLP_HIP(hipMemcpyAsync(wb.data(), at.slab.waveBeg, wb.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-        PDLP_HIP(hipStreamSynchronize(stream_));
-        uniLowerCols_ = uniUpperCols_ = 0;
-        for (size_t b = 0; b < uni.size(); ++b) {
-          const int64_t cols = wb[(b + 1) * kSlabWavesPerBlock] - wb[b * kSlabWavesPerBlock];
-          if (uni[b] & 1) uniLowerCols_ += cols;
-          if (uni[b] & 2) uniUpperCols_ += cols;
-        }
-      }
-      for (IterVecs* v : {&vecs_, &vecsCol_, &vecsAty_}) {
-        v->colBlockUni = colBlockUni_.get(); v->colBlockBounds = colBlockBounds_.get(); v->lowerUniform = allLower ? 1 : 0;
-      }
+      refreshBlockBounds();
     }
     if (persistent_) gridBar_.alloc(smallBarWords(smallGrid_));
     // Netlib-class LPs (at most 64 workgroups): the check iteration as one launch too (PDLP_MI355X_CHECK_SMALL=0: ten launches)
@@ -709,6 +680,81 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   if (useGraph_ && !persistent_ && (!sharded_ || meshMode_)) captureGraph();
   PDLP_HIP(hipStreamSynchronize(stream_));
   setupSeconds_ = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// Bounds that all columns of a block of the fused launch share -> colBlockUni_ / colBlockBounds_, the three IterVecs and
+// the counts behind bench.py's needed bytes.  At set-up, and again whenever an update has changed a bound.
+bool Solver::refreshBlockBounds() {
+  const MatView at = dAt_.view();
+  launchBlockBounds(lower_.get(), upper_.get(), at.slab.waveBeg, at.slab.nBlocks, colBlockUni_.get(), colBlockBounds_.get(), stream_);
+  std::vector<int32_t> uni((size_t)at.slab.nBlocks);
+  std::vector<double> bnd((size_t)at.slab.nBlocks * 2);
+  colBlockUni_.download(uni.data(), uni.size(), stream_);
+  colBlockBounds_.download(bnd.data(), bnd.size(), stream_);
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  bool allLower = true;  // (bit patterns: the kernel's ULO instantiation takes ONE scalar for all columns)
+  for (size_t b = 0; b < uni.size(); ++b) allLower = allLower && (uni[b] & 1) && memcmp(&bnd[2 * b], &bnd[0], sizeof(double)) == 0;
+  {  // (for bench.py's needed bytes: how many columns' lower / upper bounds the fused launch does not load)
+    std::vector<int32_t> wb((size_t)at.slab.nBlocks * kSlabWavesPerBlock + 1);
+    PDLP_HIP(hipMemcpyAsync(wb.data(), at.slab.waveBeg, wb.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    PDLP_HIP(hipStreamSynchronize(stream_));
+    uniLowerCols_ = uniUpperCols_ = 0;
+    for (size_t b = 0; b < uni.size(); ++b) {
+      const int64_t cols = wb[(b + 1) * kSlabWavesPerBlock] - wb[b * kSlabWavesPerBlock];
+      if (uni[b] & 1) uniLowerCols_ += cols;
+      if (uni[b] & 2) uniUpperCols_ += cols;
+    }
+  }
+  for (IterVecs* v : {&vecs_, &vecsCol_, &vecsAty_}) {
+    v->colBlockUni = colBlockUni_.get(); v->colBlockBounds = colBlockBounds_.get(); v->lowerUniform = allLower ? 1 : 0;
+  }
+  return allLower;
+}
+
+// Updatable solvers: what pdlp_mi355x_update replays (pdlp_update.hpp).  D: the device-side set-up's result, whose pass
+// factors are already in HBM; nullptr: host set-up, F_ holds them.
+void Solver::keepForUpdates(DeviceProblem* D) {
+  const int32_t n = F_.n, m = F_.m, n0 = F_.n0;
+  if (D) {
+    nPass_ = D->nPass;
+    csPass_ = std::move(D->csPass);
+    rsPass_ = std::move(D->rsPass);
+  } else {
+    nPass_ = F_.nPass;
+    csPass_.alloc(F_.csPass.size());
+    rsPass_.alloc(F_.rsPass.size());
+    csPass_.upload(F_.csPass.data(), F_.csPass.size(), stream_);
+    rsPass_.upload(F_.rsPass.data(), F_.rsPass.size(), stream_);
+  }
+  std::vector<int32_t> slackRow;  // slack column n0 + k belongs to the k-th kRowBound row
+  slackRow.reserve((size_t)(n - n0));
+  for (int32_t i = 0; i < m; ++i)
+    if (F_.rowKind[i] == kRowBound) slackRow.push_back(i);
+  if ((int32_t)slackRow.size() != n - n0) throw std::runtime_error("pdlp_mi355x: slack columns and ranged rows differ in number");
+  rowKindDev_.alloc((size_t)m); rowNewIdxDev_.alloc((size_t)m); slackRowDev_.alloc(slackRow.size());
+  rowKindDev_.upload(F_.rowKind.data(), (size_t)m, stream_);
+  rowNewIdxDev_.upload(F_.rowNewIdx.data(), (size_t)m, stream_);
+  slackRowDev_.upload(slackRow.data(), slackRow.size(), stream_);
+  PDLP_HIP(hipStreamSynchronize(stream_));  // slackRow and F_'s pass vectors are released here
+  F_.csPass = std::vector<double>();
+  F_.rsPass = std::vector<double>();
+}
+
+void Solver::setHotStart(const double* colValue, const double* rowValue, const double* rowDual) {
+  startX_.assign(F_.n, 0.0);
+  startY_.assign(F_.m, 0.0);
+  int32_t j = 0;
+  for (; j < F_.n0; ++j) startX_[j] = colValue[j];
+  for (int32_t i = 0; i < F_.m; ++i) {
+    const double mu = F_.rowKind[i] == kRowLeq ? -1.0 : 1.0;
+    startY_[F_.rowNewIdx[i]] = F_.sense * mu * rowDual[i];
+    if (F_.rowKind[i] == kRowBound) startX_[j++] = rowValue[i];
+  }
+  if (F_.scaled) {
+    for (int32_t k = 0; k < F_.n; ++k) startX_[k] *= F_.colScale[k];
+    for (int32_t k = 0; k < F_.m; ++k) startY_[k] *= F_.rowScale[k];
+  }
+  hasStart_ = true;
 }
 
 void Solver::release() noexcept {
@@ -2090,6 +2136,18 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     } else {
       put(0, -1.0);
     }
+  } else if (name == "update_seconds") {  // the parts of the last pdlp_mi355x_update: upload + validation, replay kernels, norms +
+    // sums, per-block bounds, graph capture, reset; [6] = the whole update (= setup_seconds of the run that follows)
+    for (int k = 0; k < 6; ++k) put(k, updSeconds_[k]);
+    put(6, setupSeconds_);
+  } else if (name == "update_state") {  // [0] bytes of HBM an updatable solver keeps besides a plain one's (pass factors, row
+    // bookkeeping, staging of the caller's arrays once an update has run), [1] pass count, [2] IterVecs::lowerUniform,
+    // [3] 1 = a captured trial graph exists
+    put(0, (double)(sizeof(double) * (csPass_.size() + rsPass_.size() + updIn_.size()) +
+                    sizeof(int32_t) * (rowKindDev_.size() + rowNewIdxDev_.size() + slackRowDev_.size() + updBad_.size())));
+    put(1, (double)nPass_);
+    put(2, (double)vecs_.lowerUniform);
+    put(3, graphExec_ ? 1.0 : 0.0);
   } else if (name == "trial_launches") {  // kernels per trial step of the hot loop (2 = fused decision + primal step)
     // mesh: 9 with single-block wait kernels, 7 with consumers that wait themselves, 5 with an exchange per launch
     // (fusedWait 0 / 1 / 2)

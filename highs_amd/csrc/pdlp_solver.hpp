@@ -110,6 +110,8 @@ class SolverBase {
   virtual void setVector(const std::string& name, const double* host, int64_t len) = 0;
   virtual void stage(const std::string& name, double* out, int32_t cap) = 0;
   virtual double timeKernel(const std::string& name, int32_t reps) = 0;
+  // pdlp_mi355x_update; validates before it changes anything.  Only the cuPDLP-C path takes updates.
+  virtual void update(const pdlp_update_t& u);
 };
 
 class Solver : public SolverBase {
@@ -126,6 +128,7 @@ class Solver : public SolverBase {
   void setVector(const std::string& name, const double* host, int64_t len) override;
   void stage(const std::string& name, double* out, int32_t cap) override;
   double timeKernel(const std::string& name, int32_t reps) override;
+  void update(const pdlp_update_t& u) override;  // pdlp_update.cpp
 
  private:
   // setup
@@ -139,6 +142,9 @@ class Solver : public SolverBase {
   void initStepSizes();
   void initVariables();
   void applyHotStart();
+  void setHotStart(const double* colValue, const double* rowValue, const double* rowDual);  // -> startX_, startY_ (formulated, scaled)
+  void keepForUpdates(DeviceProblem* D);  // updatable solvers: the passes and the row bookkeeping into HBM
+  bool refreshBlockBounds();              // fused slab trial: colBlockUni_ / colBlockBounds_ from lower_ / upper_; returns allLower
   // hot loop
   void enqueueTrial();
   void enqueueBatch(int32_t todo);  // trials up to the next halt: one persistent launch / the captured graph / single trials
@@ -228,6 +234,14 @@ class Solver : public SolverBase {
   DeviceArray<int32_t> colBlockUni_;     // IterVecs::colBlockUni / colBlockBounds (fused slab launch)
   DeviceArray<double> colBlockBounds_;
   int64_t uniLowerCols_ = 0, uniUpperCols_ = 0;  // columns covered by a block-wide lower / upper bound (stage "uniform_bound_columns")
+  // Updatable solvers (pdlp_params_t.updatable, pdlp_update.hpp): the scale factors of every pass (pass-major), the kind
+  // and permuted index of every original row, the row behind every slack column; staging for the caller's arrays
+  // (allocated by the first update).  updSeconds_: the parts of the last update (stage "update_seconds").
+  bool updatable_ = false;
+  int32_t nPass_ = 0;
+  DeviceArray<double> csPass_, rsPass_, updIn_;
+  DeviceArray<int32_t> rowKindDev_, rowNewIdxDev_, slackRowDev_, updBad_;
+  double updSeconds_[6] = {0, 0, 0, 0, 0, 0};  // upload + validation, kernels, norms + sums, block bounds, graph capture, reset
   int32_t barrierFallbacks_ = 0, smallLaunches_ = 0;
   unsigned long long smallSeq_ = 0;  // persistent launches since gridBar_ was zeroed (their roll call counts cumulatively)
   // (barrier rounds of the contexts of one device: ordered on the DEVICE by an event chain, see pdlp_solver.cpp)

@@ -1,0 +1,139 @@
+// pdlp_update.hip — the device side of pdlp_mi355x_update (see pdlp_update.hpp): new costs, bounds and right-hand sides
+// are written in formulated order and taken through the kept scaling passes, in order, with the same single divisions and
+// multiplications as k_apply_cols / k_apply_rows (pdlp_setup.hip) and applyScaling (pdlp_host.cpp).  No reductions, no
+// float atomics; -ffp-contract=off like every other unit, so host and device agree bit for bit.
+//
+// Both replay kernels are pure streams: 8 (P + 6) bytes per column, 8 (P + 3) + 8 per row, every byte touched once —
+// non-temporal loads and stores.  The pass factors are stored pass-major, so each pass's read is unit-stride across the
+// wave; a thread's P loads are independent of each other and of the branch on the column's origin, and are issued first.
+#include "pdlp_update.hpp"
+
+#include "pdlp_device.hpp"
+#include "pdlp_devfn.hpp"
+
+namespace pdlp {
+
+namespace {
+
+constexpr int kT = 256;
+constexpr int kSetupPasses = 11;  // Ruiz x 10 + Pock-Chambolle: the count every scaled cuPDLP-C form has
+inline int gridFor(int64_t n) { return (int)((n + kT - 1) / kT); }
+
+__device__ __forceinline__ double infLo(double v) { return v < -1e20 ? -INFINITY : v; }
+__device__ __forceinline__ double infUp(double v) { return v > 1e20 ? INFINITY : v; }
+
+__global__ __launch_bounds__(kT) void k_update_validate(const double* __restrict__ rowLower, const double* __restrict__ rowUpper,
+                                                        const int32_t* __restrict__ rowKind, int m, int32_t* bad) {
+  const int i = blockIdx.x * kT + threadIdx.x;
+  if (i >= m) return;
+  if (rowKindOf(ldStream(rowLower + i), ldStream(rowUpper + i)) != ldStream(rowKind + i)) atomicMin(bad, i);
+}
+
+// NP > 0: the pass count is NP (all factor loads in flight before the first division); NP = 0: nPass passes, any count
+template <int NP>
+__global__ __launch_bounds__(kT) void k_update_cols(int mask, const double* __restrict__ colCost, const double* __restrict__ colLower,
+                                                    const double* __restrict__ colUpper, const double* __restrict__ rowLower,
+                                                    const double* __restrict__ rowUpper, const int32_t* __restrict__ slackRow,
+                                                    double sense, int n0, int n, const double* __restrict__ csPass, int nPass,
+                                                    double* cost, double* lower, double* upper) {
+  const int j = blockIdx.x * kT + threadIdx.x;
+  if (j >= n) return;
+  double f[NP > 0 ? NP : 1];
+  if (NP > 0) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) f[p] = ldStream(csPass + (size_t)p * (size_t)n + j);
+  }
+  bool dc = false, dl = false, du = false;
+  double c = 0.0, lo = 0.0, up = 0.0;
+  if (j < n0) {
+    dc = mask & kUpdCost; dl = mask & kUpdColLower; du = mask & kUpdColUpper;
+    if (dc) c = ldStream(colCost + j) * sense;
+    if (dl) lo = infLo(ldStream(colLower + j));
+    if (du) up = infUp(ldStream(colUpper + j));
+  } else if (mask & kUpdRows) {  // slack column of a ranged / free row: its bounds are the row's
+    dl = du = true;
+    const int r = slackRow[j - n0];
+    lo = infLo(rowLower[r]);
+    up = infUp(rowUpper[r]);
+  }
+  if (NP > 0) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) { c /= f[p]; lo *= f[p]; up *= f[p]; }
+  } else {
+    for (int p = 0; p < nPass; ++p) {
+      const double cs = ldStream(csPass + (size_t)p * (size_t)n + j);
+      c /= cs; lo *= cs; up *= cs;
+    }
+  }
+  if (dc) stStream(cost + j, c);
+  if (dl) stStream(lower + j, lo);
+  if (du) stStream(upper + j, up);
+}
+
+template <int NP>
+__global__ __launch_bounds__(kT) void k_update_rows(const double* __restrict__ rowLower, const double* __restrict__ rowUpper,
+                                                    const int32_t* __restrict__ rowKind, const int32_t* __restrict__ rowNewIdx, int m,
+                                                    const double* __restrict__ rsPass, int nPass, double* rhs) {
+  const int i = blockIdx.x * kT + threadIdx.x;
+  if (i >= m) return;
+  const int ni = ldStream(rowNewIdx + i);  // (0 <= ni < m: a permutation written by formulate)
+  const int k = ldStream(rowKind + i);
+  const double rl = ldStream(rowLower + i), ru = ldStream(rowUpper + i);
+  double f[NP > 0 ? NP : 1];
+  if (NP > 0) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) f[p] = ldStream(rsPass + (size_t)p * (size_t)m + ni);
+  }
+  double r;
+  if (k == kRowEq) r = rl;
+  else if (k == kRowBound) r = 0.0;
+  else if (k == kRowLeq) r = -ru;
+  else r = rl;
+  if (NP > 0) {
+#pragma unroll
+    for (int p = 0; p < NP; ++p) r /= f[p];
+  } else {
+    for (int p = 0; p < nPass; ++p) r /= ldStream(rsPass + (size_t)p * (size_t)m + ni);
+  }
+  stStream(rhs + ni, r);
+}
+
+}  // namespace
+
+void launchUpdateValidate(const double* rowLower, const double* rowUpper, const int32_t* rowKind, int32_t m, int32_t* bad,
+                          hipStream_t s) {
+  if (m <= 0) return;
+  hipLaunchKernelGGL(k_update_validate, dim3(gridFor(m)), dim3(kT), 0, s, rowLower, rowUpper, rowKind, m, bad);
+  PDLP_HIP(hipGetLastError());
+}
+
+void launchUpdateCols(int32_t mask, const double* colCost, const double* colLower, const double* colUpper,
+                      const double* rowLower, const double* rowUpper, const int32_t* slackRow, double sense, int32_t n0,
+                      int32_t n, const double* csPass, int32_t nPass, double* cost, double* lower, double* upper, hipStream_t s) {
+  // only the columns that can change: the originals, and the slack columns when row bounds were given
+  const int32_t nDo = (mask & kUpdRows) ? n : ((mask & (kUpdCost | kUpdColLower | kUpdColUpper)) ? n0 : 0);
+  if (nDo <= 0) return;
+  // (the grid covers nDo columns; a thread beyond them in the last block finds nothing to write)
+  const dim3 grid(gridFor(nDo));
+  if (nPass == kSetupPasses)
+    hipLaunchKernelGGL(k_update_cols<kSetupPasses>, grid, dim3(kT), 0, s, mask, colCost, colLower, colUpper, rowLower, rowUpper,
+                       slackRow, sense, n0, n, csPass, nPass, cost, lower, upper);
+  else
+    hipLaunchKernelGGL(k_update_cols<0>, grid, dim3(kT), 0, s, mask, colCost, colLower, colUpper, rowLower, rowUpper, slackRow,
+                       sense, n0, n, csPass, nPass, cost, lower, upper);
+  PDLP_HIP(hipGetLastError());
+}
+
+void launchUpdateRows(const double* rowLower, const double* rowUpper, const int32_t* rowKind, const int32_t* rowNewIdx,
+                      int32_t m, const double* rsPass, int32_t nPass, double* rhs, hipStream_t s) {
+  if (m <= 0) return;
+  if (nPass == kSetupPasses)
+    hipLaunchKernelGGL(k_update_rows<kSetupPasses>, dim3(gridFor(m)), dim3(kT), 0, s, rowLower, rowUpper, rowKind, rowNewIdx, m,
+                       rsPass, nPass, rhs);
+  else
+    hipLaunchKernelGGL(k_update_rows<0>, dim3(gridFor(m)), dim3(kT), 0, s, rowLower, rowUpper, rowKind, rowNewIdx, m, rsPass,
+                       nPass, rhs);
+  PDLP_HIP(hipGetLastError());
+}
+
+}  // namespace pdlp

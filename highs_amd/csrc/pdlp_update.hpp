@@ -1,0 +1,53 @@
+// pdlp_update.hpp — re-solving a held problem after its costs, bounds or right-hand side changed (pdlp_mi355x_update).
+//
+// In the cuPDLP-C scheme the scale factors come from the matrix alone (pdlp_host.cpp scale(): Ruiz x 10 + Pock-Chambolle
+// look only at the matrix values); cost, bounds and rhs are merely carried along, one pass at a time (applyScaling:
+// cost /= cs, lower *= cs, upper *= cs, rhs /= rs).  Row order, slack columns and the sign flip of <= rows depend only on
+// each row's KIND.  So with the kinds unchanged and the factors of every pass kept, new data are brought to exactly the
+// bits a fresh create() on the modified problem has by REPLAYING the passes in order — dividing once by the accumulated
+// colScale does not give the same bits (tests/test_update_host.py shows a case).  The replay runs on the device
+// (pdlp_update.hip); hostReplayUpdate restates it for the CPU tests.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <vector>
+
+#include "pdlp_host.hpp"
+
+namespace pdlp {
+
+// Which parts of the standard form an update touches.
+enum : int32_t { kUpdCost = 1, kUpdColLower = 2, kUpdColUpper = 4, kUpdRows = 8 };
+inline int32_t updateMask(const pdlp_update_t& u) {
+  return (u.col_cost ? kUpdCost : 0) | (u.col_lower ? kUpdColLower : 0) | (u.col_upper ? kUpdColUpper : 0) |
+         (u.row_lower && u.row_upper ? kUpdRows : 0);
+}
+
+// What can be checked without the problem: row bounds come in pairs, a start is whole or absent.  Throws.
+void checkUpdateShape(const pdlp_update_t& u);
+// The smallest row whose kind under the new bounds differs from rowKind, or m.
+int32_t firstKindChange(const int32_t* rowKind, int32_t m, const double* rowLower, const double* rowUpper);
+// The refusal for such a row: names the row and both kinds.
+[[noreturn]] void throwKindChange(int32_t row, int32_t was, int32_t now);
+
+// Host restatement of the device replay on a form that kept its passes (StandardForm::keepPasses): F.cost / lower / upper
+// / rhs, normCost / normRhs and offset become those of formulate + scale on the modified problem.  Validates first; throws
+// without touching F.
+void hostReplayUpdate(const pdlp_update_t& u, StandardForm& F);
+
+// ---- device (pdlp_update.hip) --------------------------------------------------------------------------------------
+// bad[0] = min(bad[0], smallest row whose kind changes); the caller sets bad[0] = m first
+void launchUpdateValidate(const double* rowLower, const double* rowUpper, const int32_t* rowKind, int32_t m, int32_t* bad,
+                          hipStream_t s);
+// Columns j < n of the formulated problem.  Original columns (j < n0) take colCost[j] * sense, colLower[j], colUpper[j]
+// (each only where mask says its array was given; beyond +-1e20 is infinite); slack column n0 + k takes the bounds of
+// row slackRow[k] when mask has kUpdRows.  Then the nPass passes csPass[p * n + j] are replayed in order.
+void launchUpdateCols(int32_t mask, const double* colCost, const double* colLower, const double* colUpper,
+                      const double* rowLower, const double* rowUpper, const int32_t* slackRow, double sense, int32_t n0,
+                      int32_t n, const double* csPass, int32_t nPass, double* cost, double* lower, double* upper, hipStream_t s);
+// Original rows i < m: rhs[rowNewIdx[i]] by kind, then rhs /= rsPass[p * m + rowNewIdx[i]] in order.
+void launchUpdateRows(const double* rowLower, const double* rowUpper, const int32_t* rowKind, const int32_t* rowNewIdx,
+                      int32_t m, const double* rsPass, int32_t nPass, double* rhs, hipStream_t s);
+
+}  // namespace pdlp

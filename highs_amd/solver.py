@@ -43,6 +43,7 @@ EXPORTS = [
     "pdlp_mi355x_host_task_plan", "pdlp_mi355x_free_task_plan",
     "pdlp_mi355x_read_mps", "pdlp_mi355x_read_mps_timed", "pdlp_mi355x_free_mps_model",
     "pdlp_mi355x_create_wide", "pdlp_mi355x_solve_wide",
+    "pdlp_mi355x_update", "pdlp_mi355x_host_prepare_updated",
 ]
 
 
@@ -87,6 +88,9 @@ def lib():
         pPrep = C.POINTER(abi.PdlpPrepared)
         L.pdlp_mi355x_host_prepare.argtypes = [pP, pO, pPrep]
         L.pdlp_mi355x_free_prepared.argtypes = [pPrep]
+        pU = C.POINTER(abi.PdlpUpdate)
+        L.pdlp_mi355x_update.argtypes = [H, pU]
+        L.pdlp_mi355x_host_prepare_updated.argtypes = [pP, pO, pU, pPrep]
         L.pdlp_mi355x_free_prepared.restype = None
         L.pdlp_mi355x_row_partition.argtypes = [pPrep, C.c_int32, abi.c_i32p]
         pSlab = C.POINTER(abi.PdlpSlabLayout)
@@ -282,6 +286,7 @@ class DeviceSolver:
     def __init__(self, lp=None, problem_struct=None, params=None, rank=0, world=1, unique_id=None, **options):
         self.params = params or abi.default_params(**options)
         self._keep = None
+        self.lp = lp
         if problem_struct is None:
             self._keep = abi.ProblemHandle(lp)
             problem_struct = self._keep.struct
@@ -319,6 +324,40 @@ class DeviceSolver:
 
     def reset(self):
         _check(lib().pdlp_mi355x_reset(self.h), "reset")
+
+    def update(self, col_cost=None, col_lower=None, col_upper=None, row_lower=None, row_upper=None, offset=None, start=None):
+        """pdlp_mi355x_update: new costs / column bounds / row bounds / offset for the held problem (None = unchanged) and
+        the start of the next run (`start`: dict with col_value, row_value, row_dual, or None = cold start).  Needs a
+        solver created with updatable=True; raises with the library's message when the update is refused (the solver is
+        then unchanged).  When the solver was built from a HighsLp, self.lp follows (a copy), so solve() reports the KKT
+        measures of the problem actually solved."""
+        U = abi.UpdateHandle(col_cost, col_lower, col_upper, row_lower, row_upper, offset, start)
+        _check(lib().pdlp_mi355x_update(self.h, C.byref(U.struct)), "pdlp_mi355x_update")
+        if self.lp is not None:
+            import copy
+            lp = copy.copy(self.lp)
+            for name, a in (("col_cost", col_cost), ("col_lower", col_lower), ("col_upper", col_upper),
+                            ("row_lower", row_lower), ("row_upper", row_upper)):
+                if a is not None:
+                    setattr(lp, name, np.array(a, dtype=np.float64))
+            if offset is not None:
+                lp.offset = float(offset)
+            self.lp = lp
+
+    def solve(self):
+        """pdlp_mi355x_run on the held problem, returned as solveLpCupdlp returns it: a family of LPs over one matrix
+        is `create once; for each: update, solve`."""
+        if self.lp is None:
+            raise ValueError("solve() needs a solver built from a HighsLp (use run() with a problem struct)")
+        lp = self.lp
+        R = abi.ResultHandle(lp.num_col, lp.num_row)
+        rc = lib().pdlp_mi355x_run(self.h, C.byref(R.struct))
+        ms = model_status_from_term(R.term_code, R.num_iter, self.params.iter_limit, rc)
+        sol = HighsSolution(R.col_value, R.col_dual, R.row_value, R.row_dual, bool(R.value_valid), bool(R.dual_valid))
+        info = kkt_measures(lp, sol.col_value, sol.col_dual, sol.row_value, sol.row_dual) if rc == 0 else {}
+        info["pdlp_iteration_count"] = int(R.num_iter)
+        status = kError if rc != 0 else (kOk if ms == kOptimal or ms == kUnboundedOrInfeasible else kWarning)
+        return PdlpOutcome(status, ms, sol, int(R.num_iter), info, R)
 
     def iterate(self, n_iters):
         st = abi.PdlpIterStats()
@@ -378,14 +417,20 @@ class SyntheticProblem:
 class Prepared:
     """Host-side standard form built by the PRODUCT library (pdlp_mi355x_host_prepare); numpy copies."""
 
-    def __init__(self, lp=None, params=None, problem_struct=None, slab_long_limit=256, **options):
+    def __init__(self, lp=None, params=None, problem_struct=None, slab_long_limit=256, update=None, **options):
+        """update: an abi.UpdateHandle — the form then comes from pdlp_mi355x_host_prepare_updated (the host twin of
+        pdlp_mi355x_update: prepare, keep the scaling passes, replay the update)."""
         params = params or abi.default_params(**options)
         keep = None
         if problem_struct is None:
             keep = abi.ProblemHandle(lp)
             problem_struct = keep.struct
         F = abi.PdlpPrepared()
-        _check(lib().pdlp_mi355x_host_prepare(C.byref(problem_struct), C.byref(params), C.byref(F)), "host_prepare")
+        if update is None:
+            _check(lib().pdlp_mi355x_host_prepare(C.byref(problem_struct), C.byref(params), C.byref(F)), "host_prepare")
+        else:
+            _check(lib().pdlp_mi355x_host_prepare_updated(C.byref(problem_struct), C.byref(params), C.byref(update.struct), C.byref(F)),
+                   "host_prepare_updated")
         n, m, nnz = F.n, F.m, F.nnz
         self.n, self.m, self.n_eqs, self.n_orig, self.nnz = n, m, F.n_eqs, F.n_orig, nnz
         g = lambda p, k, dt: np.ctypeslib.as_array(p, shape=(max(k, 1),))[:k].astype(dt).copy()

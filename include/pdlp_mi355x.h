@@ -127,7 +127,8 @@ typedef struct pdlp_params {
                                  (default 1); G > 1 = the constraint matrix is row-block sharded over the
                                  devices device, device+1, ... device+G-1 of THIS process (one host thread
                                  per device, direct xGMI exchange through peer access) */
-  int32_t reserved2;
+  int32_t updatable;          /* pdlp_mi355x_create: non-zero = the solver takes pdlp_mi355x_update (it then keeps the scale
+                                 factors of every scaling pass and the row kinds in HBM); 0 = nothing is kept */
   /* --- log sink (HiGHS: highsLogUser).  NULL = stdout, as the reference's cuPDLP-C prints --- */
   void (*log_callback)(void* ctx, int level, const char* text); /* level 1 = summary, 2 = verbose */
   void* log_ctx;
@@ -177,6 +178,32 @@ int pdlp_mi355x_create(const pdlp_problem_t* P, const pdlp_params_t* opt,
                        pdlp_mi355x_solver_t** out);
 int pdlp_mi355x_run(pdlp_mi355x_solver_t* s, pdlp_result_t* R);
 void pdlp_mi355x_destroy(pdlp_mi355x_solver_t* s);
+
+/* Re-solve a held LP / QP after its costs, column bounds, row bounds or offset changed — the matrix, the Hessian,
+ * the sense, the sizes and the options stay.  Everything create() derives from the MATRIX (scale factors, row order,
+ * slack columns, both orientations, slab layouts, tuning, the captured trial graph) is kept; the new data are brought
+ * into the scaled standard form on the device by replaying the scale factors of every scaling pass in order, which
+ * gives exactly the bits a fresh pdlp_mi355x_create on the modified problem has.
+ *   * Only for solvers created with pdlp_params_t.updatable != 0, algorithm = 0, not sharded.
+ *   * Values are taken as create takes them (|v| >= 1e20 is infinite; no check for NaN or crossed bounds).
+ *   * Every row must keep its KIND (equality / >= / <= / ranged-or-free): the kind decides the row order, the slack
+ *     columns and the sign of the row.  A change is refused; the message names the smallest such row and both kinds.
+ *   * Everything is validated before anything is changed: after a non-zero return the solver is as it was.
+ *   * Afterwards the solver is in the state of a fresh create on the modified problem; pdlp_mi355x_run may follow, and
+ *     its pdlp_result_t.setup_seconds is the time the update took. */
+typedef struct pdlp_update {
+  const double* col_cost;   /* [num_col]  NULL = unchanged; original space, original sense */
+  const double* col_lower;  /* [num_col]  NULL = unchanged */
+  const double* col_upper;  /* [num_col]  NULL = unchanged */
+  const double* row_lower;  /* [num_row]  NULL = unchanged; lower and upper are given together or not at all */
+  const double* row_upper;
+  double offset; int32_t has_offset; /* offset is taken only when has_offset != 0 */
+  int32_t reserved;
+  /* start of the next run: all three NULL = cold start (as create without a hot start);
+     all three given = hot start with the meaning of pdlp_problem_t.start_* when both valid flags are set */
+  const double* start_col_value; const double* start_row_value; const double* start_row_dual;
+} pdlp_update_t;
+int pdlp_mi355x_update(pdlp_mi355x_solver_t* s, const pdlp_update_t* u);
 
 /* The same two entries with 64-bit column starts (HighsInt = int64_t builds, or any caller whose matrix
  * starts are 64-bit): a_start64[num_col+1] replaces P->a_start, which is ignored and may be NULL; every
@@ -298,6 +325,11 @@ typedef struct pdlp_prepared {
 } pdlp_prepared_t;
 int pdlp_mi355x_host_prepare(const pdlp_problem_t* P, const pdlp_params_t* opt,
                              pdlp_prepared_t* out);
+/* Host restatement of pdlp_mi355x_update for the CPU tests: prepares P as host_prepare does, keeping the scale factors of
+ * every pass, applies u by the same replay (same validation, same messages: opt->updatable = 0 and algorithm = 1 are
+ * refused here too) and returns the standard form — which must equal host_prepare of the modified problem bit for bit. */
+int pdlp_mi355x_host_prepare_updated(const pdlp_problem_t* P, const pdlp_params_t* opt, const pdlp_update_t* u,
+                                     pdlp_prepared_t* out);
 void pdlp_mi355x_free_prepared(pdlp_prepared_t* out);
 /* Row-block partition used by create_sharded: offsets[world+1]. */
 int pdlp_mi355x_row_partition(const pdlp_prepared_t* prep, int32_t world,
@@ -393,7 +425,8 @@ int pdlp_mi355x_read_mps(const char* path, int32_t num_threads, pdlp_mps_model_t
 int pdlp_mi355x_read_mps_timed(const char* path, int32_t num_threads, double time_limit, pdlp_mps_model_t* out);
 void pdlp_mi355x_free_mps_model(pdlp_mps_model_t* out);
 
-/* sizeof() of the ABI structs: 0 problem, 1 params, 2 result, 3 iter_stats, 4 prepared, 5 slab_layout, 6 mps_model */
+/* sizeof() of the ABI structs: 0 problem, 1 params, 2 result, 3 iter_stats, 4 prepared, 5 slab_layout, 6 mps_model,
+ * 7 task_plan, 8 update; -1 for any other index */
 int64_t pdlp_mi355x_sizeof(int32_t which);
 
 const char* pdlp_mi355x_last_error(void);
