@@ -106,6 +106,9 @@ class PdlpResult(C.Structure):
     ]
 
 
+UPDATABLE_DATA, UPDATABLE_MATRIX = 1, 2  # pdlp_params_t.updatable bits
+
+
 class PdlpUpdate(C.Structure):
     """pdlp_update_t (include/pdlp_mi355x.h): new data for a held solver; NULL = unchanged."""
     _fields_ = [
@@ -217,7 +220,10 @@ def default_params(**kw):
         elif k in ("pdlp_scaling_mode", "pdlp_ruiz_iterations", "pdlp_step_size_strategy"):
             setattr(p, k[5:], int(v))
         elif k == "updatable":
-            p.updatable = 1 if v else 0
+            # "matrix", or an int with UPDATABLE_MATRIX set: PDLP_UPDATABLE_DATA | PDLP_UPDATABLE_MATRIX (pdlp_mi355x_update_matrix
+            # too); any other truthy value: DATA
+            matrix = v == "matrix" if isinstance(v, str) else (not isinstance(v, bool) and isinstance(v, int) and v & UPDATABLE_MATRIX)
+            p.updatable = UPDATABLE_DATA | UPDATABLE_MATRIX if matrix else (UPDATABLE_DATA if v else 0)
         elif k == "device_reduction_order":
             # ORACLE ONLY: sum the reductions in the HIP kernels' order (oracle/pdlp_oracle.c, GPU-ORDER)
             p.reserved[0] = 1 if v else 0

@@ -182,6 +182,13 @@ int pdlp_mi355x_update(pdlp_mi355x_solver_t* s, const pdlp_update_t* u) {
   });
 }
 
+int pdlp_mi355x_update_matrix(pdlp_mi355x_solver_t* s, const double* a_value, int64_t num_nz, const pdlp_update_t* u) {
+  return guarded([&] {
+    if (!s || !s->impl) throw std::runtime_error("pdlp_mi355x_update_matrix: null solver");
+    s->impl->updateMatrix(a_value, num_nz, u);
+  });
+}
+
 void pdlp_mi355x_destroy(pdlp_mi355x_solver_t* s) {
   if (!s) return;
   try {
@@ -329,7 +336,8 @@ int pdlp_mi355x_time_kernel(pdlp_mi355x_solver_t* s, const char* kernel, int32_t
 
 namespace {
 // host_prepare, optionally followed by the host restatement of an update (u != nullptr)
-void hostPrepare(const pdlp_problem_t* P, const pdlp_params_t* opt, const pdlp_update_t* u, pdlp_prepared_t* out) {
+void hostPrepare(const pdlp_problem_t* P, const pdlp_params_t* opt, const pdlp_update_t* u, pdlp_prepared_t* out,
+                 const double* aValue = nullptr, const pdlp_update_t* uMatrix = nullptr) {
   memset(out, 0, sizeof(*out));
   pdlp::StandardForm F;
   if (opt->algorithm == 1) {  // HiPDLP form: rhs = row lower bounds (row upper bounds are not exported)
@@ -338,8 +346,11 @@ void hostPrepare(const pdlp_problem_t* P, const pdlp_params_t* opt, const pdlp_u
       pdlp::scaleHipdlp(F, opt->scaling_mode & 1, opt->scaling_mode & 4, opt->scaling_mode & 2, opt->ruiz_iterations);
   } else {
     pdlp::formulate(*P, F);
-    F.keepPasses = u != nullptr;
-    if (!(opt->features_off & PDLP_FEATURE_SCALING_OFF)) pdlp::scale(F);
+    const bool doScale = !(opt->features_off & PDLP_FEATURE_SCALING_OFF);
+    F.keepPasses = u != nullptr || aValue != nullptr;
+    if (aValue) pdlp::keepUnscaled(F);
+    if (doScale) pdlp::scale(F);
+    if (aValue) pdlp::hostReplayMatrixUpdate(*P, aValue, uMatrix, doScale, F);
     if (u) pdlp::hostReplayUpdate(*u, F);
   }
   pdlp::finalize(F);
@@ -373,6 +384,31 @@ int pdlp_mi355x_host_prepare_updated(const pdlp_problem_t* P, const pdlp_params_
       throw std::runtime_error("pdlp_mi355x_update: the solver was not created for updates (pdlp_params_t.updatable = 0)");
     hostPrepare(P, opt, u, out);
   });
+}
+
+// Test hook, not part of the public header: the entry below with a pdlp_mi355x_update (u_then, may be NULL) applied to
+// the result on the same form — what shows that a data update after a matrix update replays the NEW factors.
+int pdlp_mi355x_host_prepare_updated_matrix_then(const pdlp_problem_t* P, const pdlp_params_t* opt, const double* a_value,
+                                                 const pdlp_update_t* u, const pdlp_update_t* u_then, pdlp_prepared_t* out) {
+  return guarded([&] {
+    if (!P || !opt || !out) throw std::runtime_error("null argument");
+    // the refusals of pdlp_mi355x_update_matrix that depend on how the solver was created
+    if (opt->algorithm == 1)
+      throw std::runtime_error("pdlp_mi355x_update_matrix: HiPDLP solvers (algorithm = 1) do not take updates");
+    if (!(opt->updatable & PDLP_UPDATABLE_MATRIX))
+      throw std::runtime_error("pdlp_mi355x_update_matrix: the solver was not created for matrix updates (pdlp_params_t.updatable "
+                               "lacks PDLP_UPDATABLE_MATRIX)");
+    if (pdlp::hessianHasOffDiagonal(*P))
+      throw std::runtime_error("pdlp_mi355x_update_matrix: QPs whose Hessian has off-diagonal entries do not take matrix updates "
+                               "(the scaled copy of the Hessian follows the column factors; left for a later change)");
+    if (!a_value) throw std::runtime_error("pdlp_mi355x_update_matrix: a_value is NULL");
+    hostPrepare(P, opt, u_then, out, a_value, u);
+  });
+}
+
+int pdlp_mi355x_host_prepare_updated_matrix(const pdlp_problem_t* P, const pdlp_params_t* opt, const double* a_value,
+                                            const pdlp_update_t* u, pdlp_prepared_t* out) {
+  return pdlp_mi355x_host_prepare_updated_matrix_then(P, opt, a_value, u, nullptr, out);
 }
 
 void pdlp_mi355x_free_prepared(pdlp_prepared_t* o) {

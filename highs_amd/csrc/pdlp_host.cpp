@@ -241,18 +241,17 @@ void formulate(const pdlp_problem_t& P, StandardForm& F) {
       const int32_t r = P.a_index[p];
       if (r < 0 || r >= m) throw std::runtime_error("row index out of range");
       const int32_t kind = F.rowKind[r];
-      if (kind == kRowEq || kind == kRowBound) { A.idx[k] = F.rowNewIdx[r]; A.val[k] = P.a_value[p]; ++k; }
+      if (kind == kRowEq || kind == kRowBound) A.idx[k++] = F.rowNewIdx[r];
     }
     for (int32_t p = b; p < e; ++p) {
-      const int32_t r = P.a_index[p];
-      const int32_t kind = F.rowKind[r];
-      if (kind == kRowLeq) { A.idx[k] = F.rowNewIdx[r]; A.val[k] = -P.a_value[p]; ++k; }
-      else if (kind == kRowGeq) { A.idx[k] = F.rowNewIdx[r]; A.val[k] = P.a_value[p]; ++k; }
+      const int32_t kind = F.rowKind[P.a_index[p]];
+      if (kind == kRowLeq || kind == kRowGeq) A.idx[k++] = F.rowNewIdx[P.a_index[p]];
     }
   }
   for (int32_t i = 0, j = n0; i < m; ++i)
-    if (F.rowKind[i] == kRowBound) { A.beg[j] = (int32_t)k; A.idx[k] = F.rowNewIdx[i]; A.val[k] = -1.0; ++k; ++j; }
+    if (F.rowKind[i] == kRowBound) { A.beg[j] = (int32_t)k; A.idx[k] = F.rowNewIdx[i]; ++k; ++j; }
   A.beg[F.n] = (int32_t)k;
+  formulateValues(P.a_start, P.a_index, P.a_value, F);
 
   // Termination norms are those of the UNSCALED formulated data (Init_Scaling
   // runs before PDHG_Scale_Data, CupdlpWrapper.cpp:110 vs :153).
@@ -260,6 +259,25 @@ void formulate(const pdlp_problem_t& P, StandardForm& F) {
   F.normRhs = unscaledNormRhs(P.row_lower, P.row_upper, F.rowKind.data(), m);
   F.colScale.assign(F.n, 1.0);
   F.rowScale.assign(m, 1.0);
+}
+
+void formulateValues(const int32_t* aStart, const int32_t* aIndex, const double* aValue, StandardForm& F) {
+  std::vector<double>& val = F.csc.val;
+  int64_t k = 0;
+  for (int32_t j = 0; j < F.n0; ++j) {
+    const int32_t b = aStart[j], e = aStart[j + 1];
+    for (int32_t p = b; p < e; ++p) {
+      const int32_t kind = F.rowKind[aIndex[p]];
+      if (kind == kRowEq || kind == kRowBound) val[k++] = aValue[p];
+    }
+    for (int32_t p = b; p < e; ++p) {
+      const int32_t kind = F.rowKind[aIndex[p]];
+      if (kind == kRowLeq) val[k++] = -aValue[p];
+      else if (kind == kRowGeq) val[k++] = aValue[p];
+    }
+  }
+  for (int32_t i = 0; i < F.m; ++i)
+    if (F.rowKind[i] == kRowBound) val[k++] = -1.0;
 }
 
 double unscaledNormCost(const double* colCost, int32_t n0, double costSense) {

@@ -74,6 +74,8 @@ struct StandardForm {
   bool keepPasses = false;
   int32_t nPass = 0;
   std::vector<double> csPass, rsPass;
+  // Matrix-updatable solvers (pdlp_update.hpp): the unscaled formulated data, taken between formulate() and scale()
+  std::vector<double> cost0, lower0, upper0, rhs0, qdiag0;
   double offset = 0.0, sense = 1.0;
   double normCost = 0.0, normRhs = 0.0;  // of the unscaled formulated data
   double matNormInf = 0.0;               // max |a_ij| of the (scaled) matrix
@@ -90,6 +92,9 @@ void extractDiagonalHessian(const pdlp_problem_t& P, double sense, int32_t n, st
 void extractHessian(const pdlp_problem_t& P, double sense, int32_t n, std::vector<double>& qdiag, Compressed& qoff);
 bool hessianHasOffDiagonal(const pdlp_problem_t& P);
 void formulate(const pdlp_problem_t& P, StandardForm& F);
+// The value part of formulate(): csc.val in the reference's entry order from aValue (the positions of P.a_value), with
+// F.rowKind / F.n0 / F.m as formulate() left them.  formulate() calls it; so does the matrix update (pdlp_update.cpp).
+void formulateValues(const int32_t* aStart, const int32_t* aIndex, const double* aValue, StandardForm& F);
 // ||c||_2 and ||b||_2 of the UNSCALED formulated data, summed left to right as Init_Scaling does (cupdlp_scaling.c:395-425):
 // the costs of the original columns with the sense (slack costs are 0); the right-hand side in the PERMUTED row order,
 // equality-type rows first, then inequalities.  Shared by formulate(), the device-side set-up and the update path.

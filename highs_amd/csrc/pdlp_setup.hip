@@ -88,6 +88,8 @@ __global__ void k_col_setup(const double* __restrict__ c, const double* __restri
 }
 
 // Reference entry order inside a column: equality-type rows first, then inequality rows (LEQ negated).
+// VALS_ONLY (pdlp_mi355x_update_matrix: the pattern was checked and written at set-up): cscVal alone.
+template <bool VALS_ONLY>
 __global__ void k_col_entries(const int32_t* __restrict__ aStart, const int32_t* __restrict__ aIndex,
                               const double* __restrict__ aValue, const int32_t* __restrict__ kind,
                               const int32_t* __restrict__ rowNewIdx, int n0, int m, int32_t* cscIdx, int32_t* cscCol,
@@ -97,16 +99,16 @@ __global__ void k_col_entries(const int32_t* __restrict__ aStart, const int32_t*
     int k = b;
     for (int p = b; p < e; ++p) {
       const int r = aIndex[p];
-      if (r < 0 || r >= m) { *badFlag = 1; continue; }
+      if (r < 0 || r >= m) { if (!VALS_ONLY) *badFlag = 1; continue; }
       const int t = kind[r];
-      if (isEqKind(t)) { cscIdx[k] = rowNewIdx[r]; cscCol[k] = (int)j; cscVal[k] = aValue[p]; ++k; }
+      if (isEqKind(t)) { if (!VALS_ONLY) { cscIdx[k] = rowNewIdx[r]; cscCol[k] = (int)j; } cscVal[k] = aValue[p]; ++k; }
     }
     for (int p = b; p < e; ++p) {
       const int r = aIndex[p];
       if (r < 0 || r >= m) continue;
       const int t = kind[r];
-      if (t == kRowLeq) { cscIdx[k] = rowNewIdx[r]; cscCol[k] = (int)j; cscVal[k] = -aValue[p]; ++k; }
-      else if (t == kRowGeq) { cscIdx[k] = rowNewIdx[r]; cscCol[k] = (int)j; cscVal[k] = aValue[p]; ++k; }
+      if (t == kRowLeq) { if (!VALS_ONLY) { cscIdx[k] = rowNewIdx[r]; cscCol[k] = (int)j; } cscVal[k] = -aValue[p]; ++k; }
+      else if (t == kRowGeq) { if (!VALS_ONLY) { cscIdx[k] = rowNewIdx[r]; cscCol[k] = (int)j; } cscVal[k] = aValue[p]; ++k; }
     }
   }
 }
@@ -345,7 +347,8 @@ T fetchOne(const T* dev, hipStream_t s) {
 // CSR <-> CSC by a stable sort on the minor index: the output majors keep their
 // entries in ascending input-major order (what cupdlp_dcs_transpose produces).
 void transposeOnDevice(const int32_t* majorIn, const int32_t* minorIn, const double* valIn, int64_t nnz,
-                       int32_t nMajorOut, int32_t nMinorOut, hipStream_t s, DeviceCsrData& out) {
+                       int32_t nMajorOut, int32_t nMinorOut, hipStream_t s, DeviceCsrData& out,
+                       DeviceArray<int32_t>* permOut = nullptr /* out slot -> in slot, for those who keep it */) {
   out.nMajor = nMajorOut;
   out.nMinor = nMinorOut;
   out.nnz = nnz;
@@ -366,9 +369,76 @@ void transposeOnDevice(const int32_t* majorIn, const int32_t* minorIn, const dou
   hipLaunchKernelGGL(k_lower_bounds, dim3(gridFor(nMajorOut + 1)), dim3(kT), 0, s,
                      reinterpret_cast<const int32_t*>(keys.get()), nnz, (int64_t)nMajorOut + 1, out.beg.get());
   PDLP_HIP(hipStreamSynchronize(s));
+  if (permOut) *permOut = std::move(perm);
+}
+
+template <typename T>
+void copyOf(DeviceArray<T>& dst, const DeviceArray<T>& src, hipStream_t s) {
+  dst.alloc(src.size());
+  if (src.size()) PDLP_HIP(hipMemcpyAsync(dst.get(), src.get(), sizeof(T) * src.size(), hipMemcpyDeviceToDevice, s));
 }
 
 }  // namespace
+
+void gpuFormulateValues(const int32_t* aStart, const int32_t* aIndex, const double* aValue, const int32_t* rowKind,
+                        const int32_t* rowNewIdx, int32_t n0, int32_t m, int64_t nnz0, int64_t nSlack, double* cscVal,
+                        hipStream_t s) {
+  hipLaunchKernelGGL(k_col_entries<true>, dim3(gridFor(n0)), dim3(kT), 0, s, aStart, aIndex, aValue, rowKind, rowNewIdx, n0, m,
+                     (int32_t*)nullptr, (int32_t*)nullptr, cscVal, (int32_t*)nullptr);
+  if (nSlack > 0) hipLaunchKernelGGL(k_fill_d, dim3(gridFor(nSlack)), dim3(kT), 0, s, cscVal + nnz0, -1.0, nSlack);
+  PDLP_HIP(hipGetLastError());
+}
+
+void gpuFill(double* a, double v, int64_t count, hipStream_t s) {
+  if (count > 0) hipLaunchKernelGGL(k_fill_d, dim3(gridFor(count)), dim3(kT), 0, s, a, v, count);
+}
+
+// Ruiz x10 in the infinity norm, then Pock-Chambolle alpha = 1 (cupdlp_scaling.c:47-231); both copies of the matrix
+// (reference-order CSC for the column passes, CSR for the row passes) receive the same two divisions, so they stay
+// bit-identical
+int32_t gpuScalePasses(const ScaleOperands& o, hipStream_t s) {
+  const int32_t n = o.n, m = o.m;
+  const int64_t nnz = o.nnz;
+  DeviceArray<double> cs, rs;
+  cs.alloc(n);
+  rs.alloc(m);
+  int32_t nPass = 0;
+  auto pass = [&](bool sum) {
+    if (sum) {
+      hipLaunchKernelGGL(k_major_reduce<true>, dim3(gridFor(n)), dim3(kT), 0, s, o.cscBeg, o.cscVal, n, cs.get());
+      hipLaunchKernelGGL(k_major_reduce<true>, dim3(gridFor(m)), dim3(kT), 0, s, o.aBeg, o.aVal, m, rs.get());
+    } else {
+      hipLaunchKernelGGL(k_major_reduce<false>, dim3(gridFor(n)), dim3(kT), 0, s, o.cscBeg, o.cscVal, n, cs.get());
+      hipLaunchKernelGGL(k_major_reduce<false>, dim3(gridFor(m)), dim3(kT), 0, s, o.aBeg, o.aVal, m, rs.get());
+    }
+    hipLaunchKernelGGL(k_apply_cols, dim3(gridFor(n)), dim3(kT), 0, s, cs.get(), n, o.cost, o.lower, o.upper, o.colScale, o.qdiag);
+    hipLaunchKernelGGL(k_apply_rows, dim3(gridFor(m)), dim3(kT), 0, s, rs.get(), m, o.rhs, o.rowScale);
+    hipLaunchKernelGGL(k_scale_vals, dim3(gridFor(nnz)), dim3(kT), 0, s, o.cscIdx, o.cscCol, rs.get(), cs.get(), nnz, o.cscVal);
+    hipLaunchKernelGGL(k_scale_vals, dim3(gridFor(nnz)), dim3(kT), 0, s, o.aMajor, o.aIdx, rs.get(), cs.get(), nnz, o.aVal);
+    if (o.csPass) {
+      if (n > 0) PDLP_HIP(hipMemcpyAsync(o.csPass + (size_t)nPass * n, cs.get(), sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+      if (m > 0) PDLP_HIP(hipMemcpyAsync(o.rsPass + (size_t)nPass * m, rs.get(), sizeof(double) * m, hipMemcpyDeviceToDevice, s));
+    }
+    ++nPass;
+  };
+  for (int it = 0; it < 10; ++it) pass(false);
+  pass(true);
+  PDLP_HIP(hipStreamSynchronize(s));
+  return nPass;
+}
+
+double gpuAbsMax(const double* val, int64_t count, hipStream_t s) {
+  const int nb = 1024;
+  DeviceArray<double> part;
+  part.alloc(nb);
+  hipLaunchKernelGGL(k_absmax_partial, dim3(nb), dim3(kT), 0, s, val, count, part.get());
+  std::vector<double> h(nb);
+  part.download(h.data(), nb, s);
+  PDLP_HIP(hipStreamSynchronize(s));
+  double mx = 0.0;
+  for (double v : h) mx = std::max(mx, v);
+  return mx;
+}
 
 void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProblem& D, const HipdlpSetup* hp) {
   const bool H = hp != nullptr;  // HiPDLP form (pdhg.cc:152-357 + scaling.cc) instead of the cuPDLP-C one
@@ -434,7 +504,7 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
     PDLP_HIP(hipMemcpyAsync(cscBeg.get() + n, &last, sizeof(int32_t), hipMemcpyHostToDevice, s));
     PDLP_HIP(hipStreamSynchronize(s));
   }
-  hipLaunchKernelGGL(k_col_entries, dim3(gridFor(n0)), dim3(kT), 0, s, aStart.get(), aIndex.get(), aValue.get(),
+  hipLaunchKernelGGL(k_col_entries<false>, dim3(gridFor(n0)), dim3(kT), 0, s, aStart.get(), aIndex.get(), aValue.get(),
                      kind.get(), rowNew.get(), n0, m, cscIdx.get(), cscCol.get(), cscVal.get(), bad.get());
   if (fetchOne(bad.get(), s) != 0) throw std::runtime_error("row index out of range");
 
@@ -449,7 +519,8 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
   D.normRhs = unscaledNormRhs(P.row_lower, P.row_upper, D.rowKind.data(), m);
 
   // A by rows (ascending column): stable sort of the column-major entries by row
-  transposeOnDevice(cscCol.get(), cscIdx.get(), cscVal.get(), nnz, m, n, s, D.A);
+  const bool keepM = D.keepMatrix && !H;
+  transposeOnDevice(cscCol.get(), cscIdx.get(), cscVal.get(), nnz, m, n, s, D.A, keepM ? &D.keep.permA : nullptr);
 
   // scaling: Ruiz x10 in the infinity norm, then Pock-Chambolle alpha = 1 (cupdlp_scaling.c:47-231);
   // both copies of the matrix (reference-order CSC for the column passes, CSR for the row
@@ -508,54 +579,44 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
       PDLP_HIP(hipStreamSynchronize(s));  // q goes out of scope
     }
   }
+  if (keepM) {  // the unscaled formulated data: new matrix values change every factor, and un-scaling does not give these bits
+    copyOf(D.keep.cost0, D.cost, s); copyOf(D.keep.lower0, D.lower, s); copyOf(D.keep.upper0, D.upper, s);
+    copyOf(D.keep.rhs0, D.rhs, s);
+    if (D.qdiag.size()) copyOf(D.keep.qdiag0, D.qdiag, s);
+  }
   if (doScale) {
-    DeviceArray<double> cs, rs;
-    cs.alloc(n);
-    rs.alloc(m);
     constexpr int kPasses = 11;  // Ruiz x 10 + Pock-Chambolle
     if (D.keepPasses) { D.csPass.alloc((size_t)kPasses * n); D.rsPass.alloc((size_t)kPasses * m); }
-    auto pass = [&](bool sum) {
-      if (sum) {
-        hipLaunchKernelGGL(k_major_reduce<true>, dim3(gridFor(n)), dim3(kT), 0, s, cscBeg.get(), cscVal.get(), n, cs.get());
-        hipLaunchKernelGGL(k_major_reduce<true>, dim3(gridFor(m)), dim3(kT), 0, s, D.A.beg.get(), D.A.val.get(), m, rs.get());
-      } else {
-        hipLaunchKernelGGL(k_major_reduce<false>, dim3(gridFor(n)), dim3(kT), 0, s, cscBeg.get(), cscVal.get(), n, cs.get());
-        hipLaunchKernelGGL(k_major_reduce<false>, dim3(gridFor(m)), dim3(kT), 0, s, D.A.beg.get(), D.A.val.get(), m, rs.get());
-      }
-      hipLaunchKernelGGL(k_apply_cols, dim3(gridFor(n)), dim3(kT), 0, s, cs.get(), n, D.cost.get(), D.lower.get(),
-                         D.upper.get(), D.colScale.get(), D.qdiag.size() ? D.qdiag.get() : (double*)nullptr);
-      hipLaunchKernelGGL(k_apply_rows, dim3(gridFor(m)), dim3(kT), 0, s, rs.get(), m, D.rhs.get(), D.rowScale.get());
-      hipLaunchKernelGGL(k_scale_vals, dim3(gridFor(nnz)), dim3(kT), 0, s, cscIdx.get(), cscCol.get(), rs.get(),
-                         cs.get(), nnz, cscVal.get());
-      hipLaunchKernelGGL(k_scale_vals, dim3(gridFor(nnz)), dim3(kT), 0, s, D.A.major.get(), D.A.idx.get(), rs.get(),
-                         cs.get(), nnz, D.A.val.get());
-      if (D.keepPasses) {
-        if (n > 0) PDLP_HIP(hipMemcpyAsync(D.csPass.get() + (size_t)D.nPass * n, cs.get(), sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-        if (m > 0) PDLP_HIP(hipMemcpyAsync(D.rsPass.get() + (size_t)D.nPass * m, rs.get(), sizeof(double) * m, hipMemcpyDeviceToDevice, s));
-        ++D.nPass;
-      }
-    };
-    for (int it = 0; it < 10; ++it) pass(false);
-    pass(true);
+    ScaleOperands o;
+    o.n = n; o.m = m; o.nnz = nnz;
+    o.cscBeg = cscBeg.get(); o.cscIdx = cscIdx.get(); o.cscCol = cscCol.get(); o.cscVal = cscVal.get();
+    o.aBeg = D.A.beg.get(); o.aMajor = D.A.major.get(); o.aIdx = D.A.idx.get(); o.aVal = D.A.val.get();
+    o.cost = D.cost.get(); o.lower = D.lower.get(); o.upper = D.upper.get(); o.rhs = D.rhs.get();
+    o.colScale = D.colScale.get(); o.rowScale = D.rowScale.get();
+    o.qdiag = D.qdiag.size() ? D.qdiag.get() : nullptr;
+    if (D.keepPasses) { o.csPass = D.csPass.get(); o.rsPass = D.rsPass.get(); }
+    const int32_t done = gpuScalePasses(o, s);
+    if (D.keepPasses) D.nPass = done;
     D.scaled = true;
-    PDLP_HIP(hipStreamSynchronize(s));
   }
 
   // max |a_ij| of the scaled matrix (initial step size, cupdlp_step.c:360-365)
-  {
-    const int nb = 1024;
-    DeviceArray<double> part;
-    part.alloc(nb);
-    hipLaunchKernelGGL(k_absmax_partial, dim3(nb), dim3(kT), 0, s, cscVal.get(), nnz, part.get());
-    std::vector<double> h(nb);
-    part.download(h.data(), nb, s);
-    PDLP_HIP(hipStreamSynchronize(s));
-    D.matNormInf = 0.0;
-    for (double v : h) D.matNormInf = std::max(D.matNormInf, v);
-  }
+  D.matNormInf = gpuAbsMax(cscVal.get(), nnz, s);
 
   // A' by columns with ascending row: stable sort of the row-major entries by column
-  transposeOnDevice(D.A.major.get(), D.A.idx.get(), D.A.val.get(), nnz, n, m, s, D.At);
+  transposeOnDevice(D.A.major.get(), D.A.idx.get(), D.A.val.get(), nnz, n, m, s, D.At, keepM ? &D.keep.permAt : nullptr);
+  if (keepM) {  // the arrays a plain set-up frees here; the layouts take D.A's, so the row-major structure is copied
+    MatrixKeep& K = D.keep;
+    K.nnz0 = nnz0;
+    K.aStart = std::move(aStart); K.aIndex = std::move(aIndex);
+    K.cscBeg = std::move(cscBeg); K.cscIdx = std::move(cscIdx); K.cscCol = std::move(cscCol); K.cscVal = std::move(cscVal);
+    copyOf(K.aBeg, D.A.beg, s); copyOf(K.aMajor, D.A.major, s);
+    K.aIdx.alloc((size_t)nnz); K.aVal.alloc((size_t)nnz);
+    if (nnz > 0) {
+      PDLP_HIP(hipMemcpyAsync(K.aIdx.get(), D.A.idx.get(), sizeof(int32_t) * nnz, hipMemcpyDeviceToDevice, s));
+      PDLP_HIP(hipMemcpyAsync(K.aVal.get(), D.A.val.get(), sizeof(double) * nnz, hipMemcpyDeviceToDevice, s));
+    }
+  }
 
   // host copies: scale vectors (postsolve / hot start) and the left-to-right sums of
   // the scaled c and b that PDHG_Init_Step_Sizes needs (cupdlp_step.c:349-358)

@@ -32,6 +32,25 @@ struct DeviceCsrData {
   int64_t nnz = 0;
 };
 
+// What a matrix-updatable solver keeps of the set-up (PDLP_UPDATABLE_MATRIX, pdlp_update.hpp): everything here depends on
+// the sparsity pattern and the row kinds only, except the two value scratches and the unscaled data.
+struct MatrixKeep {
+  int64_t nnz0 = 0;  // the caller's nonzeros (nnz - slack entries)
+  DeviceArray<int32_t> aStart, aIndex;           // the caller's column-wise pattern
+  DeviceArray<int32_t> cscBeg, cscIdx, cscCol;   // reference-order columns (equality-type entries first): row, column of every entry
+  DeviceArray<int32_t> aBeg, aMajor, aIdx;       // rows with ascending column
+  DeviceArray<int32_t> permA;                    // row-major slot -> reference-order slot
+  DeviceArray<int32_t> permAt;                   // column-major (ascending row) slot -> row-major slot; released once the
+                                                 // layouts' source indices are composed with it
+  DeviceArray<double> cscVal, aVal;              // value scratch of both orders (scaled values after set-up / an update)
+  DeviceArray<double> cost0, lower0, upper0, rhs0, qdiag0;  // the UNSCALED formulated data (qdiag0: QP only)
+  size_t bytes() const {
+    return sizeof(int32_t) * (aStart.size() + aIndex.size() + cscBeg.size() + cscIdx.size() + cscCol.size() + aBeg.size() +
+                              aMajor.size() + aIdx.size() + permA.size() + permAt.size()) +
+           sizeof(double) * (cscVal.size() + aVal.size() + cost0.size() + lower0.size() + upper0.size() + rhs0.size() + qdiag0.size());
+  }
+};
+
 struct DeviceProblem {
   int32_t n = 0, m = 0, n0 = 0, nEqs = 0;
   int64_t nnz = 0;
@@ -53,6 +72,10 @@ struct DeviceProblem {
   bool keepPasses = false;
   int32_t nPass = 0;
   DeviceArray<double> csPass, rsPass;
+  // Matrix-updatable solvers (set keepMatrix before gpuPrepare; cuPDLP-C form only): the pattern-only arrays the set-up
+  // otherwise frees, both sort permutations and the unscaled data
+  bool keepMatrix = false;
+  MatrixKeep keep;
 };
 
 // Options of the HiPDLP form (pdlp_host.hpp formulateHipdlp / scaleHipdlp); nullptr = cuPDLP-C form.
@@ -63,6 +86,29 @@ struct HipdlpSetup {
 // Formulate + scale + both orientations on the device.  Throws std::runtime_error.
 void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProblem& out,
                 const HipdlpSetup* hipdlp = nullptr);
+
+// ---- the value-dependent layer of gpuPrepare, shared with pdlp_mi355x_update_matrix (pdlp_update.cpp) ----------------
+// The formulated values of the caller's a_value in reference order: <= rows negated, -1.0 for the nSlack slack entries
+// behind them.  Pattern arrays as gpuPrepare built them; writes cscVal only.
+void gpuFormulateValues(const int32_t* aStart, const int32_t* aIndex, const double* aValue, const int32_t* rowKind,
+                        const int32_t* rowNewIdx, int32_t n0, int32_t m, int64_t nnz0, int64_t nSlack, double* cscVal,
+                        hipStream_t s);
+// The scaling passes of the cuPDLP-C form (Ruiz x 10 in the infinity norm, then Pock-Chambolle alpha = 1): column
+// factors from the reference-order columns, row factors from the rows, both copies and the data take each pass.
+struct ScaleOperands {
+  int32_t n = 0, m = 0;
+  int64_t nnz = 0;
+  const int32_t *cscBeg = nullptr, *cscIdx = nullptr, *cscCol = nullptr;
+  double* cscVal = nullptr;
+  const int32_t *aBeg = nullptr, *aMajor = nullptr, *aIdx = nullptr;
+  double* aVal = nullptr;
+  double *cost = nullptr, *lower = nullptr, *upper = nullptr, *rhs = nullptr, *colScale = nullptr, *rowScale = nullptr;
+  double* qdiag = nullptr;                        // QP only, else nullptr
+  double *csPass = nullptr, *rsPass = nullptr;    // updatable solvers: [11 n], [11 m], pass-major; else nullptr
+};
+int32_t gpuScalePasses(const ScaleOperands& o, hipStream_t s);  // returns the number of passes (11); synchronises
+double gpuAbsMax(const double* val, int64_t count, hipStream_t s);  // max |val[p]| (matNormInf); synchronises
+void gpuFill(double* a, double v, int64_t count, hipStream_t s);
 
 // Slab layout (pdlp_host.hpp SlabLayout) built on the device from a device CSR.
 struct DeviceSlabLayout {

@@ -4,6 +4,7 @@
 // reference's check iterations (nIter < 10, nIter % 40 == 0, last iteration).
 #include "pdlp_solver.hpp"
 #include "pdlp_detmath.h"
+#include "pdlp_update.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -478,8 +479,13 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   if (sharded_) gpuSetup_ = false;
   const bool doScale = !(opt_.features_off & PDLP_FEATURE_SCALING_OFF);
   updatable_ = opt_.updatable != 0 && !sharded_;  // (a sharded solver refuses updates: nothing to keep)
+  // new matrix values on the kept pattern (pdlp_update.hpp).  Not for a Hessian with an off-diagonal part: its scaled copy
+  // follows the column factors (pdlp_mi355x_update_matrix says so when asked)
+  matrixUpdatable_ = updatable_ && (opt_.updatable & PDLP_UPDATABLE_MATRIX) != 0 && !hasQoff_;
+  nnzIn_ = nnzIn;
   DeviceProblem devProb;
   devProb.keepPasses = updatable_;
+  devProb.keepMatrix = matrixUpdatable_;
   F_.keepPasses = updatable_;
   if (gpuSetup_) {
     // formulate + scale + both orientations on the device; F_ keeps only the host-side bookkeeping
@@ -495,6 +501,7 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
     sumCost2_ = devProb.sumCost2;
     sumRhs2_ = devProb.sumRhs2;
     if (updatable_) keepForUpdates(&devProb);
+    if (matrixUpdatable_) mk_ = std::move(devProb.keep);
   } else if (shardedGpuSetup) {
     gpuPrepare(P, doScale, stream_, devProb);
     sumCost2_ = devProb.sumCost2;
@@ -524,9 +531,11 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   } else {
     formulate(P, F_);
     F_.keepPasses = updatable_;  // (formulate starts from a fresh form)
+    if (matrixUpdatable_) keepUnscaled(F_);
     if (doScale) scale(F_);
     finalize(F_);
     if (updatable_) keepForUpdates(nullptr);
+    if (matrixUpdatable_) keepMatrixFromHost(P);
     sumCost2_ = 0.0;
     for (double v : F_.cost) sumCost2_ += v * v;
     sumRhs2_ = 0.0;
@@ -740,6 +749,87 @@ void Solver::keepForUpdates(DeviceProblem* D) {
   F_.rsPass = std::vector<double>();
 }
 
+// Matrix-updatable solver prepared on the host: the pattern of both orders, the permutation between them and the unscaled
+// data go to HBM in the arrays the device-side set-up keeps (pdlp_setup.hpp MatrixKeep), so that the update itself is the
+// same device code for both.  The permutations are those of finalize()'s counting transposes.
+void Solver::keepMatrixFromHost(const pdlp_problem_t& P) {
+  const int32_t n = F_.n, m = F_.m, n0 = F_.n0;
+  const int64_t nnz = F_.nnz;
+  MatrixKeep& K = mk_;
+  K.nnz0 = nnzIn_;
+  auto put = [&](DeviceArray<int32_t>& d, const int32_t* h, size_t count) { d.alloc(count); d.upload(h, count, stream_); };
+  auto putD = [&](DeviceArray<double>& d, const std::vector<double>& h) { d.alloc(h.size()); d.upload(h.data(), h.size(), stream_); };
+  put(K.aStart, P.a_start, (size_t)n0 + 1);
+  put(K.aIndex, P.a_index, (size_t)nnzIn_);
+  std::vector<int32_t> cscCol((size_t)nnz), aMajor((size_t)nnz), permA((size_t)nnz), permAt((size_t)nnz);
+  for (int32_t j = 0; j < n; ++j)
+    for (int32_t p = F_.csc.beg[j]; p < F_.csc.beg[j + 1]; ++p) cscCol[p] = j;
+  for (int32_t i = 0; i < m; ++i)
+    for (int32_t q = F_.csr.beg[i]; q < F_.csr.beg[i + 1]; ++q) aMajor[q] = i;
+  {
+    std::vector<int32_t> pos(F_.csr.beg.begin(), F_.csr.beg.end() - 1);
+    for (int64_t p = 0; p < nnz; ++p) permA[pos[F_.csc.idx[p]]++] = (int32_t)p;
+    pos.assign(F_.cscSorted.beg.begin(), F_.cscSorted.beg.end() - 1);
+    for (int64_t q = 0; q < nnz; ++q) permAt[pos[F_.csr.idx[q]]++] = (int32_t)q;
+  }
+  put(K.cscBeg, F_.csc.beg.data(), F_.csc.beg.size());
+  put(K.cscIdx, F_.csc.idx.data(), (size_t)nnz);
+  put(K.cscCol, cscCol.data(), (size_t)nnz);
+  put(K.aBeg, F_.csr.beg.data(), F_.csr.beg.size());
+  put(K.aMajor, aMajor.data(), (size_t)nnz);
+  put(K.aIdx, F_.csr.idx.data(), (size_t)nnz);
+  put(K.permA, permA.data(), (size_t)nnz);
+  put(K.permAt, permAt.data(), (size_t)nnz);
+  putD(K.cscVal, F_.csc.val);
+  putD(K.aVal, F_.csr.val);
+  putD(K.cost0, F_.cost0); putD(K.lower0, F_.lower0); putD(K.upper0, F_.upper0); putD(K.rhs0, F_.rhs0);
+  if (!F_.qdiag0.empty()) putD(K.qdiag0, F_.qdiag0);
+  PDLP_HIP(hipStreamSynchronize(stream_));  // the host vectors are released here
+  F_.cost0 = F_.lower0 = F_.upper0 = F_.rhs0 = F_.qdiag0 = std::vector<double>();
+}
+
+// The operands have just been built from tagged values (value of row-major slot q = q + 1, of column-major slot q
+// likewise): every value array of a layout is turned into its source indices — those of A' composed with the column-major
+// -> row-major permutation, so that both operands are filled from ONE scratch, mk_.aVal — and filled for the first time.
+void Solver::finishMatrixKeep() {
+  // This rests on what every build path does today (DeviceMatrix::upload / buildSlabLayout on the host, buildFromDevice /
+  // gpuBuildSlabLayout / k_long_copy on the device): values are COPIED into the layouts, never scaled or combined; every
+  // value array ends in exactly one pad element; the stream / long-major and the slab array of an operand together hold
+  // every entry once.  A build that stops doing so is caught here, at create, instead of by wrong sums later.
+  const int64_t nnz = F_.nnz;
+  DeviceArray<unsigned long long> tagged;  // [0]: slots of A's value arrays that held a tag, [1]: of A''s
+  tagged.alloc(2);
+  tagged.zero(stream_);
+  auto extract = [&](const DeviceArray<double>& v, DeviceArray<int32_t>& src, const int32_t* compose, int which) {
+    if (v.size() == 0) throw std::runtime_error("pdlp_mi355x: a layout's value array without its pad element (matrix-updatable set-up)");
+    src.alloc(v.size());
+    launchTagsToSource(v.get(), (int64_t)v.size(), (int64_t)v.size() - 1, nnz, compose, src.get(), tagged.get() + which, stream_);
+  };
+  extract(dA_.val, srcAVal_, nullptr, 0);
+  if (dA_.useSlab) extract(dA_.slabVal, srcASlab_, nullptr, 0);
+  extract(dAt_.val, srcAtVal_, mk_.permAt.get(), 1);
+  if (dAt_.useSlab) extract(dAt_.slabVal, srcAtSlab_, mk_.permAt.get(), 1);
+  unsigned long long found[2] = {0, 0};
+  tagged.download(found, 2, stream_);
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  if ((int64_t)found[0] != nnz || (int64_t)found[1] != nnz)
+    throw std::runtime_error("pdlp_mi355x: the layouts of a matrix-updatable solver hold " + std::to_string(found[0]) + " / " +
+                             std::to_string(found[1]) + " tagged values of A / A', the matrix has " + std::to_string(nnz) +
+                             " entries (a layout build no longer copies values slot for slot)");
+  mk_.permAt.release();
+  refillOperands();
+  PDLP_HIP(hipStreamSynchronize(stream_));
+}
+
+void Solver::refillOperands() {
+  const int64_t nnz = F_.nnz;
+  const double* v = mk_.aVal.get();
+  launchRefill(srcAVal_.get(), v, (int64_t)srcAVal_.size(), nnz, dA_.val.get(), stream_);
+  if (dA_.useSlab) launchRefill(srcASlab_.get(), v, (int64_t)srcASlab_.size(), nnz, dA_.slabVal.get(), stream_);
+  launchRefill(srcAtVal_.get(), v, (int64_t)srcAtVal_.size(), nnz, dAt_.val.get(), stream_);
+  if (dAt_.useSlab) launchRefill(srcAtSlab_.get(), v, (int64_t)srcAtSlab_.size(), nnz, dAt_.slabVal.get(), stream_);
+}
+
 void Solver::setHotStart(const double* colValue, const double* rowValue, const double* rowDual) {
   startX_.assign(F_.n, 0.0);
   startY_.assign(F_.m, 0.0);
@@ -778,8 +868,13 @@ void Solver::uploadProblem() {
   const int32_t n = F_.n;
   dAt_.majorCost = kSlabMajorCostCols;
   if (!sharded_) {
+    if (matrixUpdatable_) {  // values that name their slot: the layouts then tell where every value slot is filled from
+      for (size_t q = 0; q < F_.csr.val.size(); ++q) F_.csr.val[q] = (double)(q + 1);
+      for (size_t q = 0; q < F_.cscSorted.val.size(); ++q) F_.cscSorted.val[q] = (double)(q + 1);
+    }
     dA_.upload(F_.csr, F_.m, n, sw_, stream_);
     dAt_.upload(F_.cscSorted, n, F_.m, sw_, stream_);
+    if (matrixUpdatable_) finishMatrixKeep();
   } else {
     Compressed csrSlab, cscSlab;
     extractSlab(F_, r0_, r1_, csrSlab, cscSlab);
@@ -866,8 +961,13 @@ void Solver::downloadForm(DeviceProblem& D, StandardForm& F, hipStream_t s) {
 
 void Solver::uploadProblemFromDevice(DeviceProblem& D) {
   dAt_.majorCost = kSlabMajorCostCols;
+  if (matrixUpdatable_) {  // values that name their slot (the scaled ones are in mk_.aVal): see finishMatrixKeep
+    launchTagValues(D.A.val.get(), D.A.nnz, stream_);
+    launchTagValues(D.At.val.get(), D.At.nnz, stream_);
+  }
   buildSlabTuned(dA_, D.A, sw_, stream_);
   buildSlabTuned(dAt_, D.At, sw_, stream_);
+  if (matrixUpdatable_) finishMatrixKeep();
   cost_ = std::move(D.cost); rhs_ = std::move(D.rhs); lower_ = std::move(D.lower); upper_ = std::move(D.upper);
   colScale_ = std::move(D.colScale); rowScale_ = std::move(D.rowScale);
   if (D.qdiag.size()) {
@@ -2148,6 +2248,15 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     put(1, (double)nPass_);
     put(2, (double)vecs_.lowerUniform);
     put(3, graphExec_ ? 1.0 : 0.0);
+    // [4] bytes of HBM a matrix-updatable solver keeps on top of [0] (PDLP_UPDATABLE_MATRIX: the pattern of both orders, a
+    // source index per value slot, the unscaled data, staging of a_value once a matrix update has run), [5] 1 = it is one
+    put(4, (double)(mk_.bytes() + sizeof(int32_t) * (srcAVal_.size() + srcASlab_.size() + srcAtVal_.size() + srcAtSlab_.size()) +
+                    sizeof(double) * updMat_.size()));
+    put(5, matrixUpdatable_ ? 1.0 : 0.0);
+  } else if (name == "update_matrix_seconds") {  // the parts of the last pdlp_mi355x_update_matrix: upload + validation, formulate,
+    // scaling passes, refills, norms + sums, per-block bounds, graph capture, reset; [8] = the whole update
+    for (int k = 0; k < 8; ++k) put(k, updMatSeconds_[k]);
+    put(8, setupSeconds_);
   } else if (name == "trial_launches") {  // kernels per trial step of the hot loop (2 = fused decision + primal step)
     // mesh: 9 with single-block wait kernels, 7 with consumers that wait themselves, 5 with an exchange per launch
     // (fusedWait 0 / 1 / 2)

@@ -112,6 +112,8 @@ class SolverBase {
   virtual double timeKernel(const std::string& name, int32_t reps) = 0;
   // pdlp_mi355x_update; validates before it changes anything.  Only the cuPDLP-C path takes updates.
   virtual void update(const pdlp_update_t& u);
+  // pdlp_mi355x_update_matrix; likewise
+  virtual void updateMatrix(const double* aValue, int64_t numNz, const pdlp_update_t* u);
 };
 
 class Solver : public SolverBase {
@@ -129,6 +131,7 @@ class Solver : public SolverBase {
   void stage(const std::string& name, double* out, int32_t cap) override;
   double timeKernel(const std::string& name, int32_t reps) override;
   void update(const pdlp_update_t& u) override;  // pdlp_update.cpp
+  void updateMatrix(const double* aValue, int64_t numNz, const pdlp_update_t* u) override;  // pdlp_update.cpp
 
  private:
   // setup
@@ -144,6 +147,11 @@ class Solver : public SolverBase {
   void applyHotStart();
   void setHotStart(const double* colValue, const double* rowValue, const double* rowDual);  // -> startX_, startY_ (formulated, scaled)
   void keepForUpdates(DeviceProblem* D);  // updatable solvers: the passes and the row bookkeeping into HBM
+  // matrix-updatable solvers (pdlp_update.hpp): the host set-up's pattern into mk_; the operands' values replaced by tags
+  // in front of the layout builds; the layouts' source indices out of the tagged builds, and the first refill
+  void keepMatrixFromHost(const pdlp_problem_t& P);
+  void finishMatrixKeep();
+  void refillOperands();
   bool refreshBlockBounds();              // fused slab trial: colBlockUni_ / colBlockBounds_ from lower_ / upper_; returns allLower
   // hot loop
   void enqueueTrial();
@@ -241,6 +249,16 @@ class Solver : public SolverBase {
   int32_t nPass_ = 0;
   DeviceArray<double> csPass_, rsPass_, updIn_;
   DeviceArray<int32_t> rowKindDev_, rowNewIdxDev_, slackRowDev_, updBad_;
+  // Matrix-updatable solvers (PDLP_UPDATABLE_MATRIX): mk_ (pdlp_setup.hpp MatrixKeep) and, per value array of the two
+  // operands' layouts (stream / long-major val, slab val), the slot of mk_.aVal every value slot is filled from (-1: pad).
+  // updMat_: staging of the caller's a_value (allocated by the first matrix update).  updMatSeconds_: the parts of the
+  // last one (stage "update_matrix_seconds").
+  bool matrixUpdatable_ = false;
+  int64_t nnzIn_ = 0;  // the caller's nonzeros at create
+  MatrixKeep mk_;
+  DeviceArray<int32_t> srcAVal_, srcASlab_, srcAtVal_, srcAtSlab_;
+  DeviceArray<double> updMat_;
+  double updMatSeconds_[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // upload + validation, formulate, scaling passes, refills, norms + sums, block bounds, graph capture, reset
   double updSeconds_[6] = {0, 0, 0, 0, 0, 0};  // upload + validation, kernels, norms + sums, block bounds, graph capture, reset
   int32_t barrierFallbacks_ = 0, smallLaunches_ = 0;
   unsigned long long smallSeq_ = 0;  // persistent launches since gridBar_ was zeroed (their roll call counts cumulatively)

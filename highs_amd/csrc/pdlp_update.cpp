@@ -75,6 +75,11 @@ void hostReplayUpdate(const pdlp_update_t& u, StandardForm& F) {
       lo = infLo(u.row_lower[r]);
       up = infUp(u.row_upper[r]);
     }
+    if (!F.cost0.empty()) {  // matrix-updatable form: the unscaled data follow every update
+      if (dc) F.cost0[j] = c;
+      if (dl) F.lower0[j] = lo;
+      if (du) F.upper0[j] = up;
+    }
     for (int32_t p = 0; p < F.nPass; ++p) {
       const double cs = F.csPass[(size_t)p * n + j];
       c /= cs; lo *= cs; up *= cs;
@@ -91,6 +96,7 @@ void hostReplayUpdate(const pdlp_update_t& u, StandardForm& F) {
       else if (k == kRowBound) r = 0.0;
       else if (k == kRowLeq) r = -u.row_upper[i];
       else r = u.row_lower[i];
+      if (!F.rhs0.empty()) F.rhs0[ni] = r;
       for (int32_t p = 0; p < F.nPass; ++p) r /= F.rsPass[(size_t)p * m + ni];
       F.rhs[ni] = r;
     }
@@ -99,8 +105,57 @@ void hostReplayUpdate(const pdlp_update_t& u, StandardForm& F) {
   if (u.has_offset) F.offset = u.offset;
 }
 
+void keepUnscaled(StandardForm& F) {
+  F.cost0 = F.cost; F.lower0 = F.lower; F.upper0 = F.upper; F.rhs0 = F.rhs; F.qdiag0 = F.qdiag;
+}
+
+void throwAllZeroMatrix() {  // the wording of requireConstraints (pdlp_host.cpp): what create() says to such a matrix
+  throw std::runtime_error("pdlp_mi355x: the LP has no rows, no columns or no matrix nonzeros — HiGHS solves such "
+                           "LPs itself (solveUnconstrainedLp) before the PDLP path");
+}
+
+void checkMatrixUpdateShape(const double* aValue, int64_t numNz, int64_t nnzAtCreate) {
+  if (!aValue) throw std::runtime_error("pdlp_mi355x_update_matrix: a_value is NULL");
+  if (numNz != nnzAtCreate)
+    throw std::runtime_error("pdlp_mi355x_update_matrix: num_nz = " + std::to_string(numNz) + " differs from the " +
+                             std::to_string(nnzAtCreate) + " nonzeros the solver was created with (the sparsity pattern is fixed: "
+                             "create a new solver)");
+}
+
+void hostReplayMatrixUpdate(const pdlp_problem_t& P, const double* aValue, const pdlp_update_t* u, bool doScale, StandardForm& F) {
+  const int64_t nnz0 = F.n0 > 0 ? (int64_t)P.a_start[F.n0] : 0;
+  if (!aValue) throw std::runtime_error("pdlp_mi355x_update_matrix: a_value is NULL");
+  if (!F.keepPasses || F.cost0.size() != F.cost.size())
+    throw std::runtime_error("pdlp_mi355x_update_matrix: the form did not keep its unscaled data");
+  if (u) {
+    checkUpdateShape(*u);
+    if (updateMask(*u) & kUpdRows) {
+      const int32_t bad = firstKindChange(F.rowKind.data(), F.m, u->row_lower, u->row_upper);
+      if (bad < F.m) throwKindChange(bad, F.rowKind[bad], rowKindOf(u->row_lower[bad], u->row_upper[bad]));
+    }
+  }
+  bool anyNonzero = false;
+  for (int64_t p = 0; p < nnz0 && !anyNonzero; ++p) anyNonzero = aValue[p] != 0.0;
+  if (!anyNonzero) throwAllZeroMatrix();
+  // ---- nothing below is refused ----
+  formulateValues(P.a_start, P.a_index, aValue, F);
+  F.cost = F.cost0; F.lower = F.lower0; F.upper = F.upper0; F.rhs = F.rhs0; F.qdiag = F.qdiag0;
+  F.colScale.assign((size_t)F.n, 1.0);
+  F.rowScale.assign((size_t)F.m, 1.0);
+  F.nPass = 0;
+  F.csPass.clear();
+  F.rsPass.clear();
+  F.scaled = false;
+  if (u) hostReplayUpdate(*u, F);  // (no pass is kept at this point: the formulated data, unscaled, and their norms)
+  if (doScale) scale(F);           // the set-up's own passes; keeps the NEW factors for later updates
+}
+
 void SolverBase::update(const pdlp_update_t&) {
   throw std::runtime_error("pdlp_mi355x_update: HiPDLP solvers (algorithm = 1) do not take updates");
+}
+
+void SolverBase::updateMatrix(const double*, int64_t, const pdlp_update_t*) {
+  throw std::runtime_error("pdlp_mi355x_update_matrix: HiPDLP solvers (algorithm = 1) do not take updates");
 }
 
 // The held solver is brought to the state of a fresh create() on the modified problem.  Everything that can be refused
@@ -153,6 +208,12 @@ void Solver::update(const pdlp_update_t& u) {
                    cost_.get(), lower_.get(), upper_.get(), stream_);
   if (mask & kUpdRows)
     launchUpdateRows(dRowLo, dRowUp, rowKindDev_.get(), rowNewIdxDev_.get(), m, rsPass_.get(), nPass_, rhs_.get(), stream_);
+  if (matrixUpdatable_) {  // the unscaled data follow every update: the same kernels with no pass to replay
+    launchUpdateCols(mask, dCost, dColLo, dColUp, dRowLo, dRowUp, slackRowDev_.get(), F_.sense, n0, n, nullptr, 0, mk_.cost0.get(),
+                     mk_.lower0.get(), mk_.upper0.get(), stream_);
+    if (mask & kUpdRows)
+      launchUpdateRows(dRowLo, dRowUp, rowKindDev_.get(), rowNewIdxDev_.get(), m, nullptr, 0, mk_.rhs0.get(), stream_);
+  }
   PDLP_HIP(hipStreamSynchronize(stream_));
   updSeconds_[1] = since(t1);
 
@@ -212,6 +273,163 @@ void Solver::update(const pdlp_update_t& u) {
   }
   PDLP_HIP(hipStreamSynchronize(stream_));
   updSeconds_[4] = since(t1);
+  setupSeconds_ = since(t0);
+}
+
+// pdlp_mi355x_update_matrix: new matrix values on the kept pattern, optionally with new data (u), as ONE change.  Of
+// create()'s work only the value-dependent layer runs: formulate values -> the set-up's pass loop -> matNormInf -> one
+// refill per value array.  No sort, no layout build, no timing launch; the slab width, the XCD map and the pacing stay
+// (none of them changes a sum).  Validation first: the caller's values and row bounds go to staging buffers that nothing
+// else reads.
+void Solver::updateMatrix(const double* aValue, int64_t numNz, const pdlp_update_t* u) {
+  using clock = std::chrono::steady_clock;
+  const auto t0 = clock::now();
+  auto since = [](clock::time_point a) { return std::chrono::duration<double>(clock::now() - a).count(); };
+  if (sharded_)
+    throw std::runtime_error("pdlp_mi355x_update_matrix: sharded solvers (pdlp_mi355x_create_sharded) do not take updates");
+  if (!(opt_.updatable & PDLP_UPDATABLE_MATRIX))
+    throw std::runtime_error("pdlp_mi355x_update_matrix: the solver was not created for matrix updates (pdlp_params_t.updatable "
+                             "lacks PDLP_UPDATABLE_MATRIX)");
+  if (hasQoff_)
+    throw std::runtime_error("pdlp_mi355x_update_matrix: QPs whose Hessian has off-diagonal entries do not take matrix updates "
+                             "(the scaled copy of the Hessian follows the column factors; left for a later change)");
+  if (!matrixUpdatable_) throw std::runtime_error("pdlp_mi355x_update_matrix: the solver kept nothing for matrix updates");
+  checkMatrixUpdateShape(aValue, numNz, nnzIn_);
+  static const pdlp_update_t kNoData{};
+  const pdlp_update_t& ud = u ? *u : kNoData;
+  checkUpdateShape(ud);
+  const int32_t n0 = F_.n0, n = F_.n, m = F_.m;
+  const int64_t nnz = F_.nnz, nnz0 = nnzIn_;
+  const int32_t mask = updateMask(ud);
+  PDLP_HIP(hipSetDevice(opt_.device));
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  if (updIn_.size() == 0) {
+    updIn_.alloc((size_t)3 * n0 + (size_t)2 * m);
+    updBad_.alloc(1);
+  }
+  if (updMat_.size() == 0) updMat_.alloc((size_t)nnz0);
+  double* dCost = updIn_.get();
+  double* dColLo = dCost + n0;
+  double* dColUp = dColLo + n0;
+  double* dRowLo = dColUp + n0;
+  double* dRowUp = dRowLo + m;
+  auto put = [&](double* dev, const double* host, int64_t count) {
+    if (count > 0) PDLP_HIP(hipMemcpyAsync(dev, host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, stream_));
+  };
+  put(updMat_.get(), aValue, nnz0);
+  if (mask & kUpdRows) {
+    put(dRowLo, ud.row_lower, m);
+    put(dRowUp, ud.row_upper, m);
+    int32_t bad = m;
+    PDLP_HIP(hipMemcpyAsync(updBad_.get(), &bad, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+    launchUpdateValidate(dRowLo, dRowUp, rowKindDev_.get(), m, updBad_.get(), stream_);
+    PDLP_HIP(hipMemcpyAsync(&bad, updBad_.get(), sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    PDLP_HIP(hipStreamSynchronize(stream_));
+    if (bad < m) throwKindChange(bad, F_.rowKind[bad], rowKindOf(ud.row_lower[bad], ud.row_upper[bad]));
+  }
+  if (gpuAbsMax(updMat_.get(), nnz0, stream_) == 0.0) throwAllZeroMatrix();  // (a NaN among the values is not zero, as for create)
+  // ---- nothing below is refused ----
+  if (mask & kUpdCost) put(dCost, ud.col_cost, n0);
+  if (mask & kUpdColLower) put(dColLo, ud.col_lower, n0);
+  if (mask & kUpdColUpper) put(dColUp, ud.col_upper, n0);
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  updMatSeconds_[0] = since(t0);
+
+  // formulated values in reference order, their row-major copy through the kept permutation; the unscaled data overlaid
+  // with what u gives (the replay kernels with no pass), copied into the solver's vectors
+  auto t1 = clock::now();
+  MatrixKeep& K = mk_;
+  gpuFormulateValues(K.aStart.get(), K.aIndex.get(), updMat_.get(), rowKindDev_.get(), rowNewIdxDev_.get(), n0, m, nnz0, nnz - nnz0,
+                     K.cscVal.get(), stream_);
+  launchRefill(K.permA.get(), K.cscVal.get(), nnz, nnz, K.aVal.get(), stream_);
+  launchUpdateCols(mask, dCost, dColLo, dColUp, dRowLo, dRowUp, slackRowDev_.get(), F_.sense, n0, n, nullptr, 0, K.cost0.get(),
+                   K.lower0.get(), K.upper0.get(), stream_);
+  if (mask & kUpdRows)
+    launchUpdateRows(dRowLo, dRowUp, rowKindDev_.get(), rowNewIdxDev_.get(), m, nullptr, 0, K.rhs0.get(), stream_);
+  auto copy = [&](double* dst, const double* src, int64_t count) {
+    if (count > 0) PDLP_HIP(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)count, hipMemcpyDeviceToDevice, stream_));
+  };
+  copy(cost_.get(), K.cost0.get(), n);
+  copy(lower_.get(), K.lower0.get(), n);
+  copy(upper_.get(), K.upper0.get(), n);
+  copy(rhs_.get(), K.rhs0.get(), m);
+  if (qdiag_.size()) copy(qdiag_.get(), K.qdiag0.get(), n);
+  gpuFill(colScale_.get(), 1.0, n, stream_);
+  gpuFill(rowScale_.get(), 1.0, m, stream_);
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  updMatSeconds_[1] = since(t1);
+
+  t1 = clock::now();
+  if (F_.scaled) {  // (PDLP_FEATURE_SCALING_OFF: nothing is scaled, no pass is kept)
+    ScaleOperands o;
+    o.n = n; o.m = m; o.nnz = nnz;
+    o.cscBeg = K.cscBeg.get(); o.cscIdx = K.cscIdx.get(); o.cscCol = K.cscCol.get(); o.cscVal = K.cscVal.get();
+    o.aBeg = K.aBeg.get(); o.aMajor = K.aMajor.get(); o.aIdx = K.aIdx.get(); o.aVal = K.aVal.get();
+    o.cost = cost_.get(); o.lower = lower_.get(); o.upper = upper_.get(); o.rhs = rhs_.get();
+    o.colScale = colScale_.get(); o.rowScale = rowScale_.get();
+    o.qdiag = qdiag_.size() ? qdiag_.get() : nullptr;
+    o.csPass = csPass_.get(); o.rsPass = rsPass_.get();  // a later pdlp_mi355x_update replays the NEW factors
+    nPass_ = gpuScalePasses(o, stream_);
+  }
+  updMatSeconds_[2] = since(t1);
+
+  t1 = clock::now();
+  refillOperands();
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  updMatSeconds_[3] = since(t1);
+
+  // matNormInf, the host copies of the scale vectors, the left-to-right sums of the scaled c, b — as the set-up does;
+  // the termination norms are those of the unscaled data and change with u only
+  t1 = clock::now();
+  F_.matNormInf = gpuAbsMax(K.cscVal.get(), nnz, stream_);
+  {
+    std::vector<double> hc((size_t)n), hb((size_t)m);
+    colScale_.download(F_.colScale.data(), (size_t)n, stream_);
+    rowScale_.download(F_.rowScale.data(), (size_t)m, stream_);
+    cost_.download(hc.data(), (size_t)n, stream_);
+    rhs_.download(hb.data(), (size_t)m, stream_);
+    PDLP_HIP(hipStreamSynchronize(stream_));
+    sumCost2_ = 0.0;
+    for (double v : hc) sumCost2_ += v * v;
+    sumRhs2_ = 0.0;
+    for (double v : hb) sumRhs2_ += v * v;
+  }
+  if (mask & kUpdCost) F_.normCost = unscaledNormCost(ud.col_cost, n0, F_.sense);
+  if (mask & kUpdRows) F_.normRhs = unscaledNormRhs(ud.row_lower, ud.row_upper, F_.rowKind.data(), m);
+  if (ud.has_offset) F_.offset = ud.offset;
+  updMatSeconds_[4] = since(t1);
+
+  t1 = clock::now();
+  bool recapture = false;
+  if (fused_) {  // every scaled bound has changed
+    const int32_t before = vecs_.lowerUniform;
+    const int32_t after = refreshBlockBounds() ? 1 : 0;
+    recapture = before != after;
+  }
+  updMatSeconds_[5] = since(t1);
+
+  if (ud.start_col_value) {
+    setHotStart(ud.start_col_value, ud.start_row_value, ud.start_row_dual);  // (with the new scale vectors)
+  } else {
+    hasStart_ = false;
+    startX_.clear();
+    startY_.clear();
+  }
+
+  t1 = clock::now();
+  stPar_ = graphExec_ && !recapture ? graphPar_ : 0;
+  reset();
+  stalledRounds_ = 0;
+  stalledSince_ = 0;
+  updMatSeconds_[7] = since(t1);
+  t1 = clock::now();
+  if (recapture && graphExec_) {
+    (void)hipGraphExecDestroy(graphExec_);
+    graphExec_ = nullptr;
+    captureGraph();
+  }
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  updMatSeconds_[6] = since(t1);
   setupSeconds_ = since(t0);
 }
 

@@ -8,6 +8,8 @@
 // wave; a thread's P loads are independent of each other and of the branch on the column's origin, and are issued first.
 #include "pdlp_update.hpp"
 
+#include <algorithm>
+
 #include "pdlp_device.hpp"
 #include "pdlp_devfn.hpp"
 
@@ -98,7 +100,79 @@ __global__ __launch_bounds__(kT) void k_update_rows(const double* __restrict__ r
   stStream(rhs + ni, r);
 }
 
+// ---- pdlp_mi355x_update_matrix: refilling a value array of a layout -----------------------------------------------------
+// dst[q] = val[src[q]] (src[q] < 0: a pad slot, stays 0).  A pure stream on the store side — 8 B stored and 4 B of index
+// loaded per slot, unit-stride, non-temporal — and one gathered 8 B load per slot; val is read once per operand, so it is
+// loaded non-temporally too.  Four slots per thread and trip, all index loads, then all gathers, issued before the first
+// store; grid-stride.
+constexpr int kRefillUnroll = 4;
+__global__ __launch_bounds__(kT) void k_refill(const int32_t* __restrict__ src, const double* __restrict__ val, int64_t count,
+                                               int64_t nVal, double* __restrict__ dst) {
+  const int64_t stride = (int64_t)gridDim.x * kT;
+  int64_t q = (int64_t)blockIdx.x * kT + threadIdx.x;
+  for (; q + (kRefillUnroll - 1) * stride < count; q += kRefillUnroll * stride) {
+    int32_t i[kRefillUnroll];
+    double v[kRefillUnroll];
+#pragma unroll
+    for (int k = 0; k < kRefillUnroll; ++k) i[k] = ldStream(src + q + k * stride);
+#pragma unroll
+    for (int k = 0; k < kRefillUnroll; ++k) v[k] = (i[k] >= 0 && (int64_t)i[k] < nVal) ? ldStream(val + i[k]) : 0.0;
+#pragma unroll
+    for (int k = 0; k < kRefillUnroll; ++k) stStream(dst + q + k * stride, v[k]);
+  }
+  for (; q < count; q += stride) {
+    const int32_t i = ldStream(src + q);
+    stStream(dst + q, (i >= 0 && (int64_t)i < nVal) ? ldStream(val + i) : 0.0);
+  }
+}
+
+// Set-up of a matrix-updatable solver: the layouts are built from values that name their own slot (val[q] = q + 1, exact
+// in a double), so every value array of a layout then holds, per slot, where its value came from; 0 = a pad.
+__global__ __launch_bounds__(kT) void k_tag_values(double* val, int64_t count) {
+  for (int64_t q = (int64_t)blockIdx.x * kT + threadIdx.x; q < count; q += (int64_t)gridDim.x * kT) val[q] = (double)(q + 1);
+}
+// src[q] = tag - 1 (through `compose` when given), -1 for pads: slots at or beyond nReal, and anything that is no tag
+__global__ __launch_bounds__(kT) void k_tags_to_source(const double* __restrict__ tags, int64_t count, int64_t nReal, int64_t nVal,
+                                                       const int32_t* __restrict__ compose, int32_t* __restrict__ src,
+                                                       unsigned long long* nTagged) {
+  unsigned long long mine = 0;
+  for (int64_t q = (int64_t)blockIdx.x * kT + threadIdx.x; q < count; q += (int64_t)gridDim.x * kT) {
+    const double t = tags[q];
+    int32_t i = -1;
+    if (q < nReal && t >= 1.0 && t <= (double)nVal && t == (double)(int64_t)t) {
+      i = (int32_t)((int64_t)t - 1);
+      if (compose) i = compose[i];
+      ++mine;
+    }
+    src[q] = i;
+  }
+  if (mine) atomicAdd(nTagged, mine);  // (an integer count: order-free)
+}
+
+inline int gridStride(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + kT - 1) / kT, 256 * 16)); }
+
 }  // namespace
+
+void launchRefill(const int32_t* src, const double* val, int64_t count, int64_t nVal, double* dst, hipStream_t s) {
+  if (count <= 0) return;
+  const int64_t perTrip = (int64_t)kT * kRefillUnroll;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((count + perTrip - 1) / perTrip, 256 * 16));
+  hipLaunchKernelGGL(k_refill, dim3(grid), dim3(kT), 0, s, src, val, count, nVal, dst);
+  PDLP_HIP(hipGetLastError());
+}
+
+void launchTagValues(double* val, int64_t count, hipStream_t s) {
+  if (count <= 0) return;
+  hipLaunchKernelGGL(k_tag_values, dim3(gridStride(count)), dim3(kT), 0, s, val, count);
+  PDLP_HIP(hipGetLastError());
+}
+
+void launchTagsToSource(const double* tags, int64_t count, int64_t nReal, int64_t nVal, const int32_t* compose, int32_t* src,
+                        unsigned long long* nTagged, hipStream_t s) {
+  if (count <= 0) return;
+  hipLaunchKernelGGL(k_tags_to_source, dim3(gridStride(count)), dim3(kT), 0, s, tags, count, nReal, nVal, compose, src, nTagged);
+  PDLP_HIP(hipGetLastError());
+}
 
 void launchUpdateValidate(const double* rowLower, const double* rowUpper, const int32_t* rowKind, int32_t m, int32_t* bad,
                           hipStream_t s) {

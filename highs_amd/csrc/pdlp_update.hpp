@@ -50,4 +50,34 @@ void launchUpdateCols(int32_t mask, const double* colCost, const double* colLowe
 void launchUpdateRows(const double* rowLower, const double* rowUpper, const int32_t* rowKind, const int32_t* rowNewIdx,
                       int32_t m, const double* rsPass, int32_t nPass, double* rhs, hipStream_t s);
 
+
+// ---- pdlp_mi355x_update_matrix (PDLP_UPDATABLE_MATRIX) -----------------------------------------------------------------
+// New matrix VALUES on the pattern the solver was created with.  Of create()'s work only a thin layer looks at the values:
+// the formulated values (sign of <= rows), the scaling passes, matNormInf, the scaled data (every factor changes) and the
+// value arrays of the layouts.  Row order, both transposes, slab partitions and sorts, slab width, XCD map, pacing, task
+// plans and the captured graph depend on the pattern alone and are kept; none of width / map / pacing changes a sum, so
+// whatever a fresh create() would time to, the bits are the same.  A matrix-updatable solver therefore keeps the pattern
+// in both orders, the permutation between them, a SOURCE INDEX per value slot of every layout and the unscaled data
+// (pdlp_setup.hpp MatrixKeep), and an update is: formulate values -> the set-up's own pass loop (gpuScalePasses) -> one
+// refill kernel per value array.  hostReplayMatrixUpdate restates it for the CPU tests.
+
+// F: formulate(P) [+ scale] with keepPasses set and F.cost0 / lower0 / upper0 / rhs0 / qdiag0 holding the unscaled data
+// (keepUnscaled).  Afterwards F is formulate + scale of the problem with a_value and u's data (finalize is the caller's),
+// its passes and unscaled copies are the new ones.  Validates first; throws without touching F.
+void keepUnscaled(StandardForm& F);
+void hostReplayMatrixUpdate(const pdlp_problem_t& P, const double* aValue, const pdlp_update_t* u, bool doScale, StandardForm& F);
+// The checks both sides share: a_value present, num_nz that of create, not all zero (create's wording).  Throw.
+void checkMatrixUpdateShape(const double* aValue, int64_t numNz, int64_t nnzAtCreate);
+[[noreturn]] void throwAllZeroMatrix();
+
+// dst[q] = src[q] >= 0 ? val[src[q]] : 0 for q < count (val has nVal elements; an index outside it counts as a pad)
+void launchRefill(const int32_t* src, const double* val, int64_t count, int64_t nVal, double* dst, hipStream_t s);
+// val[q] = q + 1: values that name their slot, for building the layouts of a matrix-updatable solver
+void launchTagValues(double* val, int64_t count, hipStream_t s);
+// a layout's value array built from tagged values -> its source indices; slots >= nReal are pads (-1); compose (or
+// nullptr): src = compose[tag - 1].  *nTagged (device) += the slots that held a tag: the caller checks that the value
+// arrays of an operand hold every entry exactly as often as the matrix has entries
+void launchTagsToSource(const double* tags, int64_t count, int64_t nReal, int64_t nVal, const int32_t* compose, int32_t* src,
+                        unsigned long long* nTagged, hipStream_t s);
+
 }  // namespace pdlp

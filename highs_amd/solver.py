@@ -44,6 +44,7 @@ EXPORTS = [
     "pdlp_mi355x_read_mps", "pdlp_mi355x_read_mps_timed", "pdlp_mi355x_free_mps_model",
     "pdlp_mi355x_create_wide", "pdlp_mi355x_solve_wide",
     "pdlp_mi355x_update", "pdlp_mi355x_host_prepare_updated",
+    "pdlp_mi355x_update_matrix", "pdlp_mi355x_host_prepare_updated_matrix",
 ]
 
 
@@ -91,6 +92,10 @@ def lib():
         pU = C.POINTER(abi.PdlpUpdate)
         L.pdlp_mi355x_update.argtypes = [H, pU]
         L.pdlp_mi355x_host_prepare_updated.argtypes = [pP, pO, pU, pPrep]
+        L.pdlp_mi355x_update_matrix.argtypes = [H, abi.c_f64p, C.c_int64, pU]
+        L.pdlp_mi355x_host_prepare_updated_matrix.argtypes = [pP, pO, abi.c_f64p, pU, pPrep]
+        # (a test hook outside the public header: host_prepare_updated_matrix with a data update behind it)
+        L.pdlp_mi355x_host_prepare_updated_matrix_then.argtypes = [pP, pO, abi.c_f64p, pU, pU, pPrep]
         L.pdlp_mi355x_free_prepared.restype = None
         L.pdlp_mi355x_row_partition.argtypes = [pPrep, C.c_int32, abi.c_i32p]
         pSlab = C.POINTER(abi.PdlpSlabLayout)
@@ -344,6 +349,29 @@ class DeviceSolver:
                 lp.offset = float(offset)
             self.lp = lp
 
+    def update_matrix(self, a_value, col_cost=None, col_lower=None, col_upper=None, row_lower=None, row_upper=None, offset=None,
+                      start=None):
+        """pdlp_mi355x_update_matrix: new matrix values on the sparsity pattern the solver was created with (a_value in the
+        positions of the problem's a_value; None is passed on as NULL and refused), together with new data and a start as
+        update() takes them, as one change.  Needs a solver created with updatable="matrix"; raises with the library's
+        message when refused (the solver is then unchanged).  self.lp follows as in update()."""
+        data = (col_cost, col_lower, col_upper, row_lower, row_upper, offset, start)
+        U = abi.UpdateHandle(*data) if any(d is not None for d in data) else None
+        a = None if a_value is None else np.ascontiguousarray(a_value, dtype=np.float64)
+        _check(lib().pdlp_mi355x_update_matrix(self.h, None if a is None else a.ctypes.data_as(abi.c_f64p), 0 if a is None else a.size,
+                                               None if U is None else C.byref(U.struct)), "pdlp_mi355x_update_matrix")
+        if self.lp is not None:
+            import copy
+            lp = copy.copy(self.lp)
+            lp.a_value = a.copy()
+            for name, v in (("col_cost", col_cost), ("col_lower", col_lower), ("col_upper", col_upper),
+                            ("row_lower", row_lower), ("row_upper", row_upper)):
+                if v is not None:
+                    setattr(lp, name, np.array(v, dtype=np.float64))
+            if offset is not None:
+                lp.offset = float(offset)
+            self.lp = lp
+
     def solve(self):
         """pdlp_mi355x_run on the held problem, returned as solveLpCupdlp returns it: a family of LPs over one matrix
         is `create once; for each: update, solve`."""
@@ -417,16 +445,25 @@ class SyntheticProblem:
 class Prepared:
     """Host-side standard form built by the PRODUCT library (pdlp_mi355x_host_prepare); numpy copies."""
 
-    def __init__(self, lp=None, params=None, problem_struct=None, slab_long_limit=256, update=None, **options):
+    def __init__(self, lp=None, params=None, problem_struct=None, slab_long_limit=256, update=None, update_matrix=None, **options):
         """update: an abi.UpdateHandle — the form then comes from pdlp_mi355x_host_prepare_updated (the host twin of
-        pdlp_mi355x_update: prepare, keep the scaling passes, replay the update)."""
+        pdlp_mi355x_update: prepare, keep the scaling passes, replay the update).
+        update_matrix: (a_value, abi.UpdateHandle or None) — the form comes from pdlp_mi355x_host_prepare_updated_matrix,
+        the host twin of pdlp_mi355x_update_matrix; with `update` as well, that update follows it on the same form."""
         params = params or abi.default_params(**options)
         keep = None
         if problem_struct is None:
             keep = abi.ProblemHandle(lp)
             problem_struct = keep.struct
         F = abi.PdlpPrepared()
-        if update is None:
+        if update_matrix is not None:
+            a, um = update_matrix
+            a = None if a is None else np.ascontiguousarray(a, dtype=np.float64)
+            _check(lib().pdlp_mi355x_host_prepare_updated_matrix_then(
+                C.byref(problem_struct), C.byref(params), None if a is None else a.ctypes.data_as(abi.c_f64p),
+                None if um is None else C.byref(um.struct), None if update is None else C.byref(update.struct), C.byref(F)),
+                "host_prepare_updated_matrix")
+        elif update is None:
             _check(lib().pdlp_mi355x_host_prepare(C.byref(problem_struct), C.byref(params), C.byref(F)), "host_prepare")
         else:
             _check(lib().pdlp_mi355x_host_prepare_updated(C.byref(problem_struct), C.byref(params), C.byref(update.struct), C.byref(F)),

@@ -127,8 +127,11 @@ typedef struct pdlp_params {
                                  (default 1); G > 1 = the constraint matrix is row-block sharded over the
                                  devices device, device+1, ... device+G-1 of THIS process (one host thread
                                  per device, direct xGMI exchange through peer access) */
-  int32_t updatable;          /* pdlp_mi355x_create: non-zero = the solver takes pdlp_mi355x_update (it then keeps the scale
-                                 factors of every scaling pass and the row kinds in HBM); 0 = nothing is kept */
+  int32_t updatable;          /* pdlp_mi355x_create: a bit mask of PDLP_UPDATABLE_*.  Non-zero = the solver takes
+                                 pdlp_mi355x_update (it then keeps the scale factors of every scaling pass and the row kinds
+                                 in HBM); with PDLP_UPDATABLE_MATRIX it also takes pdlp_mi355x_update_matrix (it then keeps
+                                 the sparsity pattern in both orders, a source index per value slot of its layouts and the
+                                 unscaled data as well: DESIGN.md section 2d has the bytes); 0 = nothing is kept */
   /* --- log sink (HiGHS: highsLogUser).  NULL = stdout, as the reference's cuPDLP-C prints --- */
   void (*log_callback)(void* ctx, int level, const char* text); /* level 1 = summary, 2 = verbose */
   void* log_ctx;
@@ -204,6 +207,24 @@ typedef struct pdlp_update {
   const double* start_col_value; const double* start_row_value; const double* start_row_dual;
 } pdlp_update_t;
 int pdlp_mi355x_update(pdlp_mi355x_solver_t* s, const pdlp_update_t* u);
+
+/* pdlp_params_t.updatable: any non-zero value means PDLP_UPDATABLE_DATA */
+enum { PDLP_UPDATABLE_DATA = 1, PDLP_UPDATABLE_MATRIX = 2 /* implies DATA */ };
+
+/* Re-solve a held LP / diagonal-Hessian QP after the VALUES of its matrix changed, the sparsity pattern kept (through
+ * HiGHS: Highs::changeCoeff on existing entries, then run()).  a_value[num_nz] in the caller's column-wise order, i.e.
+ * the positions of pdlp_problem_t.a_value at create; an explicit 0.0 is a value like any other (create keeps them too).
+ * u may be NULL or carry new costs / bounds / offset / start with the meaning and the checks of pdlp_mi355x_update; both
+ * are applied as ONE change with one reset.  What create() derives from the PATTERN (row order, both orientations, slab
+ * partitions and sorts, slab width, XCD map, pacing, task plans, the captured graph) is kept; what it derives from the
+ * values (signs of <= rows, all scaling passes, the scaled data, max |a_ij|, the value arrays of the layouts) is redone
+ * on the device by the set-up's own kernels.  Afterwards the solver is in the state of a fresh create on the problem
+ * with these values and these data, bit for bit; pdlp_result_t.setup_seconds of the next run is the update's time.
+ *   * Only for solvers created with PDLP_UPDATABLE_MATRIX in pdlp_params_t.updatable, algorithm = 0, not sharded, and
+ *     no off-diagonal Hessian entries (their scaled copy follows the column factors: left for a later change).
+ *   * num_nz must be the count at create, a_value non-NULL and not all zero (create refuses such a matrix).
+ *   * Everything is validated before anything is changed: after a non-zero return the solver is as it was. */
+int pdlp_mi355x_update_matrix(pdlp_mi355x_solver_t* s, const double* a_value, int64_t num_nz, const pdlp_update_t* u);
 
 /* The same two entries with 64-bit column starts (HighsInt = int64_t builds, or any caller whose matrix
  * starts are 64-bit): a_start64[num_col+1] replaces P->a_start, which is ignored and may be NULL; every
@@ -330,6 +351,11 @@ int pdlp_mi355x_host_prepare(const pdlp_problem_t* P, const pdlp_params_t* opt,
  * refused here too) and returns the standard form — which must equal host_prepare of the modified problem bit for bit. */
 int pdlp_mi355x_host_prepare_updated(const pdlp_problem_t* P, const pdlp_params_t* opt, const pdlp_update_t* u,
                                      pdlp_prepared_t* out);
+/* Host restatement of pdlp_mi355x_update_matrix for the CPU tests, as the entry above is for update: prepares P, keeping
+ * the pattern, the passes and the unscaled data, then applies a_value (positions of P->a_value) and u (may be NULL) as the
+ * device does — same validation, same messages. */
+int pdlp_mi355x_host_prepare_updated_matrix(const pdlp_problem_t* P, const pdlp_params_t* opt, const double* a_value,
+                                            const pdlp_update_t* u, pdlp_prepared_t* out);
 void pdlp_mi355x_free_prepared(pdlp_prepared_t* out);
 /* Row-block partition used by create_sharded: offsets[world+1]. */
 int pdlp_mi355x_row_partition(const pdlp_prepared_t* prep, int32_t world,
