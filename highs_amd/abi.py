@@ -107,6 +107,7 @@ class PdlpResult(C.Structure):
 
 
 UPDATABLE_DATA, UPDATABLE_MATRIX = 1, 2  # pdlp_params_t.updatable bits
+UPDATABLE_HESSIAN = 4                    # implies DATA, independent of MATRIX
 
 
 class PdlpUpdate(C.Structure):
@@ -151,6 +152,15 @@ class PdlpPrepared(C.Structure):
         ("row_kind", c_i32p), ("row_new_idx", c_i32p),
         ("norm_cost", C.c_double), ("norm_rhs", C.c_double), ("mat_norm_inf", C.c_double),
         ("spmv_blocks_ax", C.c_int32), ("spmv_blocks_aty", C.c_int32),
+    ]
+
+
+class PdlpPreparedHessian(C.Structure):
+    """pdlp_prepared_hessian_t (include/pdlp_mi355x.h): the scaled Hessian of a prepared form, for the CPU tests."""
+    _fields_ = [
+        ("n", C.c_int32), ("has_diag", C.c_int32),
+        ("nnz_off", C.c_int64),
+        ("qdiag", c_f64p), ("q_beg", c_i32p), ("q_idx", c_i32p), ("q_val", c_f64p),
     ]
 
 
@@ -221,9 +231,16 @@ def default_params(**kw):
             setattr(p, k[5:], int(v))
         elif k == "updatable":
             # "matrix", or an int with UPDATABLE_MATRIX set: PDLP_UPDATABLE_DATA | PDLP_UPDATABLE_MATRIX (pdlp_mi355x_update_matrix
-            # too); any other truthy value: DATA
-            matrix = v == "matrix" if isinstance(v, str) else (not isinstance(v, bool) and isinstance(v, int) and v & UPDATABLE_MATRIX)
-            p.updatable = UPDATABLE_DATA | UPDATABLE_MATRIX if matrix else (UPDATABLE_DATA if v else 0)
+            # too); "hessian" / "matrix+hessian", or an int with UPDATABLE_HESSIAN set: PDLP_UPDATABLE_HESSIAN as well
+            # (pdlp_mi355x_update_values); any other truthy value: DATA
+            if isinstance(v, str):
+                parts = v.split("+")
+                matrix, hessian = "matrix" in parts, "hessian" in parts
+            else:
+                is_mask = not isinstance(v, bool) and isinstance(v, int)
+                matrix, hessian = bool(is_mask and v & UPDATABLE_MATRIX), bool(is_mask and v & UPDATABLE_HESSIAN)
+            p.updatable = ((UPDATABLE_MATRIX if matrix else 0) | (UPDATABLE_HESSIAN if hessian else 0) |
+                           (UPDATABLE_DATA if (v or matrix or hessian) else 0))
         elif k == "device_reduction_order":
             # ORACLE ONLY: sum the reductions in the HIP kernels' order (oracle/pdlp_oracle.c, GPU-ORDER)
             p.reserved[0] = 1 if v else 0

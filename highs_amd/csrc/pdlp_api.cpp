@@ -270,6 +270,14 @@ void solveSharded(const pdlp_problem_t& P, const pdlp_params_t& opt, int G, pdlp
 }
 }  // namespace
 
+int pdlp_mi355x_update_values(pdlp_mi355x_solver_t* s, const double* a_value, int64_t num_nz, const double* q_value, int64_t num_q_nz,
+                              const pdlp_update_t* u) {
+  return guarded([&] {
+    if (!s || !s->impl) throw std::runtime_error("pdlp_mi355x_update_values: null solver");
+    s->impl->updateValues(a_value, num_nz, q_value, num_q_nz, u);
+  });
+}
+
 int pdlp_mi355x_solve(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R) {
   const int G = solveDevices(opt);
   if (G > 1) {
@@ -336,6 +344,8 @@ int pdlp_mi355x_time_kernel(pdlp_mi355x_solver_t* s, const char* kernel, int32_t
 
 namespace {
 // host_prepare, optionally followed by the host restatement of an update (u != nullptr)
+void fillPrepared(const pdlp::StandardForm& F, pdlp_prepared_t* out);
+
 void hostPrepare(const pdlp_problem_t* P, const pdlp_params_t* opt, const pdlp_update_t* u, pdlp_prepared_t* out,
                  const double* aValue = nullptr, const pdlp_update_t* uMatrix = nullptr) {
   memset(out, 0, sizeof(*out));
@@ -354,6 +364,10 @@ void hostPrepare(const pdlp_problem_t* P, const pdlp_params_t* opt, const pdlp_u
     if (u) pdlp::hostReplayUpdate(*u, F);
   }
   pdlp::finalize(F);
+  fillPrepared(F, out);
+}
+
+void fillPrepared(const pdlp::StandardForm& F, pdlp_prepared_t* out) {
   out->n = F.n; out->m = F.m; out->n_eqs = F.nEqs; out->n_orig = F.n0; out->nnz = F.nnz;
   out->csr_beg = dupVec(F.csr.beg); out->csr_idx = dupVec(F.csr.idx); out->csr_val = dupVec(F.csr.val);
   out->csc_beg = dupVec(F.cscSorted.beg); out->csc_idx = dupVec(F.cscSorted.idx); out->csc_val = dupVec(F.cscSorted.val);
@@ -409,6 +423,75 @@ int pdlp_mi355x_host_prepare_updated_matrix_then(const pdlp_problem_t* P, const 
 int pdlp_mi355x_host_prepare_updated_matrix(const pdlp_problem_t* P, const pdlp_params_t* opt, const double* a_value,
                                             const pdlp_update_t* u, pdlp_prepared_t* out) {
   return pdlp_mi355x_host_prepare_updated_matrix_then(P, opt, a_value, u, nullptr, out);
+}
+
+// Host twin of create with the pattern contract of PDLP_UPDATABLE_HESSIAN and of pdlp_mi355x_update_values; u_then (test
+// hook, may be NULL): a pdlp_mi355x_update applied to the result on the same form.
+int pdlp_mi355x_host_prepare_qp_then(const pdlp_problem_t* P, const pdlp_params_t* opt, const double* a_value, const double* q_value,
+                                     const pdlp_update_t* u, const pdlp_update_t* u_then, pdlp_prepared_t* out,
+                                     pdlp_prepared_hessian_t* qout) {
+  return guarded([&] {
+    if (!P || !opt || !out || !qout) throw std::runtime_error("null argument");
+    memset(out, 0, sizeof(*out));
+    memset(qout, 0, sizeof(*qout));
+    const bool change = a_value || q_value || u || u_then;
+    const bool keepQ = (opt->updatable & PDLP_UPDATABLE_HESSIAN) != 0;
+    if (change) {  // the refusals of pdlp_mi355x_update_values that depend on how the solver was created
+      if (opt->algorithm == 1)
+        throw std::runtime_error("pdlp_mi355x_update_values: HiPDLP solvers (algorithm = 1) do not take updates");
+      if (!keepQ)
+        throw std::runtime_error("pdlp_mi355x_update_values: the solver was not created for Hessian updates (pdlp_params_t.updatable "
+                                 "lacks PDLP_UPDATABLE_HESSIAN)");
+      if (a_value && !(opt->updatable & PDLP_UPDATABLE_MATRIX))
+        throw std::runtime_error("pdlp_mi355x_update_values: a_value given, but the solver was not created for matrix updates "
+                                 "(pdlp_params_t.updatable lacks PDLP_UPDATABLE_MATRIX)");
+    }
+    if (opt->algorithm == 1) throw std::runtime_error("pdlp_mi355x_host_prepare_qp: the cuPDLP-C form only (algorithm = 0)");
+    pdlp::StandardForm F;
+    pdlp::formulate(*P, F, keepQ);
+    const bool doScale = !(opt->features_off & PDLP_FEATURE_SCALING_OFF);
+    F.keepPasses = change;
+    if (change) {
+      if (opt->updatable & PDLP_UPDATABLE_MATRIX) pdlp::keepUnscaled(F);
+      pdlp::keepUnscaledHessian(F);
+    }
+    if (doScale) pdlp::scale(F);
+    if (change) {
+      if (q_value) pdlp::checkHessianUpdateShape(q_value, F.hmap.nSlots, F.hmap.kept(), F.hmap.nSlots);
+      if (a_value) {
+        pdlp::hostReplayMatrixUpdate(*P, a_value, u, doScale, F, q_value);
+      } else {
+        static const pdlp_update_t kNoData{};
+        const pdlp_update_t& ud = u ? *u : kNoData;
+        pdlp::checkUpdateShape(ud);
+        if (pdlp::updateMask(ud) & pdlp::kUpdRows) {
+          const int32_t bad = pdlp::firstKindChange(F.rowKind.data(), F.m, ud.row_lower, ud.row_upper);
+          if (bad < F.m) pdlp::throwKindChange(bad, F.rowKind[bad], pdlp::rowKindOf(ud.row_lower[bad], ud.row_upper[bad]));
+        }
+        if (q_value) pdlp::hostReplayHessianUpdate(q_value, F);  // (validates before it writes; u has been validated above)
+        pdlp::hostReplayUpdate(ud, F);
+      }
+      if (u_then) pdlp::hostReplayUpdate(*u_then, F);
+    }
+    pdlp::finalize(F);
+    fillPrepared(F, out);
+    qout->n = F.n;
+    qout->has_diag = F.qdiag.empty() ? 0 : 1;
+    qout->nnz_off = F.qoff.beg.empty() ? 0 : (int64_t)F.qoff.beg[F.n];
+    qout->qdiag = dupVec(F.qdiag);
+    qout->q_beg = dupVec(F.qoff.beg); qout->q_idx = dupVec(F.qoff.idx); qout->q_val = dupVec(F.qoff.val);
+  });
+}
+
+int pdlp_mi355x_host_prepare_qp(const pdlp_problem_t* P, const pdlp_params_t* opt, const double* a_value, const double* q_value,
+                                const pdlp_update_t* u, pdlp_prepared_t* out, pdlp_prepared_hessian_t* qout) {
+  return pdlp_mi355x_host_prepare_qp_then(P, opt, a_value, q_value, u, nullptr, out, qout);
+}
+
+void pdlp_mi355x_free_prepared_hessian(pdlp_prepared_hessian_t* o) {
+  if (!o) return;
+  free(o->qdiag); free(o->q_beg); free(o->q_idx); free(o->q_val);
+  memset(o, 0, sizeof(*o));
 }
 
 void pdlp_mi355x_free_prepared(pdlp_prepared_t* o) {

@@ -85,6 +85,125 @@ bool hessianHasOffDiagonal(const pdlp_problem_t& P) {
   return false;
 }
 
+bool hessianHasOffDiagonalSlot(const pdlp_problem_t& P) {
+  if (P.q_dim <= 0 || !P.q_start || !P.q_index) return false;
+  for (int32_t j = 0; j < P.q_dim; ++j)
+    for (int32_t p = P.q_start[j]; p < P.q_start[j + 1]; ++p)
+      if (P.q_index[p] != j) return true;
+  return false;
+}
+
+// extractHessian's walk over the pattern with every slot kept; each entry carries its caller slot through the sort and
+// the merge of repeated pairs
+void extractHessianPattern(const pdlp_problem_t& P, int32_t n, HessianMap& M, Compressed& off) {
+  M = HessianMap();
+  off = Compressed();
+  if (P.q_dim <= 0 || !P.q_start) return;
+  if (P.q_dim > P.num_col) throw std::runtime_error("Hessian dimension exceeds the number of columns");
+  const int32_t nq = P.q_start[P.q_dim];
+  if (nq > 0 && (!P.q_index || !P.q_value)) throw std::runtime_error("null Hessian arrays");
+  if (nq <= 0) return;
+  std::vector<int32_t> cnt((size_t)n + 1, 0), dcnt((size_t)n + 1, 0);
+  int64_t nRaw = 0;
+  for (int32_t j = 0; j < P.q_dim; ++j)
+    for (int32_t p = P.q_start[j]; p < P.q_start[j + 1]; ++p) {
+      const int32_t i = P.q_index[p];
+      if (i < 0 || i >= P.q_dim) throw std::runtime_error("Hessian index out of range");
+      if (i == j) { ++dcnt[j + 1]; continue; }
+      if (i < j)
+        throw std::runtime_error("pdlp_mi355x: the Hessian must be given by its lower triangle (entry (" + std::to_string(i) + "," +
+                                 std::to_string(j) + ") lies above the diagonal)");
+      ++cnt[i + 1]; ++cnt[j + 1];
+      nRaw += 2;
+    }
+  if (nRaw > 0x7fffffff) throw std::runtime_error("Hessian too large");
+  M.n = n;
+  M.nSlots = nq;
+  for (int32_t r = 0; r < n; ++r) { cnt[r + 1] += cnt[r]; dcnt[r + 1] += dcnt[r]; }
+  std::vector<int32_t> pos(cnt.begin(), cnt.end() - 1);
+  std::vector<int32_t> idx((size_t)nRaw), src((size_t)nRaw);
+  for (int32_t j = 0; j < P.q_dim; ++j)
+    for (int32_t p = P.q_start[j]; p < P.q_start[j + 1]; ++p) {
+      const int32_t i = P.q_index[p];
+      if (i == j) continue;
+      idx[pos[i]] = j; src[pos[i]++] = p;
+    }
+  std::vector<int32_t> tailBeg(pos);
+  for (int32_t j = 0; j < P.q_dim; ++j)
+    for (int32_t p = P.q_start[j]; p < P.q_start[j + 1]; ++p) {
+      const int32_t i = P.q_index[p];
+      if (i == j) continue;
+      idx[pos[j]] = i; src[pos[j]++] = p;
+    }
+  for (int32_t r = 0; r < n; ++r)
+    for (int32_t a = tailBeg[r] + 1; a < cnt[r + 1]; ++a) {
+      const int32_t ci = idx[a], cs = src[a];
+      int32_t b = a - 1;
+      while (b >= tailBeg[r] && idx[b] > ci) { idx[b + 1] = idx[b]; src[b + 1] = src[b]; --b; }
+      idx[b + 1] = ci; src[b + 1] = cs;
+    }
+  // destinations: the n diagonal entries (sources in caller order), then qoff's slots
+  M.dstBeg.assign(dcnt.begin(), dcnt.end());
+  M.srcSlot.assign((size_t)dcnt[n], 0);
+  {
+    std::vector<int32_t> dpos(dcnt.begin(), dcnt.end() - 1);
+    for (int32_t j = 0; j < P.q_dim; ++j)
+      for (int32_t p = P.q_start[j]; p < P.q_start[j + 1]; ++p)
+        if (P.q_index[p] == j) M.srcSlot[dpos[j]++] = p;
+  }
+  if (nRaw == 0) return;
+  off.beg.assign((size_t)n + 1, 0);
+  for (int32_t r = 0; r < n; ++r) {
+    off.beg[r] = (int32_t)off.idx.size();
+    for (int32_t a = cnt[r]; a < cnt[r + 1]; ++a) {
+      if (!(a > cnt[r] && idx[a] == off.idx.back())) {
+        off.idx.push_back(idx[a]);
+        M.offRow.push_back(r);
+        M.offCol.push_back(idx[a]);
+        M.dstBeg.push_back(0);  // (the end of the new destination: set below; its start is the end before it)
+      }
+      M.srcSlot.push_back(src[a]);
+      M.dstBeg.back() = (int32_t)M.srcSlot.size();
+    }
+  }
+  off.beg[n] = (int32_t)off.idx.size();
+  off.val.assign(off.idx.size(), 0.0);
+  M.nOff = (int32_t)off.idx.size();
+}
+
+void assembleHessian(const HessianMap& M, const double* qValue, double sense, double* qdiag, double* qoff) {
+  for (int32_t j = 0; j < M.n; ++j) {
+    double d = 0.0;
+    for (int32_t k = M.dstBeg[j]; k < M.dstBeg[j + 1]; ++k) d += qValue[M.srcSlot[k]] * sense;
+    qdiag[j] = d;
+  }
+  for (int32_t k = 0; k < M.nOff; ++k) {
+    const int32_t b = M.dstBeg[M.n + k], e = M.dstBeg[M.n + k + 1];
+    double v = qValue[M.srcSlot[b]] * sense;
+    for (int32_t a = b + 1; a < e; ++a) v += qValue[M.srcSlot[a]] * sense;
+    qoff[k] = v;
+  }
+}
+
+int32_t firstNegativeDiagonal(const HessianMap& M, const double* qValue, double sense) {
+  for (int32_t j = 0; j < M.n; ++j) {
+    double d = 0.0;
+    for (int32_t k = M.dstBeg[j]; k < M.dstBeg[j + 1]; ++k) d += qValue[M.srcSlot[k]] * sense;
+    if (d < 0.0) return j;
+  }
+  return M.n;
+}
+
+void extractHessianKept(const pdlp_problem_t& P, double sense, int32_t n, std::vector<double>& q, Compressed& off, HessianMap& M) {
+  q.clear();
+  extractHessianPattern(P, n, M, off);
+  if (!M.kept()) return;
+  if (firstNegativeDiagonal(M, P.q_value, sense) < n)
+    throw std::runtime_error("pdlp_mi355x: the Hessian is not positive semidefinite for this objective sense");
+  q.assign((size_t)n, 0.0);
+  assembleHessian(M, P.q_value, sense, q.data(), off.val.data());
+}
+
 void extractHessian(const pdlp_problem_t& P, double sense, int32_t n, std::vector<double>& q, Compressed& off) {
   q.clear();
   off = Compressed();
@@ -167,7 +286,7 @@ void requireConstraints(const pdlp_problem_t& P) {
                              "LPs itself (solveUnconstrainedLp) before the PDLP path");
 }
 
-void formulate(const pdlp_problem_t& P, StandardForm& F) {
+void formulate(const pdlp_problem_t& P, StandardForm& F, bool keepHessianPattern) {
   validateProblem(P);
   const int32_t n0 = P.num_col, m = P.num_row;
   const int64_t nnz0 = n0 > 0 ? P.a_start[n0] : 0;
@@ -224,7 +343,8 @@ void formulate(const pdlp_problem_t& P, StandardForm& F) {
     if (F.lower[j] < -kBoundInf) F.lower[j] = -kInf;
     if (F.upper[j] > kBoundInf) F.upper[j] = kInf;
   }
-  extractHessian(P, F.sense, F.n, F.qdiag, F.qoff);
+  if (keepHessianPattern) extractHessianKept(P, F.sense, F.n, F.qdiag, F.qoff, F.hmap);
+  else extractHessian(P, F.sense, F.n, F.qdiag, F.qoff);
 
   // Matrix in the reference's entry order: per column, equality-type entries
   // first, then inequality entries (LEQ negated) (:413-436); one -1 per slack.

@@ -49,6 +49,18 @@ struct Compressed {
   std::vector<double> val;    // [nnz]
 };
 
+// Hessian-updatable solvers (PDLP_UPDATABLE_HESSIAN, pdlp_update.hpp): where every slot the caller passes in q_value goes.
+// Destination j < n is the diagonal entry of column j, destination n + k is slot k of the row-ordered, both-triangle
+// off-diagonal part; the sources of destination d are srcSlot[dstBeg[d] .. dstBeg[d + 1]), in the order extractHessian adds
+// them up.  The map depends on the PATTERN alone: every slot is kept, explicit zeros included.
+struct HessianMap {
+  int32_t n = 0, nSlots = 0, nOff = 0;   // nSlots = q_start[q_dim]; nOff = slots of qoff (a lower-triangle slot feeds two)
+  std::vector<int32_t> dstBeg;           // [n + nOff + 1]
+  std::vector<int32_t> srcSlot;          // positions in the caller's q_value
+  std::vector<int32_t> offRow, offCol;   // [nOff] major and minor index of every qoff slot
+  bool kept() const { return !dstBeg.empty(); }
+};
+
 struct StandardForm {
   int32_t n = 0;      // columns incl. one slack per BOUND row
   int32_t m = 0;      // rows
@@ -76,6 +88,9 @@ struct StandardForm {
   std::vector<double> csPass, rsPass;
   // Matrix-updatable solvers (pdlp_update.hpp): the unscaled formulated data, taken between formulate() and scale()
   std::vector<double> cost0, lower0, upper0, rhs0, qdiag0;
+  // Hessian-updatable solvers: the assembly map of the kept pattern and the unscaled off-diagonal values (qdiag0 above)
+  HessianMap hmap;
+  std::vector<double> qoff0;
   double offset = 0.0, sense = 1.0;
   double normCost = 0.0, normRhs = 0.0;  // of the unscaled formulated data
   double matNormInf = 0.0;               // max |a_ij| of the (scaled) matrix
@@ -91,7 +106,21 @@ void extractDiagonalHessian(const pdlp_problem_t& P, double sense, int32_t n, st
 // diagonal (for this objective sense) are errors.
 void extractHessian(const pdlp_problem_t& P, double sense, int32_t n, std::vector<double>& qdiag, Compressed& qoff);
 bool hessianHasOffDiagonal(const pdlp_problem_t& P);
-void formulate(const pdlp_problem_t& P, StandardForm& F);
+// The pattern contract of PDLP_UPDATABLE_HESSIAN: every slot the caller passes is kept, explicit zeros included, so the
+// structure depends on the pattern alone.  qdiag exists iff the Hessian has any slot, qoff iff it has an off-diagonal
+// slot; repeated (row, column) pairs are added left to right in extractHessian's order (the same bits as extractHessian
+// wherever the caller passes no explicit zero).  extractHessianPattern builds the map and qoff's beg / idx,
+// assembleHessian is the host restatement of k_hessian_assemble (pdlp_update.hip): the diagonal accumulates from 0.0, an
+// off-diagonal slot takes its first source and adds the rest.  firstNegativeDiagonal: smallest column whose assembled
+// diagonal is negative, or n.
+bool hessianHasOffDiagonalSlot(const pdlp_problem_t& P);
+void extractHessianPattern(const pdlp_problem_t& P, int32_t n, HessianMap& M, Compressed& qoff);
+void assembleHessian(const HessianMap& M, const double* qValue, double sense, double* qdiag, double* qoff);
+int32_t firstNegativeDiagonal(const HessianMap& M, const double* qValue, double sense);
+void extractHessianKept(const pdlp_problem_t& P, double sense, int32_t n, std::vector<double>& qdiag, Compressed& qoff,
+                        HessianMap& M);
+// keepHessianPattern: the pattern contract above; F.hmap is then filled
+void formulate(const pdlp_problem_t& P, StandardForm& F, bool keepHessianPattern = false);
 // The value part of formulate(): csc.val in the reference's entry order from aValue (the positions of P.a_value), with
 // F.rowKind / F.n0 / F.m as formulate() left them.  formulate() calls it; so does the matrix update (pdlp_update.cpp).
 void formulateValues(const int32_t* aStart, const int32_t* aIndex, const double* aValue, StandardForm& F);

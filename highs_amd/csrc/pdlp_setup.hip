@@ -572,11 +572,19 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
   // QP (cuPDLP-C form): the diagonal of Q, with the objective sense, rides along with the column scaling
   {
     std::vector<double> q;
-    extractDiagonalHessian(P, D.sense, n, q);
+    if (D.keepHessianPattern) {
+      Compressed off;
+      extractHessianKept(P, D.sense, n, q, off, D.hmap);
+      if (!off.beg.empty())
+        throw std::runtime_error("pdlp_mi355x: this set-up path takes diagonal Hessians only (off-diagonal entries present)");
+    } else {
+      extractDiagonalHessian(P, D.sense, n, q);
+    }
     if (!q.empty()) {
       D.qdiag.alloc((size_t)n);
       D.qdiag.upload(q.data(), (size_t)n, s);
       PDLP_HIP(hipStreamSynchronize(s));  // q goes out of scope
+      if (D.keepHessianPattern) D.hQdiag0 = std::move(q);
     }
   }
   if (keepM) {  // the unscaled formulated data: new matrix values change every factor, and un-scaling does not give these bits

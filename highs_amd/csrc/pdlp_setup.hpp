@@ -76,6 +76,12 @@ struct DeviceProblem {
   // otherwise frees, both sort permutations and the unscaled data
   bool keepMatrix = false;
   MatrixKeep keep;
+  // PDLP_UPDATABLE_HESSIAN (set keepHessianPattern before gpuPrepare; cuPDLP-C form only): the Hessian is extracted with
+  // every slot kept (pdlp_host.hpp extractHessianKept); its assembly map and the unscaled diagonal stay on the host for
+  // the solver to take
+  bool keepHessianPattern = false;
+  HessianMap hmap;
+  std::vector<double> hQdiag0;
 };
 
 // Options of the HiPDLP form (pdlp_host.hpp formulateHipdlp / scaleHipdlp); nullptr = cuPDLP-C form.

@@ -471,7 +471,9 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   const int64_t nnzIn = P.num_col > 0 && P.a_start ? (int64_t)P.a_start[P.num_col] : 0;
   gpuSetup_ = nnzIn >= 200000;
   if (sw_.gpuSetup >= 0) gpuSetup_ = sw_.gpuSetup != 0;
-  hasQoff_ = hessianHasOffDiagonal(P);
+  // PDLP_UPDATABLE_HESSIAN: every slot of the Hessian the caller passes is kept, so the structure follows the pattern
+  const bool keepQPattern = (opt_.updatable & PDLP_UPDATABLE_HESSIAN) != 0;
+  hasQoff_ = keepQPattern ? hessianHasOffDiagonalSlot(P) : hessianHasOffDiagonal(P);
   if (hasQoff_) gpuSetup_ = false;  // the off-diagonal part of Q is scaled with the columns on the host (pdlp_host.cpp applyScaling)
   // sharded: every rank still prepares the WHOLE problem (Ruiz scaling couples all rows and columns) but does it on
   // its device and copies the result back once; only the row-block cut and the upload of its shard stay on the host
@@ -480,12 +482,15 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   const bool doScale = !(opt_.features_off & PDLP_FEATURE_SCALING_OFF);
   updatable_ = opt_.updatable != 0 && !sharded_;  // (a sharded solver refuses updates: nothing to keep)
   // new matrix values on the kept pattern (pdlp_update.hpp).  Not for a Hessian with an off-diagonal part: its scaled copy
-  // follows the column factors (pdlp_mi355x_update_matrix says so when asked)
-  matrixUpdatable_ = updatable_ && (opt_.updatable & PDLP_UPDATABLE_MATRIX) != 0 && !hasQoff_;
+  // follows the column factors (pdlp_mi355x_update_matrix says so when asked) — unless the solver is Hessian-updatable, which
+  // keeps what rescales it (pdlp_update.hpp)
+  hessianUpdatable_ = updatable_ && keepQPattern;
+  matrixUpdatable_ = updatable_ && (opt_.updatable & PDLP_UPDATABLE_MATRIX) != 0 && (!hasQoff_ || hessianUpdatable_);
   nnzIn_ = nnzIn;
   DeviceProblem devProb;
   devProb.keepPasses = updatable_;
   devProb.keepMatrix = matrixUpdatable_;
+  devProb.keepHessianPattern = keepQPattern;
   F_.keepPasses = updatable_;
   if (gpuSetup_) {
     // formulate + scale + both orientations on the device; F_ keeps only the host-side bookkeeping
@@ -502,6 +507,10 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
     sumRhs2_ = devProb.sumRhs2;
     if (updatable_) keepForUpdates(&devProb);
     if (matrixUpdatable_) mk_ = std::move(devProb.keep);
+    if (hessianUpdatable_) {
+      F_.hmap = std::move(devProb.hmap);
+      keepHessian(devProb.hQdiag0, std::vector<double>());
+    }
   } else if (shardedGpuSetup) {
     gpuPrepare(P, doScale, stream_, devProb);
     sumCost2_ = devProb.sumCost2;
@@ -529,12 +538,14 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
       devProb = DeviceProblem();  // released before any exchange kernel of another rank can run on this device
     }
   } else {
-    formulate(P, F_);
+    formulate(P, F_, keepQPattern);
     F_.keepPasses = updatable_;  // (formulate starts from a fresh form)
     if (matrixUpdatable_) keepUnscaled(F_);
+    if (hessianUpdatable_) keepUnscaledHessian(F_);
     if (doScale) scale(F_);
     finalize(F_);
     if (updatable_) keepForUpdates(nullptr);
+    if (hessianUpdatable_) keepHessian(F_.qdiag0, F_.qoff0);
     if (matrixUpdatable_) keepMatrixFromHost(P);
     sumCost2_ = 0.0;
     for (double v : F_.cost) sumCost2_ += v * v;
@@ -749,6 +760,62 @@ void Solver::keepForUpdates(DeviceProblem* D) {
   F_.rsPass = std::vector<double>();
 }
 
+// Hessian-updatable solver: the assembly map (F_.hmap, built on the host in both set-up paths) and the unscaled Hessian go
+// to HBM.  A solver created without a Hessian keeps nothing and refuses q_value later.
+void Solver::keepHessian(const std::vector<double>& qdiag0, const std::vector<double>& qoff0) {
+  const HessianMap& M = F_.hmap;
+  if (!M.kept()) return;
+  hk_.nSlots = M.nSlots;
+  hk_.nOff = M.nOff;
+  auto put = [&](DeviceArray<int32_t>& d, const std::vector<int32_t>& h) { d.alloc(std::max<size_t>(h.size(), 1)); d.upload(h.data(), h.size(), stream_); };
+  auto putD = [&](DeviceArray<double>& d, const std::vector<double>& h) { d.alloc(std::max<size_t>(h.size(), 1)); d.upload(h.data(), h.size(), stream_); };
+  put(hk_.dstBeg, M.dstBeg);
+  put(hk_.srcSlot, M.srcSlot);
+  put(hk_.offRow, M.offRow);
+  put(hk_.offCol, M.offCol);
+  if (!matrixUpdatable_) putD(hk_.qdiag0, qdiag0);  // (else mk_.qdiag0 holds it: qdiag0Dev)
+  if (M.nOff > 0) {
+    putD(hk_.qoff0, qoff0);
+    hk_.qoffScaled.alloc((size_t)M.nOff);
+  }
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  F_.hmap = HessianMap();  // (the host copies are released; F_.qdiag0 is keepMatrixFromHost's to release)
+  F_.qoff0 = std::vector<double>();
+  if (!matrixUpdatable_) F_.qdiag0 = std::vector<double>();
+}
+
+// dQ_ has just been built from tagged values (value of qoff slot k = k + 1): its value arrays become their source
+// indices, counted as finishMatrixKeep counts those of A and A', and are filled for the first time.
+void Solver::finishHessianKeep(const std::vector<double>& qoffScaled) {
+  const int64_t nOff = hk_.nOff;
+  DeviceArray<unsigned long long> tagged;
+  tagged.alloc(1);
+  tagged.zero(stream_);
+  auto extract = [&](const DeviceArray<double>& v, DeviceArray<int32_t>& src) {
+    if (v.size() == 0) throw std::runtime_error("pdlp_mi355x: a layout's value array without its pad element (Hessian-updatable set-up)");
+    src.alloc(v.size());
+    launchTagsToSource(v.get(), (int64_t)v.size(), (int64_t)v.size() - 1, nOff, nullptr, src.get(), tagged.get(), stream_);
+  };
+  extract(dQ_.val, srcQVal_);
+  if (dQ_.useSlab) extract(dQ_.slabVal, srcQSlab_);
+  unsigned long long found = 0;
+  tagged.download(&found, 1, stream_);
+  hk_.qoffScaled.upload(qoffScaled.data(), (size_t)nOff, stream_);
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  if ((int64_t)found != nOff)
+    throw std::runtime_error("pdlp_mi355x: the layouts of a Hessian-updatable solver hold " + std::to_string(found) +
+                             " tagged values of the off-diagonal Hessian, which has " + std::to_string(nOff) +
+                             " slots (a layout build no longer copies values slot for slot)");
+  refillHessian();
+  PDLP_HIP(hipStreamSynchronize(stream_));
+}
+
+void Solver::refillHessian() {
+  const double* v = hk_.qoffScaled.get();
+  launchRefill(srcQVal_.get(), v, (int64_t)srcQVal_.size(), hk_.nOff, dQ_.val.get(), stream_);
+  if (dQ_.useSlab) launchRefill(srcQSlab_.get(), v, (int64_t)srcQSlab_.size(), hk_.nOff, dQ_.slabVal.get(), stream_);
+}
+
 // Matrix-updatable solver prepared on the host: the pattern of both orders, the permutation between them and the unscaled
 // data go to HBM in the arrays the device-side set-up keeps (pdlp_setup.hpp MatrixKeep), so that the update itself is the
 // same device code for both.  The permutations are those of finalize()'s counting transposes.
@@ -914,6 +981,11 @@ void Solver::uploadProblem() {
       qb.idx.assign(F_.qoff.idx.begin() + b, F_.qoff.idx.begin() + e);
       qb.val.assign(F_.qoff.val.begin() + b, F_.qoff.val.begin() + e);
       dQ_.upload(qb, nLoc_, n, sw_, stream_);
+    } else if (hessianUpdatable_) {  // values that name their slot, as for A and A' (finishMatrixKeep)
+      const std::vector<double> scaled = F_.qoff.val;
+      for (size_t q = 0; q < F_.qoff.val.size(); ++q) F_.qoff.val[q] = (double)(q + 1);
+      dQ_.upload(F_.qoff, n, n, sw_, stream_);
+      finishHessianKeep(scaled);
     } else {  // one GPU, and the RCCL exchange: every rank steps all n columns, so it keeps the whole N
       dQ_.upload(F_.qoff, n, n, sw_, stream_);
     }
@@ -2158,6 +2230,7 @@ std::pair<double*, int64_t> Solver::lookup(const std::string& name) {
   if (name == "row_scale") return {rowScale_.get(), m};
   if (name == "slack_pos") return {slackPos_.get(), n};
   if (name == "slack_neg") return {slackNeg_.get(), n};
+  if (qdiag_.size() && name == "qdiag") return {qdiag_.get(), n};
   if (hasQoff_ && name == "nx") return {nx_[c].get(), n};
   if (hasQoff_ && name == "nx_next") return {nx_[u].get(), n};
   throw std::runtime_error("unknown vector name: " + name);
@@ -2253,6 +2326,17 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     put(4, (double)(mk_.bytes() + sizeof(int32_t) * (srcAVal_.size() + srcASlab_.size() + srcAtVal_.size() + srcAtSlab_.size()) +
                     sizeof(double) * updMat_.size()));
     put(5, matrixUpdatable_ ? 1.0 : 0.0);
+    // [6] bytes of HBM a Hessian-updatable solver keeps on top of [0] and [4] (PDLP_UPDATABLE_HESSIAN: the assembly map,
+    // row and column of every off-diagonal slot, the unscaled and the scaled off-diagonal values, a source index per
+    // value slot of the N operand, staging of q_value once a Hessian update has run), [7] 1 = it is one
+    put(6, (double)(hk_.bytes() + sizeof(int32_t) * (srcQVal_.size() + srcQSlab_.size()) + sizeof(double) * updQ_.size()));
+    put(7, hessianUpdatable_ ? 1.0 : 0.0);
+  } else if (name == "update_values_seconds") {  // the Hessian's parts of the last pdlp_mi355x_update_values: upload +
+    // validation, assembly, replay, refill of the N operand; [4] 1 = that update (or the last update of any kind) captured
+    // the trial graph again; [5] = the whole update.  The data / matrix parts are in update_seconds / update_matrix_seconds
+    for (int k = 0; k < 4; ++k) put(k, updHessSeconds_[k]);
+    put(4, (double)updRecaptured_);
+    put(5, setupSeconds_);
   } else if (name == "update_matrix_seconds") {  // the parts of the last pdlp_mi355x_update_matrix: upload + validation, formulate,
     // scaling passes, refills, norms + sums, per-block bounds, graph capture, reset; [8] = the whole update
     for (int k = 0; k < 8; ++k) put(k, updMatSeconds_[k]);

@@ -114,6 +114,8 @@ class SolverBase {
   virtual void update(const pdlp_update_t& u);
   // pdlp_mi355x_update_matrix; likewise
   virtual void updateMatrix(const double* aValue, int64_t numNz, const pdlp_update_t* u);
+  // pdlp_mi355x_update_values; likewise
+  virtual void updateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t* u);
 };
 
 class Solver : public SolverBase {
@@ -132,6 +134,8 @@ class Solver : public SolverBase {
   double timeKernel(const std::string& name, int32_t reps) override;
   void update(const pdlp_update_t& u) override;  // pdlp_update.cpp
   void updateMatrix(const double* aValue, int64_t numNz, const pdlp_update_t* u) override;  // pdlp_update.cpp
+  void updateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz,
+                    const pdlp_update_t* u) override;  // pdlp_update.cpp
 
  private:
   // setup
@@ -152,6 +156,15 @@ class Solver : public SolverBase {
   void keepMatrixFromHost(const pdlp_problem_t& P);
   void finishMatrixKeep();
   void refillOperands();
+  // Hessian-updatable solvers (pdlp_update.hpp): the assembly map and the unscaled Hessian into hk_; dQ_'s source indices
+  // out of its tagged build and the first refill; the parts of an update
+  void keepHessian(const std::vector<double>& qdiag0, const std::vector<double>& qoff0);
+  void finishHessianKeep(const std::vector<double>& qoffScaled);
+  void refillHessian();
+  void stageHessian(const double* qValue);
+  void applyHessian(bool assemble, bool replayDiag);
+  void updateImpl(const pdlp_update_t& u, const double* qValue);
+  void updateMatrixImpl(const double* aValue, int64_t numNz, const pdlp_update_t* u, const double* qValue);
   bool refreshBlockBounds();              // fused slab trial: colBlockUni_ / colBlockBounds_ from lower_ / upper_; returns allLower
   // hot loop
   void enqueueTrial();
@@ -259,6 +272,25 @@ class Solver : public SolverBase {
   DeviceArray<int32_t> srcAVal_, srcASlab_, srcAtVal_, srcAtSlab_;
   DeviceArray<double> updMat_;
   double updMatSeconds_[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // upload + validation, formulate, scaling passes, refills, norms + sums, block bounds, graph capture, reset
+  // Hessian-updatable solvers (PDLP_UPDATABLE_HESSIAN): the assembly map from the caller's q_value slots (HessianMap), row
+  // and column of every qoff slot, the unscaled Hessian (the diagonal lives in mk_.qdiag0 when the solver is matrix-
+  // updatable as well), the scaled off-diagonal values dQ_ is refilled from, and per value array of dQ_'s layouts the qoff
+  // slot every value slot is filled from.  updQ_: staging of the caller's q_value (allocated by the first Hessian update).
+  bool hessianUpdatable_ = false;
+  struct HessianKeep {
+    int32_t nSlots = 0, nOff = 0;
+    DeviceArray<int32_t> dstBeg, srcSlot, offRow, offCol;
+    DeviceArray<double> qdiag0, qoff0, qoffScaled;
+    size_t bytes() const {
+      return sizeof(int32_t) * (dstBeg.size() + srcSlot.size() + offRow.size() + offCol.size()) +
+             sizeof(double) * (qdiag0.size() + qoff0.size() + qoffScaled.size());
+    }
+  } hk_;
+  double* qdiag0Dev() { return matrixUpdatable_ ? mk_.qdiag0.get() : hk_.qdiag0.get(); }
+  DeviceArray<int32_t> srcQVal_, srcQSlab_;
+  DeviceArray<double> updQ_;
+  double updHessSeconds_[4] = {0, 0, 0, 0};  // upload + validation, assembly, replay, refill of dQ_ (stage "update_values_seconds")
+  int32_t updRecaptured_ = 0;                // 1 = the last update captured the trial graph again
   double updSeconds_[6] = {0, 0, 0, 0, 0, 0};  // upload + validation, kernels, norms + sums, block bounds, graph capture, reset
   int32_t barrierFallbacks_ = 0, smallLaunches_ = 0;
   unsigned long long smallSeq_ = 0;  // persistent launches since gridBar_ was zeroed (their roll call counts cumulatively)

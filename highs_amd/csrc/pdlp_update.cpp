@@ -122,7 +122,59 @@ void checkMatrixUpdateShape(const double* aValue, int64_t numNz, int64_t nnzAtCr
                              "create a new solver)");
 }
 
-void hostReplayMatrixUpdate(const pdlp_problem_t& P, const double* aValue, const pdlp_update_t* u, bool doScale, StandardForm& F) {
+void keepUnscaledHessian(StandardForm& F) {
+  F.qdiag0 = F.qdiag;
+  F.qoff0 = F.qoff.val;
+}
+
+void checkHessianUpdateShape(const double* qValue, int64_t numQNz, bool hasHessian, int64_t slotsAtCreate) {
+  if (!qValue) {
+    if (numQNz != 0)
+      throw std::runtime_error("pdlp_mi355x_update_values: q_value is NULL but num_q_nz = " + std::to_string(numQNz));
+    return;
+  }
+  if (!hasHessian)
+    throw std::runtime_error("pdlp_mi355x_update_values: q_value given to a solver that was created without a Hessian (the "
+                             "sparsity pattern is fixed: create a new solver)");
+  if (numQNz != slotsAtCreate)
+    throw std::runtime_error("pdlp_mi355x_update_values: num_q_nz = " + std::to_string(numQNz) + " differs from the " +
+                             std::to_string(slotsAtCreate) + " Hessian slots the solver was created with (the sparsity pattern is "
+                             "fixed: create a new solver)");
+}
+
+void throwNegativeDiagonal(int32_t col) {
+  throw std::runtime_error("pdlp_mi355x_update_values: the Hessian is not positive semidefinite for this objective sense (the "
+                           "diagonal entry of column " + std::to_string(col) + " is negative)");
+}
+
+void hostAssembleHessianUpdate(const double* qValue, StandardForm& F, bool validateOnly) {
+  if (!F.hmap.kept() || F.qdiag0.size() != (size_t)F.n || F.qoff0.size() != (size_t)F.hmap.nOff)
+    throw std::runtime_error("pdlp_mi355x_update_values: the form did not keep its Hessian");
+  const int32_t bad = firstNegativeDiagonal(F.hmap, qValue, F.sense);
+  if (bad < F.n) throwNegativeDiagonal(bad);
+  if (validateOnly) return;
+  assembleHessian(F.hmap, qValue, F.sense, F.qdiag0.data(), F.qoff0.data());
+}
+
+void hostReplayHessianUpdate(const double* qValue, StandardForm& F) {
+  if (!F.keepPasses) throw std::runtime_error("pdlp_mi355x_update_values: the form did not keep its scaling passes");
+  hostAssembleHessianUpdate(qValue, F, false);
+  const int32_t n = F.n;
+  for (int32_t j = 0; j < n; ++j) {  // as k_hessian_replay takes them
+    double d = F.qdiag0[j];
+    for (int32_t p = 0; p < F.nPass; ++p) { const double cs = F.csPass[(size_t)p * n + j]; d = (d / cs) / cs; }
+    F.qdiag[j] = d;
+  }
+  for (int32_t k = 0; k < F.hmap.nOff; ++k) {
+    const int32_t r = F.hmap.offRow[k], c = F.hmap.offCol[k];
+    double v = F.qoff0[k];
+    for (int32_t p = 0; p < F.nPass; ++p) v = (v / F.csPass[(size_t)p * n + r]) / F.csPass[(size_t)p * n + c];
+    F.qoff.val[k] = v;
+  }
+}
+
+void hostReplayMatrixUpdate(const pdlp_problem_t& P, const double* aValue, const pdlp_update_t* u, bool doScale, StandardForm& F,
+                            const double* qValue) {
   const int64_t nnz0 = F.n0 > 0 ? (int64_t)P.a_start[F.n0] : 0;
   if (!aValue) throw std::runtime_error("pdlp_mi355x_update_matrix: a_value is NULL");
   if (!F.keepPasses || F.cost0.size() != F.cost.size())
@@ -137,9 +189,12 @@ void hostReplayMatrixUpdate(const pdlp_problem_t& P, const double* aValue, const
   bool anyNonzero = false;
   for (int64_t p = 0; p < nnz0 && !anyNonzero; ++p) anyNonzero = aValue[p] != 0.0;
   if (!anyNonzero) throwAllZeroMatrix();
+  if (qValue) hostAssembleHessianUpdate(qValue, F, true);
   // ---- nothing below is refused ----
   formulateValues(P.a_start, P.a_index, aValue, F);
+  if (qValue) hostAssembleHessianUpdate(qValue, F, false);
   F.cost = F.cost0; F.lower = F.lower0; F.upper = F.upper0; F.rhs = F.rhs0; F.qdiag = F.qdiag0;
+  if (F.hmap.kept() && F.hmap.nOff > 0) F.qoff.val = F.qoff0;  // (a Hessian-updatable form: scale() below takes the off-diagonal part along)
   F.colScale.assign((size_t)F.n, 1.0);
   F.rowScale.assign((size_t)F.m, 1.0);
   F.nPass = 0;
@@ -158,10 +213,17 @@ void SolverBase::updateMatrix(const double*, int64_t, const pdlp_update_t*) {
   throw std::runtime_error("pdlp_mi355x_update_matrix: HiPDLP solvers (algorithm = 1) do not take updates");
 }
 
+void SolverBase::updateValues(const double*, int64_t, const double*, int64_t, const pdlp_update_t*) {
+  throw std::runtime_error("pdlp_mi355x_update_values: HiPDLP solvers (algorithm = 1) do not take updates");
+}
+
 // The held solver is brought to the state of a fresh create() on the modified problem.  Everything that can be refused
 // is refused before the first write to the solver's vectors: the caller's row bounds go to a staging buffer, the
 // validation kernel reads only that and the kept kinds.
-void Solver::update(const pdlp_update_t& u) {
+void Solver::update(const pdlp_update_t& u) { updateImpl(u, nullptr); }
+
+// qValue (or nullptr): new Hessian values as well (pdlp_mi355x_update_values without a_value; the count is checked there)
+void Solver::updateImpl(const pdlp_update_t& u, const double* qValue) {
   using clock = std::chrono::steady_clock;
   const auto t0 = clock::now();
   auto since = [](clock::time_point a) { return std::chrono::duration<double>(clock::now() - a).count(); };
@@ -196,6 +258,7 @@ void Solver::update(const pdlp_update_t& u) {
     PDLP_HIP(hipStreamSynchronize(stream_));
     if (bad < m) throwKindChange(bad, F_.rowKind[bad], rowKindOf(u.row_lower[bad], u.row_upper[bad]));
   }
+  if (qValue) stageHessian(qValue);
   // ---- nothing below is refused ----
   if (mask & kUpdCost) put(dCost, u.col_cost, n0);
   if (mask & kUpdColLower) put(dColLo, u.col_lower, n0);
@@ -216,6 +279,8 @@ void Solver::update(const pdlp_update_t& u) {
   }
   PDLP_HIP(hipStreamSynchronize(stream_));
   updSeconds_[1] = since(t1);
+  // the Hessian: assembled from the staging copy, taken through the kept passes (the matrix, so every factor, stays)
+  if (qValue) applyHessian(true, true);
 
   // termination norms of the unscaled data and the left-to-right sums of the scaled c, b (PDHG_Init_Step_Sizes), by the
   // host loops of the set-up
@@ -273,7 +338,80 @@ void Solver::update(const pdlp_update_t& u) {
   }
   PDLP_HIP(hipStreamSynchronize(stream_));
   updSeconds_[4] = since(t1);
+  updRecaptured_ = recapture && graphExec_ ? 1 : 0;
   setupSeconds_ = since(t0);
+}
+
+// pdlp_mi355x_update_values: a_value, q_value and u, each optional, as ONE change.  The refusals that depend on how the
+// solver was created come first; the rest is the data update or the matrix update with the Hessian's part in it.
+void Solver::updateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t* u) {
+  if (sharded_)
+    throw std::runtime_error("pdlp_mi355x_update_values: sharded solvers (pdlp_mi355x_create_sharded) do not take updates");
+  if (!(opt_.updatable & PDLP_UPDATABLE_HESSIAN))
+    throw std::runtime_error("pdlp_mi355x_update_values: the solver was not created for Hessian updates (pdlp_params_t.updatable "
+                             "lacks PDLP_UPDATABLE_HESSIAN)");
+  if (!aValue && numNz != 0)
+    throw std::runtime_error("pdlp_mi355x_update_values: a_value is NULL but num_nz = " + std::to_string(numNz));
+  if (aValue && !(opt_.updatable & PDLP_UPDATABLE_MATRIX))
+    throw std::runtime_error("pdlp_mi355x_update_values: a_value given, but the solver was not created for matrix updates "
+                             "(pdlp_params_t.updatable lacks PDLP_UPDATABLE_MATRIX)");
+  checkHessianUpdateShape(qValue, numQNz, hk_.nSlots > 0, hk_.nSlots);
+  updHessSeconds_[0] = updHessSeconds_[1] = updHessSeconds_[2] = updHessSeconds_[3] = 0.0;
+  if (aValue) {
+    updateMatrixImpl(aValue, numNz, u, qValue);
+  } else {
+    static const pdlp_update_t kNoData{};
+    updateImpl(u ? *u : kNoData, qValue);
+  }
+}
+
+// The caller's q_value into its staging buffer and the validation kernel on it: nothing of the solver is written.
+void Solver::stageHessian(const double* qValue) {
+  using clock = std::chrono::steady_clock;
+  const auto t0 = clock::now();
+  const int32_t n = F_.n;
+  if (updQ_.size() == 0) updQ_.alloc((size_t)hk_.nSlots);
+  if (updBad_.size() == 0) updBad_.alloc(1);
+  PDLP_HIP(hipMemcpyAsync(updQ_.get(), qValue, sizeof(double) * (size_t)hk_.nSlots, hipMemcpyHostToDevice, stream_));
+  int32_t bad = n;
+  PDLP_HIP(hipMemcpyAsync(updBad_.get(), &bad, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  launchHessianValidate(hk_.dstBeg.get(), hk_.srcSlot.get(), updQ_.get(), F_.sense, n, updBad_.get(), stream_);
+  PDLP_HIP(hipMemcpyAsync(&bad, updBad_.get(), sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  updHessSeconds_[0] = std::chrono::duration<double>(clock::now() - t0).count();
+  if (bad < n) throwNegativeDiagonal(bad);
+}
+
+// assemble: qdiag0 / qoff0 from the staged q_value.  replayDiag: qdiag_ from qdiag0 through the kept passes (a matrix
+// update leaves the diagonal to its scaling passes instead).  Always: the off-diagonal part through csPass_ as it stands,
+// and dQ_'s value arrays refilled from it.
+void Solver::applyHessian(bool assemble, bool replayDiag) {
+  using clock = std::chrono::steady_clock;
+  auto since = [](clock::time_point a) { return std::chrono::duration<double>(clock::now() - a).count(); };
+  const int32_t n = F_.n, nOff = hk_.nOff;
+  double* qdiag0 = qdiag0Dev();
+  auto t1 = clock::now();
+  if (assemble) {
+    launchHessianAssemble(hk_.dstBeg.get(), hk_.srcSlot.get(), updQ_.get(), F_.sense, n, nOff, qdiag0, hk_.qoff0.get(), stream_);
+    PDLP_HIP(hipStreamSynchronize(stream_));
+    updHessSeconds_[1] = since(t1);
+  }
+  t1 = clock::now();
+  const double* diagSrc = replayDiag ? qdiag0 : nullptr;
+  const double* offSrc = nOff > 0 ? hk_.qoff0.get() : nullptr;
+  if (F_.scaled) {
+    launchHessianReplay(diagSrc, offSrc, hk_.offRow.get(), hk_.offCol.get(), n, nOff, csPass_.get(), nPass_, qdiag_.get(),
+                        hk_.qoffScaled.get(), stream_);
+  } else {  // (PDLP_FEATURE_SCALING_OFF: nothing is replayed)
+    if (diagSrc) PDLP_HIP(hipMemcpyAsync(qdiag_.get(), diagSrc, sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, stream_));
+    if (offSrc) PDLP_HIP(hipMemcpyAsync(hk_.qoffScaled.get(), offSrc, sizeof(double) * (size_t)nOff, hipMemcpyDeviceToDevice, stream_));
+  }
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  updHessSeconds_[2] = since(t1);
+  t1 = clock::now();
+  if (nOff > 0) refillHessian();
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  updHessSeconds_[3] = since(t1);
 }
 
 // pdlp_mi355x_update_matrix: new matrix values on the kept pattern, optionally with new data (u), as ONE change.  Of
@@ -282,6 +420,12 @@ void Solver::update(const pdlp_update_t& u) {
 // (none of them changes a sum).  Validation first: the caller's values and row bounds go to staging buffers that nothing
 // else reads.
 void Solver::updateMatrix(const double* aValue, int64_t numNz, const pdlp_update_t* u) {
+  // on a Hessian-updatable solver this is pdlp_mi355x_update_values without q_value (a NULL a_value stays refused)
+  if ((opt_.updatable & PDLP_UPDATABLE_HESSIAN) && !sharded_ && aValue) return updateValues(aValue, numNz, nullptr, 0, u);
+  updateMatrixImpl(aValue, numNz, u, nullptr);
+}
+
+void Solver::updateMatrixImpl(const double* aValue, int64_t numNz, const pdlp_update_t* u, const double* qValue) {
   using clock = std::chrono::steady_clock;
   const auto t0 = clock::now();
   auto since = [](clock::time_point a) { return std::chrono::duration<double>(clock::now() - a).count(); };
@@ -290,7 +434,7 @@ void Solver::updateMatrix(const double* aValue, int64_t numNz, const pdlp_update
   if (!(opt_.updatable & PDLP_UPDATABLE_MATRIX))
     throw std::runtime_error("pdlp_mi355x_update_matrix: the solver was not created for matrix updates (pdlp_params_t.updatable "
                              "lacks PDLP_UPDATABLE_MATRIX)");
-  if (hasQoff_)
+  if (hasQoff_ && !hessianUpdatable_)
     throw std::runtime_error("pdlp_mi355x_update_matrix: QPs whose Hessian has off-diagonal entries do not take matrix updates "
                              "(the scaled copy of the Hessian follows the column factors; left for a later change)");
   if (!matrixUpdatable_) throw std::runtime_error("pdlp_mi355x_update_matrix: the solver kept nothing for matrix updates");
@@ -328,6 +472,7 @@ void Solver::updateMatrix(const double* aValue, int64_t numNz, const pdlp_update
     if (bad < m) throwKindChange(bad, F_.rowKind[bad], rowKindOf(ud.row_lower[bad], ud.row_upper[bad]));
   }
   if (gpuAbsMax(updMat_.get(), nnz0, stream_) == 0.0) throwAllZeroMatrix();  // (a NaN among the values is not zero, as for create)
+  if (qValue) stageHessian(qValue);
   // ---- nothing below is refused ----
   if (mask & kUpdCost) put(dCost, ud.col_cost, n0);
   if (mask & kUpdColLower) put(dColLo, ud.col_lower, n0);
@@ -339,6 +484,8 @@ void Solver::updateMatrix(const double* aValue, int64_t numNz, const pdlp_update
   // with what u gives (the replay kernels with no pass), copied into the solver's vectors
   auto t1 = clock::now();
   MatrixKeep& K = mk_;
+  if (qValue) launchHessianAssemble(hk_.dstBeg.get(), hk_.srcSlot.get(), updQ_.get(), F_.sense, n, hk_.nOff, K.qdiag0.get(),
+                                    hk_.qoff0.get(), stream_);
   gpuFormulateValues(K.aStart.get(), K.aIndex.get(), updMat_.get(), rowKindDev_.get(), rowNewIdxDev_.get(), n0, m, nnz0, nnz - nnz0,
                      K.cscVal.get(), stream_);
   launchRefill(K.permA.get(), K.cscVal.get(), nnz, nnz, K.aVal.get(), stream_);
@@ -372,6 +519,9 @@ void Solver::updateMatrix(const double* aValue, int64_t numNz, const pdlp_update
     nPass_ = gpuScalePasses(o, stream_);
   }
   updMatSeconds_[2] = since(t1);
+
+  // the off-diagonal part of the Hessian through the NEW factors (the diagonal rode along with the passes, as in create)
+  if (hessianUpdatable_ && hk_.nOff > 0) applyHessian(false, false);
 
   t1 = clock::now();
   refillOperands();
@@ -430,6 +580,7 @@ void Solver::updateMatrix(const double* aValue, int64_t numNz, const pdlp_update
   }
   PDLP_HIP(hipStreamSynchronize(stream_));
   updMatSeconds_[6] = since(t1);
+  updRecaptured_ = recapture && graphExec_ ? 1 : 0;
   setupSeconds_ = since(t0);
 }
 

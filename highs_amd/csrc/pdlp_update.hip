@@ -149,6 +149,88 @@ __global__ __launch_bounds__(kT) void k_tags_to_source(const double* __restrict_
   if (mine) atomicAdd(nTagged, mine);  // (an integer count: order-free)
 }
 
+// ---- pdlp_mi355x_update_values: new Hessian values on the kept pattern (pdlp_update.hpp) -------------------------------------
+// The assembly map (pdlp_host.hpp HessianMap) is a compact CSR over destinations: j < n the diagonal of column j, n + k
+// slot k of qoff.  Sums run in extractHessian's order, one thread per destination, so there is nothing to reduce.
+
+// smallest column whose assembled diagonal is negative (the caller sets bad[0] = n first); reads the staging copy only
+__global__ __launch_bounds__(kT) void k_hessian_validate(const int32_t* __restrict__ dstBeg, const int32_t* __restrict__ srcSlot,
+                                                         const double* __restrict__ qValue, double sense, int n, int32_t* bad) {
+  const int j = blockIdx.x * kT + threadIdx.x;
+  if (j >= n) return;
+  const int b = ldStream(dstBeg + j), e = ldStream(dstBeg + j + 1);
+  double d = 0.0;
+  for (int k = b; k < e; ++k) d += qValue[srcSlot[k]] * sense;
+  if (d < 0.0) atomicMin(bad, j);
+}
+
+// Gathered loads of q_value (a slot is read once or twice: no reuse worth a cache line's stay), unit-stride non-temporal
+// stores.  The diagonal accumulates from 0.0; an off-diagonal slot takes its first source and adds the rest.
+__global__ __launch_bounds__(kT) void k_hessian_assemble(const int32_t* __restrict__ dstBeg, const int32_t* __restrict__ srcSlot,
+                                                         const double* __restrict__ qValue, double sense, int n, int nDst,
+                                                         double* __restrict__ qdiag0, double* __restrict__ qoff0) {
+  const int d = blockIdx.x * kT + threadIdx.x;
+  if (d >= nDst) return;
+  const int b = ldStream(dstBeg + d), e = ldStream(dstBeg + d + 1);
+  if (d < n) {
+    double acc = 0.0;
+    for (int k = b; k < e; ++k) acc += ldStream(qValue + srcSlot[k]) * sense;
+    stStream(qdiag0 + d, acc);
+  } else if (b < e) {  // (every off-diagonal destination has a source: the map is built from the slots)
+    double acc = ldStream(qValue + srcSlot[b]) * sense;
+    for (int k = b + 1; k < e; ++k) acc += ldStream(qValue + srcSlot[k]) * sense;
+    stStream(qoff0 + (d - n), acc);
+  }
+}
+
+// The scaling passes replayed on the unscaled Hessian: the operations of applyScaling (pdlp_host.cpp) and k_apply_cols
+// (pdlp_setup.hip), one pass at a time.  Blocks [0, diagBlocks) take the diagonal — d = (d / cs_p[j]) / cs_p[j], the factor
+// unit-stride across the wave — the rest the off-diagonal slots — v = (v / cs_p[row]) / cs_p[col], two gathered 8-byte
+// loads per pass.  NP as in k_update_cols: all factor loads in flight before the first division.
+template <int NP>
+__global__ __launch_bounds__(kT) void k_hessian_replay(const double* __restrict__ qdiag0, const double* __restrict__ qoff0,
+                                                       const int32_t* __restrict__ offRow, const int32_t* __restrict__ offCol, int n,
+                                                       int nOff, int diagBlocks, const double* __restrict__ csPass, int nPass,
+                                                       double* __restrict__ qdiag, double* __restrict__ qoff) {
+  if ((int)blockIdx.x < diagBlocks) {
+    const int j = blockIdx.x * kT + threadIdx.x;
+    if (j >= n) return;
+    double f[NP > 0 ? NP : 1];
+    if (NP > 0) {
+#pragma unroll
+      for (int p = 0; p < NP; ++p) f[p] = ldStream(csPass + (size_t)p * (size_t)n + j);
+    }
+    double d = ldStream(qdiag0 + j);
+    if (NP > 0) {
+#pragma unroll
+      for (int p = 0; p < NP; ++p) d = (d / f[p]) / f[p];
+    } else {
+      for (int p = 0; p < nPass; ++p) {
+        const double cs = ldStream(csPass + (size_t)p * (size_t)n + j);
+        d = (d / cs) / cs;
+      }
+    }
+    stStream(qdiag + j, d);
+  } else {
+    const int k = ((int)blockIdx.x - diagBlocks) * kT + threadIdx.x;
+    if (k >= nOff) return;
+    const int r = ldStream(offRow + k), c = ldStream(offCol + k);  // (0 <= r, c < n: indices of the formulated columns)
+    double fr[NP > 0 ? NP : 1], fc[NP > 0 ? NP : 1];
+    if (NP > 0) {
+#pragma unroll
+      for (int p = 0; p < NP; ++p) { fr[p] = csPass[(size_t)p * (size_t)n + r]; fc[p] = csPass[(size_t)p * (size_t)n + c]; }
+    }
+    double v = ldStream(qoff0 + k);
+    if (NP > 0) {
+#pragma unroll
+      for (int p = 0; p < NP; ++p) v = (v / fr[p]) / fc[p];
+    } else {
+      for (int p = 0; p < nPass; ++p) v = (v / csPass[(size_t)p * (size_t)n + r]) / csPass[(size_t)p * (size_t)n + c];
+    }
+    stStream(qoff + k, v);
+  }
+}
+
 inline int gridStride(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + kT - 1) / kT, 256 * 16)); }
 
 }  // namespace
@@ -171,6 +253,36 @@ void launchTagsToSource(const double* tags, int64_t count, int64_t nReal, int64_
                         unsigned long long* nTagged, hipStream_t s) {
   if (count <= 0) return;
   hipLaunchKernelGGL(k_tags_to_source, dim3(gridStride(count)), dim3(kT), 0, s, tags, count, nReal, nVal, compose, src, nTagged);
+  PDLP_HIP(hipGetLastError());
+}
+
+void launchHessianValidate(const int32_t* dstBeg, const int32_t* srcSlot, const double* qValue, double sense, int32_t n,
+                           int32_t* bad, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_hessian_validate, dim3(gridFor(n)), dim3(kT), 0, s, dstBeg, srcSlot, qValue, sense, n, bad);
+  PDLP_HIP(hipGetLastError());
+}
+
+void launchHessianAssemble(const int32_t* dstBeg, const int32_t* srcSlot, const double* qValue, double sense, int32_t n,
+                           int32_t nOff, double* qdiag0, double* qoff0, hipStream_t s) {
+  const int64_t nDst = (int64_t)n + nOff;
+  if (nDst <= 0) return;
+  hipLaunchKernelGGL(k_hessian_assemble, dim3(gridFor(nDst)), dim3(kT), 0, s, dstBeg, srcSlot, qValue, sense, n, (int)nDst, qdiag0,
+                     qoff0);
+  PDLP_HIP(hipGetLastError());
+}
+
+void launchHessianReplay(const double* qdiag0, const double* qoff0, const int32_t* offRow, const int32_t* offCol, int32_t n,
+                         int32_t nOff, const double* csPass, int32_t nPass, double* qdiag, double* qoff, hipStream_t s) {
+  const int diagBlocks = qdiag0 ? gridFor(n) : 0, offBlocks = qoff0 ? gridFor(nOff) : 0;
+  if (diagBlocks + offBlocks <= 0) return;
+  const dim3 grid(diagBlocks + offBlocks);
+  if (nPass == kSetupPasses)
+    hipLaunchKernelGGL(k_hessian_replay<kSetupPasses>, grid, dim3(kT), 0, s, qdiag0, qoff0, offRow, offCol, n, nOff, diagBlocks, csPass,
+                       nPass, qdiag, qoff);
+  else
+    hipLaunchKernelGGL(k_hessian_replay<0>, grid, dim3(kT), 0, s, qdiag0, qoff0, offRow, offCol, n, nOff, diagBlocks, csPass, nPass,
+                       qdiag, qoff);
   PDLP_HIP(hipGetLastError());
 }
 

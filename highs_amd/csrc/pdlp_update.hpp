@@ -65,7 +65,9 @@ void launchUpdateRows(const double* rowLower, const double* rowUpper, const int3
 // (keepUnscaled).  Afterwards F is formulate + scale of the problem with a_value and u's data (finalize is the caller's),
 // its passes and unscaled copies are the new ones.  Validates first; throws without touching F.
 void keepUnscaled(StandardForm& F);
-void hostReplayMatrixUpdate(const pdlp_problem_t& P, const double* aValue, const pdlp_update_t* u, bool doScale, StandardForm& F);
+// qValue (or nullptr): new Hessian values as well, for a form that also kept its Hessian (keepUnscaledHessian)
+void hostReplayMatrixUpdate(const pdlp_problem_t& P, const double* aValue, const pdlp_update_t* u, bool doScale, StandardForm& F,
+                            const double* qValue = nullptr);
 // The checks both sides share: a_value present, num_nz that of create, not all zero (create's wording).  Throw.
 void checkMatrixUpdateShape(const double* aValue, int64_t numNz, int64_t nnzAtCreate);
 [[noreturn]] void throwAllZeroMatrix();
@@ -79,5 +81,37 @@ void launchTagValues(double* val, int64_t count, hipStream_t s);
 // arrays of an operand hold every entry exactly as often as the matrix has entries
 void launchTagsToSource(const double* tags, int64_t count, int64_t nReal, int64_t nVal, const int32_t* compose, int32_t* src,
                         unsigned long long* nTagged, hipStream_t s);
+
+
+// ---- pdlp_mi355x_update_values (PDLP_UPDATABLE_HESSIAN) -----------------------------------------------------------------
+// New Hessian VALUES on the pattern the solver was created with, alone or together with new matrix values and data.  The
+// scale factors come from the matrix alone, so with the matrix unchanged a new Q is brought into scaled form by replaying
+// the kept column factors of every pass — q_jj -> (q_jj / cs_p[j]) / cs_p[j], q_ij -> (q_ij / cs_p[i]) / cs_p[j], the
+// operations applyScaling does — with no scaling pass, no norm, no layout build and the captured graph kept.  When the
+// matrix changes too, the same replay with the NEW factors rescales the off-diagonal part (the diagonal rides along with
+// the passes as in create).  A Hessian-updatable solver keeps: the assembly map from the caller's slots to the diagonal
+// and the row-ordered both-triangle off-diagonal part (pdlp_host.hpp HessianMap), qoff's row and column per slot, the
+// unscaled qdiag0 / qoff0, and a source index per value slot of dQ_'s layouts (by the tagged-values construction of the
+// matrix update).  hostReplayHessianUpdate restates the Hessian-only case for the CPU tests; with a matrix update the
+// Hessian goes through hostReplayMatrixUpdate's scale().
+void keepUnscaledHessian(StandardForm& F);  // F.qdiag0, F.qoff0 from a form made by formulate(P, F, true), before scale()
+// q_value present iff counted, count that of create, a solver with a Hessian.  Throws.
+void checkHessianUpdateShape(const double* qValue, int64_t numQNz, bool hasHessian, int64_t slotsAtCreate);
+[[noreturn]] void throwNegativeDiagonal(int32_t col);
+// validates (negative diagonal), then F.qdiag0 / F.qoff0 / F.qdiag / F.qoff.val become those of the new values, scaled
+// by the kept passes.  Throws without touching F.
+void hostReplayHessianUpdate(const double* qValue, StandardForm& F);
+// the same validation and assembly into F.qdiag0 / F.qoff0 only (the matrix update's scale() does the rest)
+void hostAssembleHessianUpdate(const double* qValue, StandardForm& F, bool validateOnly);
+
+// bad[0] = min(bad[0], smallest column whose assembled diagonal is negative); the caller sets bad[0] = n first
+void launchHessianValidate(const int32_t* dstBeg, const int32_t* srcSlot, const double* qValue, double sense, int32_t n,
+                           int32_t* bad, hipStream_t s);
+// qdiag0[j] / qoff0[k] from the caller's slots times sense, summed in extractHessian's order
+void launchHessianAssemble(const int32_t* dstBeg, const int32_t* srcSlot, const double* qValue, double sense, int32_t n,
+                           int32_t nOff, double* qdiag0, double* qoff0, hipStream_t s);
+// qdiag = qdiag0 and qoff = qoff0 taken through the nPass passes csPass[p * n + .]; a part whose source is nullptr is skipped
+void launchHessianReplay(const double* qdiag0, const double* qoff0, const int32_t* offRow, const int32_t* offCol, int32_t n,
+                         int32_t nOff, const double* csPass, int32_t nPass, double* qdiag, double* qoff, hipStream_t s);
 
 }  // namespace pdlp

@@ -45,6 +45,7 @@ EXPORTS = [
     "pdlp_mi355x_create_wide", "pdlp_mi355x_solve_wide",
     "pdlp_mi355x_update", "pdlp_mi355x_host_prepare_updated",
     "pdlp_mi355x_update_matrix", "pdlp_mi355x_host_prepare_updated_matrix",
+    "pdlp_mi355x_update_values", "pdlp_mi355x_host_prepare_qp", "pdlp_mi355x_free_prepared_hessian",
 ]
 
 
@@ -97,6 +98,13 @@ def lib():
         # (a test hook outside the public header: host_prepare_updated_matrix with a data update behind it)
         L.pdlp_mi355x_host_prepare_updated_matrix_then.argtypes = [pP, pO, abi.c_f64p, pU, pU, pPrep]
         L.pdlp_mi355x_free_prepared.restype = None
+        pQ = C.POINTER(abi.PdlpPreparedHessian)
+        L.pdlp_mi355x_update_values.argtypes = [H, abi.c_f64p, C.c_int64, abi.c_f64p, C.c_int64, pU]
+        L.pdlp_mi355x_host_prepare_qp.argtypes = [pP, pO, abi.c_f64p, abi.c_f64p, pU, pPrep, pQ]
+        # (a test hook outside the public header: host_prepare_qp with a data update behind it)
+        L.pdlp_mi355x_host_prepare_qp_then.argtypes = [pP, pO, abi.c_f64p, abi.c_f64p, pU, pU, pPrep, pQ]
+        L.pdlp_mi355x_free_prepared_hessian.argtypes = [pQ]
+        L.pdlp_mi355x_free_prepared_hessian.restype = None
         L.pdlp_mi355x_row_partition.argtypes = [pPrep, C.c_int32, abi.c_i32p]
         pSlab = C.POINTER(abi.PdlpSlabLayout)
         L.pdlp_mi355x_host_slab_layout.argtypes = [pPrep, C.c_int32, C.c_int32, pSlab]
@@ -372,6 +380,36 @@ class DeviceSolver:
                 lp.offset = float(offset)
             self.lp = lp
 
+    def update_values(self, a_value=None, q_value=None, col_cost=None, col_lower=None, col_upper=None, row_lower=None,
+                      row_upper=None, offset=None, start=None):
+        """pdlp_mi355x_update_values: new Hessian values (q_value in the positions of the problem's Hessian values) and / or
+        new matrix values (a_value, as update_matrix takes them), together with new data and a start as update() takes
+        them, as one change.  None = unchanged.  Needs a solver created with updatable="hessian" (or "matrix+hessian" for
+        a_value); raises with the library's message when refused (the solver is then unchanged).  self.lp follows as in
+        update(), its hessian included."""
+        data = (col_cost, col_lower, col_upper, row_lower, row_upper, offset, start)
+        U = abi.UpdateHandle(*data) if any(d is not None for d in data) else None
+        a = None if a_value is None else np.ascontiguousarray(a_value, dtype=np.float64)
+        q = None if q_value is None else np.ascontiguousarray(q_value, dtype=np.float64)
+        _check(lib().pdlp_mi355x_update_values(self.h, None if a is None else a.ctypes.data_as(abi.c_f64p), 0 if a is None else a.size,
+                                               None if q is None else q.ctypes.data_as(abi.c_f64p), 0 if q is None else q.size,
+                                               None if U is None else C.byref(U.struct)), "pdlp_mi355x_update_values")
+        if self.lp is not None:
+            import copy
+            lp = copy.copy(self.lp)
+            if a is not None:
+                lp.a_value = a.copy()
+            if q is not None:
+                hess = lp.hessian
+                lp.hessian = (hess[0], hess[1], q.copy())
+            for name, v in (("col_cost", col_cost), ("col_lower", col_lower), ("col_upper", col_upper),
+                            ("row_lower", row_lower), ("row_upper", row_upper)):
+                if v is not None:
+                    setattr(lp, name, np.array(v, dtype=np.float64))
+            if offset is not None:
+                lp.offset = float(offset)
+            self.lp = lp
+
     def solve(self):
         """pdlp_mi355x_run on the held problem, returned as solveLpCupdlp returns it: a family of LPs over one matrix
         is `create once; for each: update, solve`."""
@@ -440,6 +478,39 @@ class SyntheticProblem:
             self.close()
         except Exception:
             pass
+
+
+def host_prepare_qp(lp, a_value=None, q_value=None, update=None, update_then=None, params=None, **options):
+    """pdlp_mi355x_host_prepare_qp: the host twin of a Hessian-updatable create (a_value, q_value and update all None) and
+    of pdlp_mi355x_update_values.  update / update_then: abi.UpdateHandle or None (update_then: a pdlp_mi355x_update
+    applied afterwards on the same form).  Returns (form, hessian): two dicts with every field of pdlp_prepared_t and
+    pdlp_prepared_hessian_t as numpy copies / numbers."""
+    params = params or abi.default_params(**options)
+    keep = abi.ProblemHandle(lp)
+    F, Q = abi.PdlpPrepared(), abi.PdlpPreparedHessian()
+    a = None if a_value is None else np.ascontiguousarray(a_value, dtype=np.float64)
+    q = None if q_value is None else np.ascontiguousarray(q_value, dtype=np.float64)
+    _check(lib().pdlp_mi355x_host_prepare_qp_then(
+        C.byref(keep.struct), C.byref(params), None if a is None else a.ctypes.data_as(abi.c_f64p),
+        None if q is None else q.ctypes.data_as(abi.c_f64p), None if update is None else C.byref(update.struct),
+        None if update_then is None else C.byref(update_then.struct), C.byref(F), C.byref(Q)), "host_prepare_qp")
+    g = lambda p, k, dt: np.ctypeslib.as_array(p, shape=(max(k, 1),))[:k].astype(dt).copy() if p else np.zeros(0, dtype=dt)
+    n, m, nnz = F.n, F.m, F.nnz
+    form = dict(
+        n=n, m=m, n_eqs=F.n_eqs, n_orig=F.n_orig, nnz=nnz,
+        csr_beg=g(F.csr_beg, m + 1, np.int32), csr_idx=g(F.csr_idx, nnz, np.int32), csr_val=g(F.csr_val, nnz, np.float64),
+        csc_beg=g(F.csc_beg, n + 1, np.int32), csc_idx=g(F.csc_idx, nnz, np.int32), csc_val=g(F.csc_val, nnz, np.float64),
+        cost=g(F.cost, n, np.float64), rhs=g(F.rhs, m, np.float64), lower=g(F.lower, n, np.float64), upper=g(F.upper, n, np.float64),
+        col_scale=g(F.col_scale, n, np.float64), row_scale=g(F.row_scale, m, np.float64),
+        row_kind=g(F.row_kind, m, np.int32), row_new_idx=g(F.row_new_idx, m, np.int32),
+        norm_cost=F.norm_cost, norm_rhs=F.norm_rhs, mat_norm_inf=F.mat_norm_inf,
+        spmv_blocks_ax=F.spmv_blocks_ax, spmv_blocks_aty=F.spmv_blocks_aty)
+    no = Q.nnz_off
+    hess = dict(n=Q.n, has_diag=Q.has_diag, nnz_off=no, qdiag=g(Q.qdiag, Q.n if Q.has_diag else 0, np.float64),
+                q_beg=g(Q.q_beg, Q.n + 1 if no else 0, np.int32), q_idx=g(Q.q_idx, no, np.int32), q_val=g(Q.q_val, no, np.float64))
+    lib().pdlp_mi355x_free_prepared(C.byref(F))
+    lib().pdlp_mi355x_free_prepared_hessian(C.byref(Q))
+    return form, hess
 
 
 class Prepared:

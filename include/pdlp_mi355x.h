@@ -131,7 +131,9 @@ typedef struct pdlp_params {
                                  pdlp_mi355x_update (it then keeps the scale factors of every scaling pass and the row kinds
                                  in HBM); with PDLP_UPDATABLE_MATRIX it also takes pdlp_mi355x_update_matrix (it then keeps
                                  the sparsity pattern in both orders, a source index per value slot of its layouts and the
-                                 unscaled data as well: DESIGN.md section 2d has the bytes); 0 = nothing is kept */
+                                 unscaled data as well: DESIGN.md section 2d has the bytes); with PDLP_UPDATABLE_HESSIAN it
+                                 takes new Hessian values through pdlp_mi355x_update_values and keeps EVERY Hessian slot the
+                                 caller passes; 0 = nothing is kept */
   /* --- log sink (HiGHS: highsLogUser).  NULL = stdout, as the reference's cuPDLP-C prints --- */
   void (*log_callback)(void* ctx, int level, const char* text); /* level 1 = summary, 2 = verbose */
   void* log_ctx;
@@ -182,8 +184,8 @@ int pdlp_mi355x_create(const pdlp_problem_t* P, const pdlp_params_t* opt,
 int pdlp_mi355x_run(pdlp_mi355x_solver_t* s, pdlp_result_t* R);
 void pdlp_mi355x_destroy(pdlp_mi355x_solver_t* s);
 
-/* Re-solve a held LP / QP after its costs, column bounds, row bounds or offset changed — the matrix, the Hessian,
- * the sense, the sizes and the options stay.  Everything create() derives from the MATRIX (scale factors, row order,
+/* Re-solve a held LP / QP after its costs, column bounds, row bounds or offset changed — the matrix, the Hessian (new
+ * Hessian values go through pdlp_mi355x_update_values below), the sense, the sizes and the options stay.  Everything create() derives from the MATRIX (scale factors, row order,
  * slack columns, both orientations, slab layouts, tuning, the captured trial graph) is kept; the new data are brought
  * into the scaled standard form on the device by replaying the scale factors of every scaling pass in order, which
  * gives exactly the bits a fresh pdlp_mi355x_create on the modified problem has.
@@ -209,7 +211,11 @@ typedef struct pdlp_update {
 int pdlp_mi355x_update(pdlp_mi355x_solver_t* s, const pdlp_update_t* u);
 
 /* pdlp_params_t.updatable: any non-zero value means PDLP_UPDATABLE_DATA */
-enum { PDLP_UPDATABLE_DATA = 1, PDLP_UPDATABLE_MATRIX = 2 /* implies DATA */ };
+enum {
+  PDLP_UPDATABLE_DATA = 1,
+  PDLP_UPDATABLE_MATRIX = 2, /* implies DATA */
+  PDLP_UPDATABLE_HESSIAN = 4 /* implies DATA; independent of MATRIX */
+};
 
 /* Re-solve a held LP / diagonal-Hessian QP after the VALUES of its matrix changed, the sparsity pattern kept (through
  * HiGHS: Highs::changeCoeff on existing entries, then run()).  a_value[num_nz] in the caller's column-wise order, i.e.
@@ -221,10 +227,36 @@ enum { PDLP_UPDATABLE_DATA = 1, PDLP_UPDATABLE_MATRIX = 2 /* implies DATA */ };
  * on the device by the set-up's own kernels.  Afterwards the solver is in the state of a fresh create on the problem
  * with these values and these data, bit for bit; pdlp_result_t.setup_seconds of the next run is the update's time.
  *   * Only for solvers created with PDLP_UPDATABLE_MATRIX in pdlp_params_t.updatable, algorithm = 0, not sharded, and
- *     no off-diagonal Hessian entries (their scaled copy follows the column factors: left for a later change).
+ *     no off-diagonal Hessian entries (their scaled copy follows the column factors) — unless the solver also has
+ *     PDLP_UPDATABLE_HESSIAN, which keeps what rescales them: the call is then
+ *     pdlp_mi355x_update_values(s, a_value, num_nz, NULL, 0, u).
  *   * num_nz must be the count at create, a_value non-NULL and not all zero (create refuses such a matrix).
  *   * Everything is validated before anything is changed: after a non-zero return the solver is as it was. */
 int pdlp_mi355x_update_matrix(pdlp_mi355x_solver_t* s, const double* a_value, int64_t num_nz, const pdlp_update_t* u);
+
+/* Re-solve a held QP after the VALUES of its Hessian changed, the sparsity pattern kept (through HiGHS: Highs::passHessian
+ * on the same pattern, then run()) — a risk-aversion sweep, a re-estimated covariance, the Hessian of an SQP subproblem —
+ * alone or together with new matrix values and new data, all applied as ONE change with one reset.
+ *   * a_value == NULL (with num_nz == 0): the matrix is unchanged; else as pdlp_mi355x_update_matrix takes it (needs
+ *     PDLP_UPDATABLE_MATRIX as well; a QP WITH off-diagonal Hessian entries is accepted here).
+ *   * q_value == NULL (with num_q_nz == 0): the Hessian is unchanged; else q_value[num_q_nz] in the positions of
+ *     pdlp_problem_t.q_value at create, num_q_nz == q_start[q_dim] at create.
+ *   * u may be NULL, or carry data and a start with the meaning and the checks of pdlp_mi355x_update.
+ * The scale factors come from the matrix alone, so with the matrix unchanged the new Hessian is brought into scaled form by
+ * replaying the kept column factors of every pass: no scaling pass, no norm, no layout build, and the captured trial graph
+ * stays.  With a_value the matrix update runs as above and the same replay, with the NEW factors, rescales the Hessian.
+ * THE PATTERN CONTRACT.  A solver created with PDLP_UPDATABLE_HESSIAN keeps every Hessian slot the caller passes, explicit
+ * zeros included (as a_value's are kept): its diagonal term exists iff the Hessian has any slot, its off-diagonal operand
+ * iff the pattern has an off-diagonal slot; repeated (row, column) pairs are added left to right as always.  Without the
+ * bit create drops zero values as before.  So a Hessian-updatable create differs from a plain one only where the caller
+ * passes explicit zeros.
+ *   * Only for solvers created with PDLP_UPDATABLE_HESSIAN, algorithm = 0, not sharded, and (for q_value) with a Hessian.
+ *   * A diagonal that is negative after the objective sense is refused, with create's words and the smallest such column.
+ *   * Everything is validated before anything is changed: after a non-zero return the solver is as it was.
+ *   * Afterwards the solver is in the state of a fresh create on the modified problem with the same updatable bits, bit for
+ *     bit; pdlp_result_t.setup_seconds of the next run is the update's time. */
+int pdlp_mi355x_update_values(pdlp_mi355x_solver_t* s, const double* a_value, int64_t num_nz, const double* q_value,
+                              int64_t num_q_nz, const pdlp_update_t* u);
 
 /* The same two entries with 64-bit column starts (HighsInt = int64_t builds, or any caller whose matrix
  * starts are 64-bit): a_start64[num_col+1] replaces P->a_start, which is ignored and may be NULL; every
@@ -271,7 +303,7 @@ int pdlp_mi355x_iterate(pdlp_mi355x_solver_t* s, int32_t n_iters,
 /* Device vector access by name for kernel-level parity tests. Names:
  * "x","y","ax","aty" (current iterate), "x_next","y_next","ax_next","aty_next",
  * "x_avg","y_avg","ax_avg","aty_avg","x_sum","y_sum","cost","rhs","lower",
- * "upper","col_scale","row_scale","slack_pos","slack_neg".
+ * "upper","col_scale","row_scale","slack_pos","slack_neg"; QP solvers also "qdiag" (the scaled diagonal of Q, length n).
  * len must equal the vector's length (n or m). */
 int pdlp_mi355x_get_vector(pdlp_mi355x_solver_t* s, const char* name,
                            double* host, int64_t len);
@@ -357,6 +389,22 @@ int pdlp_mi355x_host_prepare_updated(const pdlp_problem_t* P, const pdlp_params_
 int pdlp_mi355x_host_prepare_updated_matrix(const pdlp_problem_t* P, const pdlp_params_t* opt, const double* a_value,
                                             const pdlp_update_t* u, pdlp_prepared_t* out);
 void pdlp_mi355x_free_prepared(pdlp_prepared_t* out);
+/* Host twin of a Hessian-updatable create and of pdlp_mi355x_update_values, for the CPU tests.  a_value, q_value and u all
+ * NULL: a plain prepare of P (with the pattern contract iff opt->updatable has PDLP_UPDATABLE_HESSIAN).  Otherwise P is
+ * prepared keeping what the device keeps and the change is applied as the device applies it — same validation, same
+ * messages.  *qout receives the scaled Hessian of the form: its diagonal (has_diag = 0: none) and its off-diagonal part
+ * with both triangles, by rows with ascending column.  Arrays are malloc'ed by the library; release with
+ * pdlp_mi355x_free_prepared / pdlp_mi355x_free_prepared_hessian. */
+typedef struct pdlp_prepared_hessian {
+  int32_t n, has_diag;
+  int64_t nnz_off;
+  double* qdiag;           /* [n] or NULL */
+  int32_t *q_beg, *q_idx;  /* [n+1], [nnz_off] or NULL */
+  double* q_val;
+} pdlp_prepared_hessian_t;
+int pdlp_mi355x_host_prepare_qp(const pdlp_problem_t* P, const pdlp_params_t* opt, const double* a_value, const double* q_value,
+                                const pdlp_update_t* u, pdlp_prepared_t* out, pdlp_prepared_hessian_t* qout);
+void pdlp_mi355x_free_prepared_hessian(pdlp_prepared_hessian_t* out);
 /* Row-block partition used by create_sharded: offsets[world+1]. */
 int pdlp_mi355x_row_partition(const pdlp_prepared_t* prep, int32_t world,
                               int32_t* offsets);
