@@ -127,6 +127,37 @@ class PdlpUpdate(C.Structure):
     ]
 
 
+# pdlp_session_info_t.path / .changed (include/pdlp_mi355x.h)
+SESSION_NONE, SESSION_CREATE, SESSION_UPDATE, SESSION_UPDATE_MATRIX, SESSION_UPDATE_VALUES, SESSION_ONE_SHOT = range(6)
+SESSION_PATH_NAME = {0: "none", 1: "create", 2: "update", 3: "update matrix", 4: "update values", 5: "one-shot"}
+CHANGED_PATTERN, CHANGED_MATRIX_VALUES, CHANGED_HESSIAN_PATTERN, CHANGED_HESSIAN_VALUES = 1, 2, 4, 8
+CHANGED_COST, CHANGED_COL_LOWER, CHANGED_COL_UPPER, CHANGED_ROW_BOUNDS, CHANGED_OFFSET = 16, 32, 64, 128, 256
+CHANGED_RUNTIME_OPTIONS, CHANGED_STRUCTURAL_OPTIONS, CHANGED_SHAPE = 512, 1024, 2048
+
+
+class PdlpSessionInfo(C.Structure):
+    """pdlp_session_info_t (include/pdlp_mi355x.h): what the last pdlp_mi355x_session_solve found and did; its size is
+    checked against pdlp_mi355x_session_info_size()."""
+    _fields_ = [
+        ("path", C.c_int32),
+        ("changed", C.c_int32),
+        ("kind_row", C.c_int32),
+        ("kind_was", C.c_int32),
+        ("kind_now", C.c_int32),
+        ("reserved", C.c_int32),
+        ("diff_seconds", C.c_double),
+        ("upload_seconds", C.c_double),
+        ("apply_seconds", C.c_double),
+        ("setup_seconds", C.c_double),
+        ("held_bytes", C.c_int64),
+        ("reason", C.c_char * 160),
+    ]
+
+    @property
+    def text(self):
+        return self.reason.decode()
+
+
 class PdlpIterStats(C.Structure):
     _fields_ = [
         ("iters", C.c_int32),

@@ -14,12 +14,17 @@
 
 #include "pdlp_halpern.hpp"
 #include "pdlp_mps.hpp"
+#include "pdlp_session.hpp"
 #include "pdlp_solver.hpp"
 #include "pdlp_update.hpp"
 #include "pdlp_detmath.h"
 
 struct pdlp_mi355x_solver {
   pdlp::SolverBase* impl;
+};
+
+struct pdlp_mi355x_session {
+  pdlp::Session impl;
 };
 
 namespace {
@@ -596,6 +601,83 @@ int64_t pdlp_mi355x_sizeof(int32_t which) {
     case 8: return sizeof(pdlp_update_t);
     default: return -1;
   }
+}
+
+// ---- sessions (pdlp_session.hpp) --------------------------------------------------------------------------------------
+int pdlp_mi355x_session_create(pdlp_mi355x_session_t** out) {
+  return guarded([&] {
+    if (!out) throw std::runtime_error("pdlp_mi355x_session_create: null argument");
+    *out = new pdlp_mi355x_session();  // (no HIP call: a session holds nothing until its first solve)
+  });
+}
+
+int pdlp_mi355x_session_solve(pdlp_mi355x_session_t* S, const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R) {
+  int rc = 0;
+  const int thrown = guarded([&] {
+    if (!S) throw std::runtime_error("pdlp_mi355x_session_solve: null session");
+    if (!P || !opt || !R) throw std::runtime_error("null argument");
+    rc = S->impl.solve(*P, *opt, R);
+  });
+  return thrown ? thrown : rc;
+}
+
+int pdlp_mi355x_session_info(const pdlp_mi355x_session_t* S, pdlp_session_info_t* out) {
+  return guarded([&] {
+    if (!S || !out) throw std::runtime_error("pdlp_mi355x_session_info: null argument");
+    *out = S->impl.info();
+  });
+}
+
+void pdlp_mi355x_session_release(pdlp_mi355x_session_t* S) {
+  if (S) S->impl.release();
+}
+
+void pdlp_mi355x_session_destroy(pdlp_mi355x_session_t* S) {
+  if (!S) return;
+  S->impl.release();
+  delete S;
+}
+
+int64_t pdlp_mi355x_session_info_size(void) { return sizeof(pdlp_session_info_t); }
+
+// Host twin of the session's decision: what the device finds by streaming the staged arrays against the kept ones is
+// found here by walking the two problems; the ladder is the session's own.
+int pdlp_mi355x_host_classify(const pdlp_problem_t* held, const pdlp_params_t* held_opt, const pdlp_problem_t* P,
+                              const pdlp_params_t* opt, pdlp_session_info_t* out) {
+  return guarded([&] {
+    if (!P || !opt || !out || (held && !held_opt)) throw std::runtime_error("pdlp_mi355x_host_classify: null argument");
+    memset(out, 0, sizeof(*out));
+    pdlp::SessionFacts f;
+    f.oneShot = pdlp::sessionOneShotReason(*opt);
+    f.held = held != nullptr;
+    if (!f.oneShot && held) {
+      f.changed = pdlp::sessionOptionChanges(*held_opt, *opt);
+      if (!(f.changed & PDLP_CHANGED_STRUCTURAL_OPTIONS))
+        f.changed |= pdlp::sessionShapeChanges(pdlp::sessionShapeOf(*held), pdlp::sessionShapeOf(*P));
+      if (!(f.changed & (PDLP_CHANGED_STRUCTURAL_OPTIONS | PDLP_CHANGED_SHAPE))) {
+        pdlp::validateProblem(*held);
+        pdlp::validateProblem(*P);
+        const pdlp::SessionShape sh = pdlp::sessionShapeOf(*P);
+        auto differ = [](const void* a, const void* b, size_t bytes) { return a != b && bytes > 0 && memcmp(a, b, bytes) != 0; };
+        const size_t n0 = (size_t)sh.numCol, m = (size_t)sh.numRow, nnz = (size_t)sh.nnz, q = (size_t)sh.qSlots;
+        if (differ(held->a_start, P->a_start, 4 * (n0 + 1)) || differ(held->a_index, P->a_index, 4 * nnz)) f.changed |= PDLP_CHANGED_PATTERN;
+        if (differ(held->a_value, P->a_value, 8 * nnz)) f.changed |= PDLP_CHANGED_MATRIX_VALUES;
+        if (differ(held->col_cost, P->col_cost, 8 * n0)) f.changed |= PDLP_CHANGED_COST;
+        if (differ(held->col_lower, P->col_lower, 8 * n0)) f.changed |= PDLP_CHANGED_COL_LOWER;
+        if (differ(held->col_upper, P->col_upper, 8 * n0)) f.changed |= PDLP_CHANGED_COL_UPPER;
+        if (differ(held->row_lower, P->row_lower, 8 * m) || differ(held->row_upper, P->row_upper, 8 * m)) f.changed |= PDLP_CHANGED_ROW_BOUNDS;
+        if (q > 0) {
+          if (differ(held->q_start, P->q_start, 4 * ((size_t)sh.qDim + 1)) || differ(held->q_index, P->q_index, 4 * q)) f.changed |= PDLP_CHANGED_HESSIAN_PATTERN;
+          if (differ(held->q_value, P->q_value, 8 * q)) f.changed |= PDLP_CHANGED_HESSIAN_VALUES;
+        }
+        for (int32_t i = 0; i < sh.numRow && f.kindRow < 0; ++i) {
+          const int32_t was = pdlp::rowKindOf(held->row_lower[i], held->row_upper[i]), now = pdlp::rowKindOf(P->row_lower[i], P->row_upper[i]);
+          if (was != now) { f.kindRow = i; f.kindWas = was; f.kindNow = now; }
+        }
+      }
+    }
+    pdlp::sessionLadder(f, out);
+  });
 }
 
 // MPS ingest (pdlp_mps.cpp).  The arrays of *out are malloc'ed copies owned by the caller's struct.

@@ -922,7 +922,8 @@ void Solver::release() noexcept {
   if (hostStats_) (void)hipHostFree(hostStats_);
   if (hostCtl_) (void)hipHostFree(hostCtl_);
   if (hostRing_) (void)hipHostFree(hostRing_);
-  hostCtl_ = nullptr; hostRing_ = nullptr;
+  if (hostRec_) (void)hipHostFree(hostRec_);
+  hostCtl_ = nullptr; hostRing_ = nullptr; hostRec_ = nullptr;
   delete comm_;
   delete mesh_;
   if (stream_) (void)hipStreamDestroy(stream_);

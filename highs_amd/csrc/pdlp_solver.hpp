@@ -116,6 +116,9 @@ class SolverBase {
   virtual void updateMatrix(const double* aValue, int64_t numNz, const pdlp_update_t* u);
   // pdlp_mi355x_update_values; likewise
   virtual void updateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t* u);
+  // New tolerances, limits and log sink for the runs that follow (pdlp_params_t primal_tol, dual_tol, gap_tol, time_limit,
+  // iter_limit, log_level, log_callback, log_ctx); every other field of opt is ignored.  Only the cuPDLP-C path takes them.
+  virtual void setRuntimeOptions(const pdlp_params_t& opt);
 };
 
 class Solver : public SolverBase {
@@ -136,6 +139,22 @@ class Solver : public SolverBase {
   void updateMatrix(const double* aValue, int64_t numNz, const pdlp_update_t* u) override;  // pdlp_update.cpp
   void updateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz,
                     const pdlp_update_t* u) override;  // pdlp_update.cpp
+  void setRuntimeOptions(const pdlp_params_t& opt) override;  // pdlp_session.cpp
+
+  // ---- what a session drives (pdlp_session.hpp; all in pdlp_session.cpp) ----
+  // The caller's a_value, costs, bounds and (QPs) Hessian arrays into HBM copies of their own, for later comparisons.
+  // Needs a solver created with PDLP_UPDATABLE_MATRIX (and PDLP_UPDATABLE_HESSIAN for a problem with Hessian slots).
+  void sessionAdopt(const pdlp_problem_t& P);
+  // P's arrays into the staging buffers of the updates (and the pattern's), then the comparison pass against the kept
+  // copies: *changed = the array bits of PDLP_CHANGED_*, *kindRow = the smallest row whose kind changes or -1 (*kindWas its
+  // kept kind), *uploadSeconds = what the uploads alone took.  P has the shape of the held problem (the caller has checked).  Nothing of the solver is written.
+  void sessionStage(const pdlp_problem_t& P, int32_t* changed, int32_t* kindRow, int32_t* kindWas, double* uploadSeconds);
+  // While set, update / updateMatrix / updateValues take the caller's arrays from the staging buffers as sessionStage left
+  // them instead of uploading them again (the host pointers still serve the host-side norms).
+  void sessionSetStaged(bool on) { staged_ = on; }
+  // After an update from staged arrays: staging and kept copies change places (the kept copy now is P).
+  void sessionCommit();
+  size_t sessionHeldBytes() const;  // HBM kept for reuse beyond a plain solver's
 
  private:
   // setup
@@ -291,6 +310,14 @@ class Solver : public SolverBase {
   DeviceArray<double> updQ_;
   double updHessSeconds_[4] = {0, 0, 0, 0};  // upload + validation, assembly, replay, refill of dQ_ (stage "update_values_seconds")
   int32_t updRecaptured_ = 0;                // 1 = the last update captured the trial graph again
+  // Session-held solvers (pdlp_session.hpp): the caller's arrays of the last call (sessIn_ laid out as updIn_, sessMat_ as
+  // updMat_, sessQ_ as updQ_, sessQPat_ = q_start then q_index), staging of the pattern (a_start, a_index, q_start,
+  // q_index), the comparison's record and its pinned mirror.  staged_: see sessionSetStaged.
+  bool staged_ = false;
+  DeviceArray<double> sessIn_, sessMat_, sessQ_;
+  DeviceArray<int32_t> sessQPat_, updPat_, sessRec_;
+  int32_t* hostRec_ = nullptr;
+  int32_t sessQDim_ = 0;
   double updSeconds_[6] = {0, 0, 0, 0, 0, 0};  // upload + validation, kernels, norms + sums, block bounds, graph capture, reset
   int32_t barrierFallbacks_ = 0, smallLaunches_ = 0;
   unsigned long long smallSeq_ = 0;  // persistent launches since gridBar_ was zeroed (their roll call counts cumulatively)

@@ -217,6 +217,10 @@ void SolverBase::updateValues(const double*, int64_t, const double*, int64_t, co
   throw std::runtime_error("pdlp_mi355x_update_values: HiPDLP solvers (algorithm = 1) do not take updates");
 }
 
+void SolverBase::setRuntimeOptions(const pdlp_params_t&) {
+  throw std::runtime_error("pdlp_mi355x: HiPDLP solvers (algorithm = 1) are not held across solves: no new options");
+}
+
 // The held solver is brought to the state of a fresh create() on the modified problem.  Everything that can be refused
 // is refused before the first write to the solver's vectors: the caller's row bounds go to a staging buffer, the
 // validation kernel reads only that and the kept kinds.
@@ -245,8 +249,8 @@ void Solver::updateImpl(const pdlp_update_t& u, const double* qValue) {
   double* dColUp = dColLo + n0;
   double* dRowLo = dColUp + n0;
   double* dRowUp = dRowLo + m;
-  auto put = [&](double* dev, const double* host, int32_t count) {
-    if (count > 0) PDLP_HIP(hipMemcpyAsync(dev, host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, stream_));
+  auto put = [&](double* dev, const double* host, int32_t count) {  // (a session has staged them already)
+    if (count > 0 && !staged_) PDLP_HIP(hipMemcpyAsync(dev, host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, stream_));
   };
   if (mask & kUpdRows) {
     put(dRowLo, u.row_lower, m);
@@ -372,7 +376,7 @@ void Solver::stageHessian(const double* qValue) {
   const int32_t n = F_.n;
   if (updQ_.size() == 0) updQ_.alloc((size_t)hk_.nSlots);
   if (updBad_.size() == 0) updBad_.alloc(1);
-  PDLP_HIP(hipMemcpyAsync(updQ_.get(), qValue, sizeof(double) * (size_t)hk_.nSlots, hipMemcpyHostToDevice, stream_));
+  if (!staged_) PDLP_HIP(hipMemcpyAsync(updQ_.get(), qValue, sizeof(double) * (size_t)hk_.nSlots, hipMemcpyHostToDevice, stream_));
   int32_t bad = n;
   PDLP_HIP(hipMemcpyAsync(updBad_.get(), &bad, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
   launchHessianValidate(hk_.dstBeg.get(), hk_.srcSlot.get(), updQ_.get(), F_.sense, n, updBad_.get(), stream_);
@@ -457,8 +461,8 @@ void Solver::updateMatrixImpl(const double* aValue, int64_t numNz, const pdlp_up
   double* dColUp = dColLo + n0;
   double* dRowLo = dColUp + n0;
   double* dRowUp = dRowLo + m;
-  auto put = [&](double* dev, const double* host, int64_t count) {
-    if (count > 0) PDLP_HIP(hipMemcpyAsync(dev, host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, stream_));
+  auto put = [&](double* dev, const double* host, int64_t count) {  // (a session has staged them already)
+    if (count > 0 && !staged_) PDLP_HIP(hipMemcpyAsync(dev, host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, stream_));
   };
   put(updMat_.get(), aValue, nnz0);
   if (mask & kUpdRows) {

@@ -46,6 +46,8 @@ EXPORTS = [
     "pdlp_mi355x_update", "pdlp_mi355x_host_prepare_updated",
     "pdlp_mi355x_update_matrix", "pdlp_mi355x_host_prepare_updated_matrix",
     "pdlp_mi355x_update_values", "pdlp_mi355x_host_prepare_qp", "pdlp_mi355x_free_prepared_hessian",
+    "pdlp_mi355x_session_create", "pdlp_mi355x_session_solve", "pdlp_mi355x_session_info", "pdlp_mi355x_session_release",
+    "pdlp_mi355x_session_destroy", "pdlp_mi355x_session_info_size", "pdlp_mi355x_host_classify",
 ]
 
 
@@ -105,6 +107,19 @@ def lib():
         L.pdlp_mi355x_host_prepare_qp_then.argtypes = [pP, pO, abi.c_f64p, abi.c_f64p, pU, pU, pPrep, pQ]
         L.pdlp_mi355x_free_prepared_hessian.argtypes = [pQ]
         L.pdlp_mi355x_free_prepared_hessian.restype = None
+        pI = C.POINTER(abi.PdlpSessionInfo)
+        L.pdlp_mi355x_session_create.argtypes = [C.POINTER(H)]
+        L.pdlp_mi355x_session_solve.argtypes = [H, pP, pO, pR]
+        L.pdlp_mi355x_session_info.argtypes = [H, pI]
+        L.pdlp_mi355x_session_release.argtypes = [H]
+        L.pdlp_mi355x_session_release.restype = None
+        L.pdlp_mi355x_session_destroy.argtypes = [H]
+        L.pdlp_mi355x_session_destroy.restype = None
+        L.pdlp_mi355x_session_info_size.restype = C.c_int64
+        L.pdlp_mi355x_host_classify.argtypes = [pP, pO, pP, pO, pI]
+        if L.pdlp_mi355x_session_info_size() != C.sizeof(abi.PdlpSessionInfo):
+            raise RuntimeError("pdlp_session_info_t: the library's size %d differs from abi.PdlpSessionInfo's %d" %
+                               (L.pdlp_mi355x_session_info_size(), C.sizeof(abi.PdlpSessionInfo)))
         L.pdlp_mi355x_row_partition.argtypes = [pPrep, C.c_int32, abi.c_i32p]
         pSlab = C.POINTER(abi.PdlpSlabLayout)
         L.pdlp_mi355x_host_slab_layout.argtypes = [pPrep, C.c_int32, C.c_int32, pSlab]
@@ -238,13 +253,84 @@ def _solve_once(P, params, R, solve_fn, solve_wide_fn):
     return fn(C.byref(P.struct), P.a_start.ctypes.data_as(abi.c_i64p), C.byref(params), C.byref(R.struct))
 
 
-def solveLpCupdlp(lp: HighsLp, start=None, solve_fn=None, solve_wide_fn=None, **options):
+def _outcome(lp, R, params, rc):
+    ms = model_status_from_term(R.term_code, R.num_iter, params.iter_limit, rc)
+    sol = HighsSolution(R.col_value, R.col_dual, R.row_value, R.row_dual, bool(R.value_valid), bool(R.dual_valid))
+    info = kkt_measures(lp, sol.col_value, sol.col_dual, sol.row_value, sol.row_dual) if rc == 0 else {}
+    info["pdlp_iteration_count"] = int(R.num_iter)
+    status = kError if rc != 0 else (kOk if ms == kOptimal or ms == kUnboundedOrInfeasible else kWarning)
+    return PdlpOutcome(status, ms, sol, int(R.num_iter), info, R)
+
+
+class Session:
+    """pdlp_mi355x_session_*: one resident solver reused across whole-problem solves.  Every solve() takes a whole HighsLp,
+    as solveLpCupdlp does; the library finds on the device what differs from the problem it holds and creates, updates or
+    forwards accordingly (include/pdlp_mi355x.h has the ladder).  One thread at a time."""
+
+    def __init__(self):
+        self.h = C.c_void_p()
+        _check(lib().pdlp_mi355x_session_create(C.byref(self.h)), "pdlp_mi355x_session_create")
+
+    def solve(self, lp, start=None, **options):
+        """-> (PdlpOutcome as solveLpCupdlp returns it, abi.PdlpSessionInfo).  A failed solve is reported through the
+        outcome's status (kError / kSolveError), as solveLpCupdlp reports it; the session then holds nothing."""
+        params = options.pop("params", None) or abi.default_params(**options)
+        P = abi.ProblemHandle(lp, start)
+        if P.wide:
+            raise ValueError("sessions take 32-bit column starts")
+        R = abi.ResultHandle(lp.num_col, lp.num_row)
+        rc = lib().pdlp_mi355x_session_solve(self.h, C.byref(P.struct), C.byref(params), C.byref(R.struct))
+        out = _outcome(lp, R, params, rc)
+        if rc != 0:
+            out.info["error"] = lib().pdlp_mi355x_last_error().decode()
+        return out, self.info
+
+    @property
+    def info(self):
+        """About the last solve (path NONE before the first)."""
+        I = abi.PdlpSessionInfo()
+        _check(lib().pdlp_mi355x_session_info(self.h, C.byref(I)), "pdlp_mi355x_session_info")
+        return I
+
+    def release(self):
+        """Drop the held solver; the session stays usable (the next solve creates)."""
+        lib().pdlp_mi355x_session_release(self.h)
+
+    def close(self):
+        if self.h:
+            lib().pdlp_mi355x_session_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def host_classify(lp_held, lp, held_options=None, start=None, **options):
+    """pdlp_mi355x_host_classify: what a session holding lp_held (solved with held_options; lp_held None: holding nothing)
+    would do with lp and **options -> abi.PdlpSessionInfo.  Host only."""
+    held_params = abi.default_params(**(held_options or {}))
+    params = abi.default_params(**options)
+    H = None if lp_held is None else abi.ProblemHandle(lp_held)
+    P = abi.ProblemHandle(lp, start)
+    I = abi.PdlpSessionInfo()
+    _check(lib().pdlp_mi355x_host_classify(None if H is None else C.byref(H.struct), C.byref(held_params), C.byref(P.struct),
+                                           C.byref(params), C.byref(I)), "pdlp_mi355x_host_classify")
+    return I
+
+
+def solveLpCupdlp(lp: HighsLp, start=None, solve_fn=None, solve_wide_fn=None, session=None, **options):
     """Solve `lp` with the MI355X PDLP path.  Keyword options use the HiGHS
     option names: kkt_tolerance, primal_feasibility_tolerance (primal_tol),
     pdlp_iteration_limit, pdlp_features_off, time_limit, log_level, ...
     An int64 `lp.a_start` with values above INT32_MAX goes through pdlp_mi355x_solve_wide.
     `solve_fn` lets the tests run the same marshalling against the oracle; `solve_wide_fn`
-    stands in for the wide entry the same way."""
+    stands in for the wide entry the same way.  `session`: a Session — the solve goes through it (pdlp_mi355x_session_solve)
+    and reuses the solver it holds where the problem allows; session.info tells which path was taken."""
+    if session is not None:
+        return session.solve(lp, start=start, **options)[0]
     params = options.pop("params", None) or abi.default_params(**options)
     P = abi.ProblemHandle(lp, start)
     R = abi.ResultHandle(lp.num_col, lp.num_row)

@@ -258,6 +258,95 @@ int pdlp_mi355x_update_matrix(pdlp_mi355x_solver_t* s, const double* a_value, in
 int pdlp_mi355x_update_values(pdlp_mi355x_solver_t* s, const double* a_value, int64_t num_nz, const double* q_value,
                               int64_t num_q_nz, const pdlp_update_t* u);
 
+/* ---- sessions: one resident solver reused across whole-problem solve calls ----------------------
+ * A session takes a WHOLE problem on every call, as pdlp_mi355x_solve does, finds out on the device what differs from the
+ * problem it holds and takes the cheapest path that gives the bits of a fresh solve: the caller neither tracks changes nor
+ * chooses among pdlp_mi355x_update / _update_matrix / _update_values (through HiGHS: changeColCost / changeCoeff /
+ * passHessian, then run() again).
+ *
+ * THE CONTRACT of pdlp_mi355x_session_solve(S, P, opt, R): *R is, bit for bit — every solution vector, every count, every
+ * scalar except setup_seconds and solve_seconds — what
+ *     pdlp_mi355x_create(P, opt') + pdlp_mi355x_run + pdlp_mi355x_destroy
+ * gives, where opt' is opt with updatable |= PDLP_UPDATABLE_DATA | PDLP_UPDATABLE_MATRIX, and | PDLP_UPDATABLE_HESSIAN when P
+ * has any Hessian slot (q_dim > 0 and q_start[q_dim] > 0).  That equals a plain pdlp_mi355x_solve(P, opt, R) except for a QP
+ * whose caller passes explicit zeros in q_value: a Hessian-updatable create keeps every slot (THE PATTERN CONTRACT above),
+ * a plain one drops zero values.  A hot start in P (both valid flags set) is honoured on every path.
+ *
+ * THE LADDER: on each call the first rule that applies decides pdlp_session_info_t.path.
+ *   1. PDLP_SESSION_ONE_SHOT   opt->algorithm == 1, more than one device resolved (num_devices / PDLP_MI355X_DEVICES), or
+ *                              sharding forced: those solvers refuse updates.  The call forwards to pdlp_mi355x_solve and the
+ *                              session holds nothing afterwards.
+ *   2. PDLP_SESSION_CREATE     nothing is held; a structural option differs (device, check_interval, features_off,
+ *                              restart_method, algorithm, scaling_mode, ruiz_iterations, step_size_strategy, reserved[],
+ *                              updatable); num_col, num_row, num_nz, sense, q_dim or the Hessian's slot count differ (so
+ *                              also: a Hessian appears or disappears); a_start / a_index or q_start / q_index differ; some
+ *                              row changes its kind (kind_row is the smallest such row; not an error).  What is held is
+ *                              destroyed first.
+ *   3. PDLP_SESSION_UPDATE_VALUES  q_value differs, with or without a_value and data.
+ *   4. PDLP_SESSION_UPDATE_MATRIX  a_value differs, perhaps with data.
+ *   5. PDLP_SESSION_UPDATE     only costs / bounds / offset differ, or nothing at all (then only the start and the reset).
+ * Arrays are compared element by element on their 64-bit (32-bit) patterns: -0.0 differs from 0.0, NaNs compare as bits.  A
+ * needless "changed" costs time only; a wrong "unchanged" cannot happen.  The run-time options primal_tol, dual_tol,
+ * gap_tol, time_limit, iter_limit, log_level, log_callback, log_ctx are applied to the held solver on every path.  The
+ * environment switches of a solver are read when it is created, as always.  If a reuse path fails
+ * for any reason the held solver is destroyed and the create path is taken once; only a failure of that create is returned.
+ * After a non-zero return the session holds nothing.  With log_level >= 1 one line names the path and the reason.
+ *
+ * What is kept in HBM besides the solver's own PDLP_UPDATABLE_* state: the caller's a_value, col_cost, col_lower, col_upper,
+ * row_lower, row_upper and (QPs) q_start, q_index, q_value, plus staging of the same size (DESIGN.md section 2f has the
+ * bytes; pdlp_session_info_t.held_bytes reports them).  The library keeps no host copy of the caller's problem.
+ *
+ * THREADING: a session is used by one thread at a time (different sessions may be used by different threads).
+ * pdlp_mi355x_session_create makes no HIP call; create / release / destroy / info work on a machine without a GPU. */
+enum {
+  PDLP_SESSION_NONE = 0, /* nothing solved yet */
+  PDLP_SESSION_CREATE = 1,
+  PDLP_SESSION_UPDATE = 2,
+  PDLP_SESSION_UPDATE_MATRIX = 3,
+  PDLP_SESSION_UPDATE_VALUES = 4,
+  PDLP_SESSION_ONE_SHOT = 5
+};
+/* pdlp_session_info_t.changed */
+enum {
+  PDLP_CHANGED_PATTERN = 1,          /* a_start / a_index */
+  PDLP_CHANGED_MATRIX_VALUES = 2,    /* a_value */
+  PDLP_CHANGED_HESSIAN_PATTERN = 4,  /* q_start / q_index */
+  PDLP_CHANGED_HESSIAN_VALUES = 8,   /* q_value */
+  PDLP_CHANGED_COST = 16,
+  PDLP_CHANGED_COL_LOWER = 32,
+  PDLP_CHANGED_COL_UPPER = 64,
+  PDLP_CHANGED_ROW_BOUNDS = 128,     /* row_lower or row_upper */
+  PDLP_CHANGED_OFFSET = 256,
+  PDLP_CHANGED_RUNTIME_OPTIONS = 512,
+  PDLP_CHANGED_STRUCTURAL_OPTIONS = 1024,
+  PDLP_CHANGED_SHAPE = 2048          /* num_col, num_row, num_nz, sense, q_dim, Hessian slot count; arrays are then not compared */
+};
+typedef struct pdlp_session_info {
+  int32_t path;     /* PDLP_SESSION_* of the last solve */
+  int32_t changed;  /* PDLP_CHANGED_* against the held problem; 0 when nothing was held or the call was one-shot */
+  int32_t kind_row; /* smallest row whose kind changes, or -1 */
+  int32_t kind_was, kind_now; /* 0 equality, 1 <=, 2 >=, 3 ranged or free; -1 when kind_row is -1 */
+  int32_t reserved;
+  double diff_seconds;   /* uploads into staging + the comparison pass */
+  double upload_seconds; /* of diff_seconds: the uploads alone (pageable host memory -> HBM) */
+  double apply_seconds;  /* the chosen path's own work: the update from the staged arrays, or the create */
+  double setup_seconds;  /* everything the call spent before the first iteration, the comparison included */
+  int64_t held_bytes;   /* HBM the session keeps for reuse beyond a plain solver (0: nothing is held) */
+  char reason[160];     /* NUL-terminated, e.g. "create: row 17 changes kind: equality -> <=" */
+} pdlp_session_info_t;
+typedef struct pdlp_mi355x_session pdlp_mi355x_session_t; /* opaque */
+int pdlp_mi355x_session_create(pdlp_mi355x_session_t** out);
+int pdlp_mi355x_session_solve(pdlp_mi355x_session_t* S, const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R);
+int pdlp_mi355x_session_info(const pdlp_mi355x_session_t* S, pdlp_session_info_t* out); /* about the last solve */
+void pdlp_mi355x_session_release(pdlp_mi355x_session_t* S); /* drop the held solver, keep the session */
+void pdlp_mi355x_session_destroy(pdlp_mi355x_session_t* S);
+int64_t pdlp_mi355x_session_info_size(void); /* sizeof(pdlp_session_info_t); pdlp_mi355x_sizeof keeps its indices */
+/* Host-only restatement of the session's decision for the CPU tests: `held` / held_opt are the problem and options of the
+ * previous call (held == NULL: nothing is held), P / opt those of this one.  Same ladder (one function shared with the
+ * session), same changed mask, same reason words; the four timings and held_bytes are 0. */
+int pdlp_mi355x_host_classify(const pdlp_problem_t* held, const pdlp_params_t* held_opt, const pdlp_problem_t* P,
+                              const pdlp_params_t* opt, pdlp_session_info_t* out);
+
 /* The same two entries with 64-bit column starts (HighsInt = int64_t builds, or any caller whose matrix
  * starts are 64-bit): a_start64[num_col+1] replaces P->a_start, which is ignored and may be NULL; every
  * other field keeps its meaning.  a_start64 is checked on the host before any HIP call: a_start64[0] == 0,

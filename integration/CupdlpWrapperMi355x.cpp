@@ -21,7 +21,9 @@
 // reproduce (CupdlpWrapper.cpp:225-251 status map, :642-717 option map).
 #include <algorithm>
 #include <cmath>
+#include <cstdlib>
 #include <limits>
+#include <mutex>
 
 #include "lp_data/HighsLpSolverObject.h"
 #include "lp_data/HighsSolution.h"
@@ -61,6 +63,26 @@ HighsStatus solveQpPdlpMi355x(const HighsOptions& options, HighsTimer& timer, co
   (void)timer;
   (void)callback;
   return solveOnMi355x(options, lp, &hessian, highs_basis, highs_solution, model_status, highs_info);
+}
+
+// PDLP_MI355X_KEEP_SOLVER=1 in the environment (read on every call, like the library's own PDLP_MI355X_* switches; HiGHS has
+// no option for it): the solve goes through ONE process-wide session (pdlp_mi355x_session_solve), which keeps the solver
+// resident and, on the next Highs::run(), creates, updates or forwards according to what changed (changeColCost ->
+// update, changeCoeff -> update matrix, passHessian -> update values, anything structural -> create).  A session serves
+// one thread at a time: a caller that finds it busy (another Highs instance running on another thread) takes the one-shot
+// call.  Unset or 0: pdlp_mi355x_solve as before.
+// The session is never released: at process end its device memory is left to the process (the driver reclaims it).  An
+// atexit handler or a static destructor here would make HIP calls while the HIP runtime's own tear-down may already have
+// run, and no HIP call may follow that.
+static int solveKeepingTheSolver(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R) {
+  const char* e = getenv("PDLP_MI355X_KEEP_SOLVER");
+  if (!e || atoi(e) == 0) return pdlp_mi355x_solve(P, opt, R);
+  static std::mutex mu;
+  static pdlp_mi355x_session_t* session = nullptr;
+  std::unique_lock<std::mutex> lock(mu, std::try_to_lock);
+  if (!lock.owns_lock()) return pdlp_mi355x_solve(P, opt, R);
+  if (!session && pdlp_mi355x_session_create(&session) != 0) return pdlp_mi355x_solve(P, opt, R);
+  return pdlp_mi355x_session_solve(session, P, opt, R);
 }
 
 static HighsStatus solveOnMi355x(const HighsOptions& options, const HighsLp& lp, const HighsHessian* hessian,
@@ -147,7 +169,7 @@ static HighsStatus solveOnMi355x(const HighsOptions& options, const HighsLp& lp,
   R.row_value = highs_solution.row_value.data();
   R.row_dual = highs_solution.row_dual.data();
 
-  const int rc = pdlp_mi355x_solve(&P, &opt, &R);
+  const int rc = solveKeepingTheSolver(&P, &opt, &R);
 
   highs_info.pdlp_iteration_count = R.num_iter;
   highs_solution.value_valid = R.value_valid != 0;
