@@ -158,6 +158,27 @@ class PdlpSessionInfo(C.Structure):
         return self.reason.decode()
 
 
+class PdlpBatchInfo(C.Structure):
+    """pdlp_batch_info_t (include/pdlp_mi355x.h): what the last pdlp_mi355x_batch_run did; its size is checked against
+    pdlp_mi355x_batch_info_size()."""
+    _fields_ = [
+        ("lanes", C.c_int32),
+        ("lanes_concurrent", C.c_int32),
+        ("variants", C.c_int32),
+        ("trial_launches", C.c_int32),
+        ("check_launches", C.c_int32),
+        ("fallback_variants", C.c_int32),
+        ("xcc_of_lane", C.c_int32 * 8),
+        ("reserved", C.c_int32 * 2),
+        ("wall_seconds", C.c_double),
+        ("reason", C.c_char * 160),
+    ]
+
+    @property
+    def text(self):
+        return self.reason.decode()
+
+
 class PdlpIterStats(C.Structure):
     _fields_ = [
         ("iters", C.c_int32),

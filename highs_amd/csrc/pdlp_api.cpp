@@ -12,6 +12,7 @@
 #include <thread>
 #include <vector>
 
+#include "pdlp_batch.hpp"
 #include "pdlp_halpern.hpp"
 #include "pdlp_mps.hpp"
 #include "pdlp_session.hpp"
@@ -25,6 +26,10 @@ struct pdlp_mi355x_solver {
 
 struct pdlp_mi355x_session {
   pdlp::Session impl;
+};
+
+struct pdlp_mi355x_batch {
+  std::unique_ptr<pdlp::Batch> impl;
 };
 
 namespace {
@@ -639,6 +644,41 @@ void pdlp_mi355x_session_destroy(pdlp_mi355x_session_t* S) {
 }
 
 int64_t pdlp_mi355x_session_info_size(void) { return sizeof(pdlp_session_info_t); }
+
+// ---- batches (pdlp_batch.hpp) -------------------------------------------------------------------------------------------
+int pdlp_mi355x_batch_create(const pdlp_problem_t* P, const pdlp_params_t* opt, int32_t lanes, pdlp_mi355x_batch_t** out) {
+  return guarded([&] {
+    if (!P || !opt || !out) throw std::runtime_error("pdlp_mi355x_batch_create: null argument");
+    *out = nullptr;
+    std::unique_ptr<pdlp::Batch> b(new pdlp::Batch(*P, *opt, lanes));  // (the refusals by name come before any HIP call)
+    *out = new pdlp_mi355x_batch{std::move(b)};
+  });
+}
+
+int pdlp_mi355x_batch_run(pdlp_mi355x_batch_t* B, int32_t K, const pdlp_update_t* u, pdlp_result_t* R) {
+  return guarded([&] {
+    if (!B || !B->impl) throw std::runtime_error("pdlp_mi355x_batch_run: null batch");
+    B->impl->run(K, u, R);
+  });
+}
+
+int pdlp_mi355x_batch_info(const pdlp_mi355x_batch_t* B, pdlp_batch_info_t* out) {
+  return guarded([&] {
+    if (!B || !B->impl || !out) throw std::runtime_error("pdlp_mi355x_batch_info: null argument");
+    *out = B->impl->info();
+  });
+}
+
+void pdlp_mi355x_batch_destroy(pdlp_mi355x_batch_t* B) {
+  if (!B) return;
+  try {
+    B->impl.reset();
+  } catch (...) {
+  }
+  delete B;
+}
+
+int64_t pdlp_mi355x_batch_info_size(void) { return sizeof(pdlp_batch_info_t); }
 
 // Host twin of the session's decision: what the device finds by streaming the staged arrays against the kept ones is
 // found here by walking the two problems; the ladder is the session's own.

@@ -1,0 +1,91 @@
+// pdlp_batch.hpp — up to eight variants of one small LP solved at once, one per XCD (pdlp_mi355x_batch_*).
+//
+// A batch owns `lanes` ordinary solvers of ONE problem.  Where a solver's trial loop runs XCD-local (at most 32 work
+// blocks: seven of the eight XCDs idle by construction) the lanes' loops share launches: k_trials_small_lanes /
+// k_check_small_lanes give workgroup b to lane b & 7, every lane running — on its own state, barrier words and vectors —
+// exactly what its solo launch runs.  Nothing is synchronised between lanes: step sizes, restarts, check schedule and
+// halt are each lane's own, so the bits of every result are those of a solo update + run.  A lane whose variant has ended
+// takes the next one while the others carry on.  Everywhere else batch_run is a loop of update + run on lane 0.
+//
+// The driver (BatchDriver) sees its lanes and the device only through the two interfaces below, so that it also runs
+// against canned lanes on a machine without a device.
+#pragma once
+#include <cstdint>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "pdlp_kernels.hpp"
+#include "pdlp_host.hpp"
+
+namespace pdlp {
+
+class Solver;
+
+// One unit of a lane's queue: [trial batch to the next scheduled check][check], as launch records.
+struct LaneUnit {
+  bool hasTrials = false;  // false: the entry's check alone
+  SmallLaneLaunch trials;
+  CheckLaneLaunch check;
+};
+
+enum LaneVerdict : int { kLaneGoOn = 0, kLaneOver = 1, kLaneFailed = 2 };
+
+// What the driver asks of a resident solver (SolverLane: Solver's lane steps, pdlp_solver.hpp).
+class BatchLane {
+ public:
+  virtual ~BatchLane() = default;
+  virtual std::string sequentialReason() = 0;  // empty: the launches can be shared
+  virtual int32_t workBlocks() = 0;
+  virtual void validate(const pdlp_update_t& u) = 0;  // throws with update's words; changes nothing
+  virtual void setVariant(int32_t k, int32_t iterLimit) = 0;  // log prefix and iteration limit (0: the batch's) of what follows
+  virtual void update(const pdlp_update_t& u) = 0;
+  virtual void runAlone(pdlp_result_t* R) = 0;  // the ordinary run, with its own fall-backs
+  virtual void begin() = 0;
+  virtual bool idle() = 0;
+  virtual void queue(int32_t ahead, std::vector<LaneUnit>& units) = 0;
+  virtual LaneVerdict afterRound() = 0;
+  virtual void finish(pdlp_result_t* R) = 0;
+  virtual int32_t xcc() = 0;
+};
+
+// One round on the device: launch j = the j-th units of all lanes that have one, [trials] then [check] in one launch each
+// behind ONE take of the device gate; every taking lane's state record downloaded behind them; one synchronisation.
+class BatchBackend {
+ public:
+  virtual ~BatchBackend() = default;
+  virtual void round(const std::vector<LaneUnit>* units, int nLanes, int32_t* trialLaunches, int32_t* checkLaunches) = 0;
+};
+
+class BatchDriver {
+ public:
+  BatchDriver(std::vector<BatchLane*> lanes, BatchBackend* backend);
+  void run(int32_t K, const pdlp_update_t* u, pdlp_result_t* R);
+  const pdlp_batch_info_t& info() const { return info_; }
+
+ private:
+  void runSequential(int32_t first, int32_t K, const pdlp_update_t* u, pdlp_result_t* R);
+  void runConcurrent(int32_t K, const pdlp_update_t* u, pdlp_result_t* R);
+  std::vector<BatchLane*> lanes_;
+  BatchBackend* backend_;
+  pdlp_batch_info_t info_{};
+};
+
+// Refusals of pdlp_mi355x_batch_create that need no device: nullptr, or the message.
+std::string batchCreateRefusal(const pdlp_params_t& opt, int32_t lanes);
+
+// The batch behind the C ABI: the solvers, their lanes, the device backend and the driver.
+class Batch {
+ public:
+  Batch(const pdlp_problem_t& P, const pdlp_params_t& opt, int32_t lanes);
+  ~Batch();
+  void run(int32_t K, const pdlp_update_t* u, pdlp_result_t* R);
+  const pdlp_batch_info_t& info() const { return driver_->info(); }
+
+ private:
+  struct Impl;
+  std::unique_ptr<Impl> impl_;
+  std::unique_ptr<BatchDriver> driver_;
+};
+
+}  // namespace pdlp

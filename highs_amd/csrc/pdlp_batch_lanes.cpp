@@ -1,0 +1,384 @@
+// pdlp_batch_lanes.cpp — the device side of a batch (pdlp_batch.hpp): Solver's lane steps, i.e. Solver::run cut into the
+// pieces the driver calls per lane; the lane and the backend the driver works with on a device; the batch itself.
+#include <algorithm>
+#include <climits>
+#include <cstdio>
+#include <cstring>
+
+#include "pdlp_batch.hpp"
+#include "pdlp_session.hpp"
+#include "pdlp_solver.hpp"
+#include "pdlp_update.hpp"
+
+namespace pdlp {
+
+namespace {
+const int32_t kCheckInterval = Solver::defaultCheckInterval();
+}
+
+// ---- Solver: one run as a lane ------------------------------------------------------------------------------------------
+std::string Solver::laneSequentialReason() const {
+  const std::string blocks = std::to_string(smallGrid_) + " work blocks";
+  if (sharded_) return "sharded solver";
+  if (!persistent_) return "the trial loop is not one persistent launch (" + std::to_string(std::max(dA_.nBlocks, dAt_.nBlocks)) + " work blocks)";
+  if (!xcdLocal_) {
+    if (smallGrid_ > 32) return blocks + " need more than one XCD";
+    if (sw_.xcdLocal == 0) return blocks + ", but the XCD-local mode is switched off";
+    return blocks + ", but the XCD-local placement does not hold on this device";
+  }
+  if (!checkSmall_) return blocks + ", but the check is not one launch";
+  if (!devCheck_) return blocks + ", but the checks are driven by the host";
+  if (profile_) return blocks + ", but the solver is in profile mode";
+  if (!smallLanesSupported(dA_.view(), dAt_.view(), primalInA_) || !checkLanesSupported(dA_.view(), dAt_.view()))
+    return blocks + ", but not in 512-entry blocks";
+  return std::string();
+}
+
+void Solver::validateUpdate(const pdlp_update_t& u) const {
+  if (sharded_)
+    throw std::runtime_error("pdlp_mi355x_update: sharded solvers (pdlp_mi355x_create_sharded) do not take updates");
+  if (!updatable_)
+    throw std::runtime_error("pdlp_mi355x_update: the solver was not created for updates (pdlp_params_t.updatable = 0)");
+  checkUpdateShape(u);
+  if (u.row_lower) {  // (the rule of the device's validation kernel, on the host's copy of the kinds)
+    const int32_t m = F_.m;
+    const int32_t bad = firstKindChange(F_.rowKind.data(), m, u.row_lower, u.row_upper);
+    if (bad < m) throwKindChange(bad, F_.rowKind[bad], rowKindOf(u.row_lower[bad], u.row_upper[bad]));
+  }
+}
+
+// run() up to the first round of doSolveDevice
+void Solver::laneBegin() {
+  reset();
+  solveBeg_ = std::chrono::steady_clock::now();
+  if (hasStart_) log(1, "Hot starting with given column primal values and row dual values\n");
+  lane_ = LaneRun();
+  DevState& s = *hostState_;
+  lane_.iterLim = (int64_t)opt_.iter_limit;
+  if (s.nIter >= lane_.iterLim) {
+    lane_.noLoop = true;
+    return;
+  }
+  uploadCtl(true, lane_.iterLim);
+  checkSeen_ = checkSeq_;
+  // entry: a check is due right here (iteration 0 is on every schedule)
+  const int32_t interval = opt_.check_interval > 0 ? opt_.check_interval : kCheckInterval;
+  if (s.nIter < 10 || s.nIter % interval == 0 || s.nIter == opt_.iter_limit - 1) {
+    s.haltIter = s.nIter;
+    s.halted = 1;
+  } else {
+    s.haltIter = nextCheckIter(s.nIter);
+    s.halted = 0;
+  }
+  pushState(false);
+  PDLP_HIP(hipStreamSynchronize(stream_));  // (the round's launches come on the batch's stream)
+}
+
+// The units of doSolveDevice's next round, as launch records: enqueueBatch's persistent launch and enqueueCheckDevice's
+// one-launch check, with their bookkeeping (launch counters, the ring's record) done as if launched here.
+void Solver::laneQueue(int32_t ahead, std::vector<LaneUnit>& units) {
+  DevState& s = *hostState_;
+  const int64_t iterLim = lane_.iterLim;
+  lane_.iterBefore = s.nIter;
+  lane_.trialsBefore = s.nTrials;
+  lane_.seq0 = checkSeq_;
+  auto haltAfter = [&](int64_t it) { return (int64_t)nextCheckIter((int32_t)it); };
+  auto trials = [&](int32_t todo) {
+    SmallLaneLaunch t;
+    t.A = dA_.view(); t.At = dAt_.view(); t.v = vecs_; t.st = dst();
+    t.partDY = partDY_.get(); t.partDX = partDX_.get(); t.partInter = partInter_.get(); t.bar = gridBar_.get();
+    t.grid = smallGrid_; t.maxTrials = todo + 8; t.timeoutMs = sw_.barrierTimeoutMs;
+    t.failRollCall = sw_.fault == 1 && smallLaunches_ == 0;
+    t.selfTest = smallLaunches_ == 0;
+    t.seq = ++smallSeq_;
+    t.primalInA = primalInA_;
+    ++smallLaunches_;
+    return t;
+  };
+  auto check = [&]() {
+    CheckLaneLaunch c;
+    CheckRecord* rec = hostRing_ + (checkSeq_ % kRingSlots);
+    rec->ran = 0;
+    ++checkSeq_;
+    c.A = dA_.view(); c.At = dAt_.view(); c.v = vecs_; c.st = dst(); c.cc = dCtl_.get(); c.rec = rec;
+    c.r = RestartVecs{xAvg_.get(), yAvg_.get(), axAvg_.get(), atyAvg_.get(), nullptr, xLast_.get(), yLast_.get()};
+    c.rowScale = rowScale_.get(); c.colScale = colScale_.get(); c.scaled = F_.scaled ? 1 : 0;
+    c.spC = slackPos_.get(); c.snC = slackNeg_.get(); c.spA = slackPosAvg_.get(); c.snA = slackNegAvg_.get();
+    c.statPart = statPart_.get(); c.statStride = statStride_; c.statOut = statOut_.get();
+    c.partX = partDX_.get(); c.partY = partRestartY_.get(); c.bar = checkBar_.get();
+    c.grid = smallGrid_; c.timeoutMs = sw_.barrierTimeoutMs; c.seq = ++checkSmallSeq_;
+    needPrimal_ = true;
+    return c;
+  };
+  int64_t itExp = s.nIter, haltExp = s.haltIter;
+  if (s.halted) {  // (entry only: every batch below is followed by its check)
+    LaneUnit e;
+    e.check = check();
+    units.push_back(e);
+    haltExp = haltAfter(itExp);
+  }
+  int64_t queuedTrials = 0;  // (the tabulated powers of the step rule reach 4096 trials beyond the last refresh)
+  for (int32_t u = 0; u < ahead && queuedTrials < 3000; ++u) {
+    int64_t todo = haltExp - itExp;
+    if (todo < 1) todo = 1;
+    if (todo > 4 * kCheckInterval) todo = 4 * kCheckInterval;
+    LaneUnit unit;
+    unit.hasTrials = true;
+    unit.trials = trials((int32_t)todo);
+    unit.check = check();
+    units.push_back(unit);
+    queuedTrials += todo + 8;
+    itExp = std::min(itExp + todo, haltExp);
+    if (itExp >= iterLim - 1) break;  // the check that ends the solve
+    if (itExp == haltExp) haltExp = haltAfter(itExp);
+  }
+}
+
+void Solver::laneDownload(hipStream_t shared) {
+  PDLP_HIP(hipMemcpyAsync(hostState_, dst(), sizeof(DevState), hipMemcpyDeviceToHost, shared));
+}
+
+// syncState (the stream is idle, the state record is here) + processRecords + the tail of doSolveDevice's loop
+LaneVerdict Solver::laneAfterRound() {
+  DevState& s = *hostState_;
+  if (s.commError) {  // 2: placement, 3: roll call (the launch changed nothing for this lane); 1: barrier timeout (the lane is stopped)
+    lane_.commError = s.commError;
+    log(1, "Note: this lane's workgroups of a shared launch %s; its variant is solved alone\n",
+        s.commError == 2 ? "were not placed on one XCD" : s.commError == 3 ? "were not resident together in time" : "did not meet at a barrier in time");
+    return kLaneFailed;
+  }
+  processRecords(true, lane_.iterLim, lane_.logSinceHeader);
+  bool over = false;
+  for (int64_t q = lane_.seq0; q < checkSeq_; ++q) over = over || (hostRing_[q % kRingSlots].ran && hostRing_[q % kRingSlots].terminated);
+  if (over) return kLaneOver;
+  if (s.nIter == lane_.iterBefore && s.nTrials - lane_.trialsBefore > 0) {
+    if (++stalledRounds_ >= 50)
+      throw std::runtime_error("pdlp_mi355x: the adaptive step-size search does not terminate (no trial step accepted in " +
+                               std::to_string(s.nTrials - stalledSince_) + " trials: NaN or Inf in the problem data?)");
+  } else {
+    stalledRounds_ = 0;
+    stalledSince_ = s.nTrials;
+  }
+  if (timeIsUp()) {
+    lane_.timeUp = true;
+    return kLaneOver;
+  }
+  if (s.powRed && s.nTrials + 4096 >= s.powBase + s.powCount) pushState(true);
+  return kLaneGoOn;
+}
+
+int32_t Solver::laneXcc() {
+  if (!persistent_ || gridBar_.size() == 0) return -1;
+  unsigned long long id = 0;  // (the XCC ids behind the arrival words and the flag: id + 1, 0 = never published)
+  PDLP_HIP(hipMemcpyAsync(&id, gridBar_.get() + smallGrid_ + 8, sizeof(id), hipMemcpyDeviceToHost, stream_));
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  return id == 0 ? -1 : (int32_t)id - 1;
+}
+
+void Solver::laneFinish(pdlp_result_t* R) {
+  if (!lane_.noLoop) endDeviceLoop(true, lane_.timeUp, lane_.logSinceHeader);
+  finishRun(R);
+}
+
+namespace {
+
+// Log lines of a lane: "[variant k] " in front of every line, then the caller's sink (NULL: stdout).
+struct LogTap {
+  void (*sink)(void*, int, const char*) = nullptr;
+  void* sinkCtx = nullptr;
+  std::string prefix;
+  bool lineStart = true;
+  static void write(void* ctx, int level, const char* text) {
+    LogTap& t = *static_cast<LogTap*>(ctx);
+    std::string out;
+    for (const char* p = text; *p; ++p) {
+      if (t.lineStart && *p != '\n') out += t.prefix;
+      t.lineStart = *p == '\n';
+      out += *p;
+    }
+    if (t.sink) t.sink(t.sinkCtx, level, out.c_str());
+    else { fputs(out.c_str(), stdout); fflush(stdout); }
+  }
+};
+
+// The data of P that an update can change, kept on the host: variant k is P with u[k] applied, whatever variant the lane
+// solved before — so what an earlier variant changed on a lane and this one leaves alone goes back to P's values.
+struct BaseData {
+  std::vector<double> cost, colLower, colUpper, rowLower, rowUpper;
+  double offset = 0.0;
+  explicit BaseData(const pdlp_problem_t& P)
+      : cost(P.col_cost, P.col_cost + P.num_col), colLower(P.col_lower, P.col_lower + P.num_col),
+        colUpper(P.col_upper, P.col_upper + P.num_col), rowLower(P.row_lower, P.row_lower + P.num_row),
+        rowUpper(P.row_upper, P.row_upper + P.num_row), offset(P.offset) {}
+};
+
+class SolverLane : public BatchLane {
+ public:
+  SolverLane(Solver* s, const pdlp_params_t& opt, const BaseData* base) : s_(s), opt_(opt), base_(base) {
+    tap_.sink = opt.log_callback;
+    tap_.sinkCtx = opt.log_ctx;
+  }
+  std::string sequentialReason() override { return s_->laneSequentialReason(); }
+  int32_t workBlocks() override { return s_->laneWorkBlocks(); }
+  void validate(const pdlp_update_t& u) override { s_->validateUpdate(u); }
+  void setVariant(int32_t k, int32_t iterLimit) override {
+    pdlp_params_t o = opt_;
+    if (iterLimit > 0) o.iter_limit = iterLimit;
+    if (o.log_level >= 1) {
+      tap_.prefix = "[variant " + std::to_string(k) + "] ";
+      tap_.lineStart = true;
+      o.log_callback = &LogTap::write;
+      o.log_ctx = &tap_;
+    }
+    s_->setRuntimeOptions(o);
+  }
+  void update(const pdlp_update_t& u) override {
+    enum { kCost = 1, kColLower = 2, kColUpper = 4, kRows = 8, kOffset = 16 };
+    pdlp_update_t v = u;
+    int now = 0;
+    auto take = [&](const double*& field, const std::vector<double>& base, int bit) {
+      if (field) now |= bit;
+      else if (differs_ & bit) field = base.data();
+    };
+    take(v.col_cost, base_->cost, kCost);
+    take(v.col_lower, base_->colLower, kColLower);
+    take(v.col_upper, base_->colUpper, kColUpper);
+    if (v.row_lower) now |= kRows;  // (given together: validated)
+    else if (differs_ & kRows) { v.row_lower = base_->rowLower.data(); v.row_upper = base_->rowUpper.data(); }
+    if (v.has_offset) now |= kOffset;
+    else if (differs_ & kOffset) { v.has_offset = 1; v.offset = base_->offset; }
+    differs_ |= now;  // (also when the update throws half-way: a needless restore costs time only)
+    s_->update(v);
+    differs_ = now;
+  }
+  void runAlone(pdlp_result_t* R) override { s_->run(R); }
+  void begin() override { s_->laneBegin(); }
+  bool idle() override { return s_->laneIdle(); }
+  void queue(int32_t ahead, std::vector<LaneUnit>& units) override { s_->laneQueue(ahead, units); }
+  LaneVerdict afterRound() override { return s_->laneAfterRound(); }
+  void finish(pdlp_result_t* R) override { s_->laneFinish(R); }
+  int32_t xcc() override { return s_->laneXcc(); }
+
+ private:
+  Solver* s_;
+  pdlp_params_t opt_;
+  const BaseData* base_;
+  int differs_ = 0;  // the arrays in which the solver's problem differs from P
+  LogTap tap_;
+};
+
+// The rounds on the device.  Everything of a round goes to lane 0's stream, behind one take of the device gate; the
+// argument records of all its launches are written into pinned host memory first and reach HBM in one copy.
+class DeviceBackend : public BatchBackend {
+ public:
+  explicit DeviceBackend(std::vector<Solver*> solvers) : solvers_(std::move(solvers)) {
+    slotT_ = smallLanesSlotBytes();
+    slotC_ = checkLanesSlotBytes();
+    const size_t bytes = (size_t)kMaxUnits * (slotT_ + slotC_);
+    PDLP_HIP(hipHostMalloc(&host_, bytes, hipHostMallocDefault));
+    PDLP_HIP(hipMalloc(&dev_, bytes));
+  }
+  ~DeviceBackend() override {
+    if (host_) (void)hipHostFree(host_);
+    if (dev_) (void)hipFree(dev_);
+  }
+  void round(const std::vector<LaneUnit>* units, int nLanes, int32_t* trialLaunches, int32_t* checkLaunches) override {
+    size_t J = 0;
+    for (int l = 0; l < nLanes; ++l) J = std::max(J, units[l].size());
+    if (J == 0) return;
+    if (J > (size_t)kMaxUnits) throw std::runtime_error("pdlp_mi355x_batch_run: more units in a round than argument slots");
+    std::vector<SmallLaneLaunch> tl(J * kBatchLanes);
+    std::vector<CheckLaneLaunch> cl(J * kBatchLanes);
+    std::vector<char> anyTrials(J, 0);
+    char* hostT = static_cast<char*>(host_);
+    char* hostC = hostT + J * slotT_;
+    for (size_t j = 0; j < J; ++j) {
+      for (int l = 0; l < nLanes; ++l) {
+        if (j >= units[l].size()) continue;  // (grid 0: the lane takes no part in launch j)
+        const LaneUnit& q = units[l][j];
+        if (q.hasTrials) { tl[j * kBatchLanes + l] = q.trials; anyTrials[j] = 1; }
+        cl[j * kBatchLanes + l] = q.check;
+      }
+      fillSmallTrialsLanes(&tl[j * kBatchLanes], nLanes, hostT + j * slotT_);
+      fillCheckSmallLanes(&cl[j * kBatchLanes], nLanes, hostC + j * slotC_);
+    }
+    Solver& first = *solvers_[0];
+    hipStream_t s = first.laneStream();
+    const char* devT = static_cast<const char*>(dev_);
+    const char* devC = devT + J * slotT_;
+    std::unique_lock<std::mutex> gate = first.laneBeginRound();
+    try {
+      PDLP_HIP(hipMemcpyAsync(dev_, host_, J * (slotT_ + slotC_), hipMemcpyHostToDevice, s));
+      for (size_t j = 0; j < J; ++j) {
+        if (anyTrials[j]) {
+          launchSmallTrialsLanes(&tl[j * kBatchLanes], nLanes, devT + j * slotT_, s);
+          ++*trialLaunches;
+        }
+        launchCheckSmallLanes(&cl[j * kBatchLanes], nLanes, devC + j * slotC_, s);
+        ++*checkLaunches;
+      }
+    } catch (...) {  // the end of the round is marked on every way out (Solver::BarrierRound)
+      try { first.laneEndRound(gate); } catch (...) {}
+      throw;
+    }
+    first.laneEndRound(gate);
+    for (int l = 0; l < nLanes; ++l)
+      if (!units[l].empty()) solvers_[l]->laneDownload(s);
+    PDLP_HIP(hipStreamSynchronize(s));
+    PDLP_HIP(hipGetLastError());  // a launch that failed (bad grid, LDS request, ...) surfaces here
+  }
+
+ private:
+  static constexpr int kMaxUnits = 20;  // a round queues the entry's check and at most 16 units per lane
+  std::vector<Solver*> solvers_;
+  size_t slotT_ = 0, slotC_ = 0;
+  void* host_ = nullptr;
+  void* dev_ = nullptr;
+};
+
+}  // namespace
+
+std::string batchCreateRefusal(const pdlp_params_t& opt, int32_t lanes) {
+  if (lanes < 1 || lanes > kBatchLanes)
+    return "pdlp_mi355x_batch_create: lanes = " + std::to_string(lanes) + " is outside 1..8 (one lane per XCD)";
+  if (opt.algorithm != 0 && opt.algorithm != 1) return "unknown algorithm (0 = cuPDLP-C path, 1 = HiPDLP path)";
+  if (const char* why = sessionOneShotReason(opt)) return std::string("pdlp_mi355x_batch_create: ") + why;
+  return std::string();
+}
+
+struct Batch::Impl {
+  std::vector<std::unique_ptr<Solver>> solvers;
+  std::vector<std::unique_ptr<SolverLane>> lanes;
+  std::unique_ptr<DeviceBackend> backend;
+  std::unique_ptr<BaseData> base;
+  int32_t device = 0;
+};
+
+Batch::Batch(const pdlp_problem_t& P, const pdlp_params_t& opt, int32_t lanes) : impl_(new Impl) {
+  const std::string refused = batchCreateRefusal(opt, lanes);
+  if (!refused.empty()) throw std::runtime_error(refused);
+  pdlp_params_t o = opt;
+  o.updatable |= PDLP_UPDATABLE_DATA;
+  impl_->device = o.device;
+  validateProblem(P);
+  impl_->base.reset(new BaseData(P));
+  std::vector<BatchLane*> ls;
+  std::vector<Solver*> ss;
+  for (int32_t l = 0; l < lanes; ++l) {
+    impl_->solvers.emplace_back(new Solver(P, o, 0, 1, nullptr));
+    impl_->lanes.emplace_back(new SolverLane(impl_->solvers.back().get(), o, impl_->base.get()));
+    ls.push_back(impl_->lanes.back().get());
+    ss.push_back(impl_->solvers.back().get());
+  }
+  impl_->backend.reset(new DeviceBackend(ss));
+  driver_.reset(new BatchDriver(ls, impl_->backend.get()));
+}
+
+Batch::~Batch() = default;
+
+void Batch::run(int32_t K, const pdlp_update_t* u, pdlp_result_t* R) {
+  PDLP_HIP(hipSetDevice(impl_->device));
+  driver_->run(K, u, R);
+}
+
+}  // namespace pdlp

@@ -253,8 +253,9 @@ __device__ __forceinline__ void plainLongBlock(const LongMat& L, int tb, const d
   __syncthreads();
 }
 
+// The body of the launch for workgroup lb of G: shared by k_check_small and k_check_small_lanes.
 template <int CHUNK_A, int CHUNK_AT>
-__global__ __launch_bounds__(kVecThreads) void k_check_small(const CheckSmallArgs a) {
+__device__ __forceinline__ void checkSmallBody(const CheckSmallArgs& a, const int lb, const int G) {
   constexpr int kMaxChunk = CHUNK_A > CHUNK_AT ? CHUNK_A : CHUNK_AT;
   __shared__ double prod[kMaxChunk + kMaxChunk / 8 + 8];
   __shared__ double scratch[2 * kColStats][kVecThreads / kWave];
@@ -263,7 +264,7 @@ __global__ __launch_bounds__(kVecThreads) void k_check_small(const CheckSmallArg
   __shared__ CheckCtl ctl;
   __shared__ int flag;
   __shared__ int barBad;  // a grid barrier of this launch did not hold in this workgroup (gridBarrier's verdict)
-  const int tid = threadIdx.x, lb = blockIdx.x, G = gridDim.x;
+  const int tid = threadIdx.x;
   if (tid == 0) barBad = 0;
   // roll call: every launch of the sequence takes part, due or not (the count is cumulative)
   if (tid < kWave) {
@@ -396,6 +397,31 @@ __global__ __launch_bounds__(kVecThreads) void k_check_small(const CheckSmallArg
   if (tid == 0) writeRecord(a.rec, sh, ctl);
 }
 
+template <int CHUNK_A, int CHUNK_AT>
+__global__ __launch_bounds__(kVecThreads) void k_check_small(const CheckSmallArgs a) {
+  checkSmallBody<CHUNK_A, CHUNK_AT>(a, (int)blockIdx.x, (int)gridDim.x);
+}
+
+// The checks of up to eight solvers of one problem in one launch (pdlp_batch.hpp), with the lane mapping of
+// k_trials_small_lanes: workgroup b works for lane b & 7 as its workgroup b >> 3 of grid[lane].  Accesses, barrier and
+// roll call of a lane are those of its solo launch (agent scope: right wherever the workgroups sit); a lane whose check is
+// not due, or whose solve is over, leaves behind its own roll call as it does alone.  The argument records lie in HBM and
+// are read through the constant address space (pdlp_small.hip k_trials_small_lanes has the reasons).
+struct CheckLanesHdr {
+  int32_t nLanes;
+  int32_t grid[8];  // 0: the lane takes no part in this launch
+};
+template <int CHUNK_A, int CHUNK_AT>
+__global__ __launch_bounds__(kVecThreads) void k_check_small_lanes(const CheckLanesHdr h, const CheckSmallArgs* __restrict__ lanes) {
+  const int lane = (int)blockIdx.x & 7, lb = (int)blockIdx.x >> 3;
+  if (lane >= h.nLanes) return;
+  const int G = h.grid[lane];
+  if (lb >= G) return;
+  typedef const CheckSmallArgs __attribute__((address_space(4))) * ConstArgs;
+  const CheckSmallArgs& a = *(const CheckSmallArgs*)((ConstArgs)lanes + lane);
+  checkSmallBody<CHUNK_A, CHUNK_AT>(a, lb, G);
+}
+
 using CheckSmallKernel = void (*)(const CheckSmallArgs);
 CheckSmallKernel pickCheckSmall(int chunkA, int chunkAt) {
   if (chunkA == kChunkSmall && chunkAt == kChunkSmall) return k_check_small<kChunkSmall, kChunkSmall>;
@@ -435,10 +461,11 @@ int checkSmallResident(const MatView& A, const MatView& At, int device) {
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
   return (perCu < 4 ? perCu : 4) * cus;
 }
-void launchCheckSmall(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, CheckCtl* cc, CheckRecord* rec,
-                      const RestartVecs& r, const double* rowScale, const double* colScale, int scaled, double* spC, double* snC,
-                      double* spA, double* snA, double* statPart, int32_t statStride, double* statOut, double* partX, double* partY,
-                      unsigned long long* bar, int32_t grid, unsigned long long seq, int32_t timeoutMs, hipStream_t s) {
+namespace {
+CheckSmallArgs checkSmallArgsOf(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, CheckCtl* cc, CheckRecord* rec,
+                                const RestartVecs& r, const double* rowScale, const double* colScale, int scaled, double* spC, double* snC,
+                                double* spA, double* snA, double* statPart, int32_t statStride, double* statOut, double* partX,
+                                double* partY, unsigned long long* bar, unsigned long long seq, int32_t timeoutMs) {
   CheckSmallArgs a{};
   a.A = A.csr; a.At = At.csr; a.LA = A.lng; a.LAt = At.lng; a.v = v; a.st = st; a.cc = cc; a.rec = rec; a.r = r;
   a.xAvg = const_cast<double*>(r.xAvg); a.yAvg = const_cast<double*>(r.yAvg);
@@ -448,7 +475,46 @@ void launchCheckSmall(const MatView& A, const MatView& At, const IterVecs& v, De
   a.statPart = statPart; a.statStride = statStride; a.statOut = statOut; a.partX = partX; a.partY = partY;
   a.bar = bar; a.seq = seq;
   a.limit = (unsigned long long)(timeoutMs > 0 ? timeoutMs : 1000) * 100000ull;
+  return a;
+}
+using CheckLanesKernel = void (*)(const CheckLanesHdr, const CheckSmallArgs*);
+CheckLanesKernel pickCheckLanes(int chunkA, int chunkAt) {  // (the lanes run XCD-local trial loops: 512-entry blocks only)
+  return chunkA == kChunkSmall && chunkAt == kChunkSmall ? k_check_small_lanes<kChunkSmall, kChunkSmall> : nullptr;
+}
+}  // namespace
+void launchCheckSmall(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, CheckCtl* cc, CheckRecord* rec,
+                      const RestartVecs& r, const double* rowScale, const double* colScale, int scaled, double* spC, double* snC,
+                      double* spA, double* snA, double* statPart, int32_t statStride, double* statOut, double* partX, double* partY,
+                      unsigned long long* bar, int32_t grid, unsigned long long seq, int32_t timeoutMs, hipStream_t s) {
+  const CheckSmallArgs a = checkSmallArgsOf(A, At, v, st, cc, rec, r, rowScale, colScale, scaled, spC, snC, spA, snA, statPart, statStride,
+                                            statOut, partX, partY, bar, seq, timeoutMs);
   hipLaunchKernelGGL(pickCheckSmall(A.csr.chunk, At.csr.chunk), dim3(grid), dim3(kVecThreads), 0, s, a);
+}
+
+size_t checkLanesSlotBytes() { return kBatchLanes * sizeof(CheckSmallArgs); }
+bool checkLanesSupported(const MatView& A, const MatView& At) { return pickCheckLanes(A.csr.chunk, At.csr.chunk) != nullptr; }
+void fillCheckSmallLanes(const CheckLaneLaunch* lanes, int nLanes, void* hostSlot) {
+  CheckSmallArgs* out = static_cast<CheckSmallArgs*>(hostSlot);
+  for (int l = 0; l < kBatchLanes; ++l) {
+    if (l >= nLanes || lanes[l].grid <= 0) { out[l] = CheckSmallArgs{}; continue; }
+    const CheckLaneLaunch& q = lanes[l];
+    out[l] = checkSmallArgsOf(q.A, q.At, q.v, q.st, q.cc, q.rec, q.r, q.rowScale, q.colScale, q.scaled, q.spC, q.snC, q.spA, q.snA, q.statPart,
+                              q.statStride, q.statOut, q.partX, q.partY, q.bar, q.seq, q.timeoutMs);
+  }
+}
+void launchCheckSmallLanes(const CheckLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s) {
+  CheckLanesHdr h{};
+  h.nLanes = nLanes;
+  int maxG = 0, first = -1;
+  for (int l = 0; l < nLanes && l < kBatchLanes; ++l) {
+    h.grid[l] = lanes[l].grid > 0 ? lanes[l].grid : 0;
+    if (lanes[l].grid <= 0) continue;
+    if (first < 0) first = l;
+    if (lanes[l].grid > maxG) maxG = lanes[l].grid;
+  }
+  if (first < 0) return;
+  hipLaunchKernelGGL(pickCheckLanes(lanes[first].A.csr.chunk, lanes[first].At.csr.chunk), dim3(8 * maxG), dim3(kVecThreads), 0, s, h,
+                     static_cast<const CheckSmallArgs*>(devSlot));
 }
 
 }  // namespace pdlp

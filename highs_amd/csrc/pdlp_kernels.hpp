@@ -345,6 +345,28 @@ void launchSmallTrials(const MatView& A, const MatView& At, const IterVecs& v, D
                        double* partInter, unsigned long long* bar, int32_t grid, int32_t maxTrials, int mode, hipStream_t s,
                        int32_t timeoutMs = 1000, bool failRollCall = false, bool selfTest = false, unsigned long long seq = 1,
                        bool primalInA = false);
+// Up to eight XCD-local loops of DIFFERENT solvers of one problem in one launch (k_trials_small_lanes; pdlp_batch.hpp):
+// workgroup b of 8 * max(grid) works for lane b & 7 as its logical workgroup b >> 3, with that lane's own state, barrier
+// words and vectors.  A lane's record holds what launchSmallTrials takes (mode 1); grid = 0: the lane takes no part in this
+// launch.  The eight argument records of a launch lie in HBM: fill writes them into host memory (smallLanesSlotBytes()
+// bytes), the caller copies them to devSlot in stream order in front of the launch.
+constexpr int kBatchLanes = 8;
+struct SmallLaneLaunch {
+  MatView A, At;
+  IterVecs v;
+  DevState* st = nullptr;
+  double* partDY = nullptr;
+  double* partDX = nullptr;
+  double* partInter = nullptr;
+  unsigned long long* bar = nullptr;
+  int32_t grid = 0, maxTrials = 0, timeoutMs = 1000;
+  bool failRollCall = false, selfTest = false, primalInA = false;
+  unsigned long long seq = 1;
+};
+size_t smallLanesSlotBytes();
+bool smallLanesSupported(const MatView& A, const MatView& At, bool primalInA);
+void fillSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, void* hostSlot);
+void launchSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s);
 constexpr int kSmallHierWords = 4 * 16 * 32;  // the XCD-hierarchical barrier's words (pdlp_devfn.hpp HierBar)
 // arrival words, timeout flag, XCC ids of the placement check; behind them (256-byte aligned) the hierarchical barrier's words
 // ... and, last, the words of the XCD-local mode's coherence self-test (grid test words, grid arrival words, flag, failure word)
@@ -405,11 +427,39 @@ void launchDot(const double* a, const double* b, int32_t len, double* partials, 
 // bar: grid + 8 words zeroed when the solve starts; seq = 1, 2, ... counts the launches since.  A roll call that fails
 // (shared device) leaves everything untouched and sets commError = 3.
 int checkSmallResident(const MatView& A, const MatView& At, int device);
-struct RestartVecs;
+struct RestartVecs {  // the vectors of a restart (launchRestartVec below)
+  const double* xAvg; const double* yAvg; const double* axAvg; const double* atyAvg; const double* nxAvg;
+  double* xLast; double* yLast;
+};
 void launchCheckSmall(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, CheckCtl* cc, CheckRecord* rec,
                       const RestartVecs& r, const double* rowScale, const double* colScale, int scaled, double* spC, double* snC,
                       double* spA, double* snA, double* statPart, int32_t statStride, double* statOut, double* partX, double* partY,
                       unsigned long long* bar, int32_t grid, unsigned long long seq, int32_t timeoutMs, hipStream_t s);
+
+// The same for up to eight solvers of one problem in one launch (k_check_small_lanes; lane mapping, argument slot and the
+// fill / launch pair as for launchSmallTrialsLanes).  A lane's record holds what launchCheckSmall takes.
+struct CheckLaneLaunch {
+  MatView A, At;
+  IterVecs v;
+  DevState* st = nullptr;
+  CheckCtl* cc = nullptr;
+  CheckRecord* rec = nullptr;
+  RestartVecs r{};
+  const double* rowScale = nullptr;
+  const double* colScale = nullptr;
+  int scaled = 0;
+  double* spC = nullptr; double* snC = nullptr; double* spA = nullptr; double* snA = nullptr;
+  double* statPart = nullptr;
+  int32_t statStride = 0;
+  double* statOut = nullptr; double* partX = nullptr; double* partY = nullptr;
+  unsigned long long* bar = nullptr;
+  int32_t grid = 0, timeoutMs = 1000;
+  unsigned long long seq = 1;
+};
+size_t checkLanesSlotBytes();
+bool checkLanesSupported(const MatView& A, const MatView& At);
+void fillCheckSmallLanes(const CheckLaneLaunch* lanes, int nLanes, void* hostSlot);
+void launchCheckSmallLanes(const CheckLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s);
 
 // ---- the scalar side of a device-driven check (pdlp_check.hip) ------------------------------------------------------
 // stat: the 2*kRowStats + 2*kColStats statistics (launchFinalReduce2).  Residuals of both iterates, termination
@@ -418,10 +468,6 @@ void launchCheckDecide(DevState* st, CheckCtl* cc, const double* stat, CheckReco
 // If the check decided to restart: running sums cleared, average -> current iterate (restartKind 2), the partials of
 // ||x - xLast||^2 (nbX blocks, partX) and ||y - yLast||^2 (nbY blocks, partY) in the grids of launchDiffNorm2, and
 // xLast / yLast <- the restarted iterate (PDHG_Restart_Iterate_GPU, cupdlp_proj.c:88-148).  v / vCol: rows / own columns.
-struct RestartVecs {
-  const double* xAvg; const double* yAvg; const double* axAvg; const double* atyAvg; const double* nxAvg;
-  double* xLast; double* yLast;
-};
 void launchRestartVec(const IterVecs& v, const DevState* st, const CheckCtl* cc, const RestartVecs& r, double* partX, int32_t nbX,
                       double* partY, int32_t nbY, hipStream_t s);
 // Row-block sharded solve, restart to the average: launchRestartVec above works on a rank's own columns and rows; the

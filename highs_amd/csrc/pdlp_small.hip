@@ -321,8 +321,10 @@ __device__ __forceinline__ void smallLongBlock(const SmallArgs& a, const LongMat
 // PINA: no P phase — the gathers of phase A recompute x+ of their columns (primalOf), the owner of a column stores it
 // alongside; two barriers per trial instead of three.  A workgroup may then enter phase A of the next trial while another
 // still sums the (dy)^2 partials of this one: those alternate between two halves of partDY with the trial's parity.
+// The body of a launch for logical workgroup lb of G: shared by k_trials_small and k_trials_small_lanes (one lane of the
+// latter is, instruction for instruction, a launch of the former), so the two cannot differ.
 template <int CHUNK_A, int CHUNK_AT, int MODE, bool PINA>
-__global__ __launch_bounds__(kSpmvThreads) void k_trials_small(const SmallArgs a) {
+__device__ __forceinline__ void trialsSmallBody(const SmallArgs& a, const int lb, const int G) {
   constexpr bool LOCAL = MODE == 1;
   constexpr int kMaxChunk = CHUNK_A > CHUNK_AT ? CHUNK_A : CHUNK_AT;
   __shared__ double prod[kMaxChunk + kMaxChunk / 8 + 8];
@@ -333,9 +335,6 @@ __global__ __launch_bounds__(kSpmvThreads) void k_trials_small(const SmallArgs a
   __shared__ int hierN;
   __shared__ uint32_t hierActive;
   const int tid = threadIdx.x;
-  if (LOCAL && (blockIdx.x & 7) != 0) return;  // XCD-local: every eighth workgroup works
-  const int lb = LOCAL ? (int)blockIdx.x >> 3 : (int)blockIdx.x;      // logical workgroup
-  const int G = LOCAL ? (int)gridDim.x >> 3 : (int)gridDim.x;
   if (tid < (int)(sizeof(DevState) / 4)) reinterpret_cast<uint32_t*>(&sh)[tid] = reinterpret_cast<const uint32_t*>(a.st)[tid];
   padSlots(prod, kMaxChunk + kMaxChunk / 8 + 8, tid, kSpmvThreads);  // (never written again)
   __syncthreads();
@@ -561,6 +560,38 @@ __global__ __launch_bounds__(kSpmvThreads) void k_trials_small(const SmallArgs a
   if (lb == 0 && tid < (int)(sizeof(DevState) / 4)) reinterpret_cast<uint32_t*>(a.st)[tid] = reinterpret_cast<const uint32_t*>(&sh)[tid];
 }
 
+template <int CHUNK_A, int CHUNK_AT, int MODE, bool PINA>
+__global__ __launch_bounds__(kSpmvThreads) void k_trials_small(const SmallArgs a) {
+  constexpr bool LOCAL = MODE == 1;
+  if (LOCAL && (blockIdx.x & 7) != 0) return;  // XCD-local: every eighth workgroup works
+  const int lb = LOCAL ? (int)blockIdx.x >> 3 : (int)blockIdx.x;      // logical workgroup
+  const int G = LOCAL ? (int)gridDim.x >> 3 : (int)gridDim.x;
+  trialsSmallBody<CHUNK_A, CHUNK_AT, MODE, PINA>(a, lb, G);
+}
+
+// Up to eight INDEPENDENT XCD-local loops in one launch (pdlp_batch.hpp): workgroup b works for lane b & 7 as that lane's
+// logical workgroup b >> 3, so under the dispatch order the XCD-local mode relies on lane L's workers share XCD L — which
+// every lane CHECKS for its own workers exactly as a solo launch does (the XCC ids behind its own arrival words).  A lane
+// reads and writes only its own state record, barrier words, partials and vectors; lanes never wait for each other.
+// The eight argument records lie in HBM (lanes[0..8), written by the host in front of the launch): 8 x 520 bytes do not
+// fit the 4 KB kernel-argument segment.  They are read through the constant address space — nobody writes them while a
+// launch that reads them is queued — so that, as with kernel arguments, every field is a scalar load that can be repeated
+// instead of being kept in a register.
+struct SmallLanesHdr {
+  int32_t nLanes;
+  int32_t grid[8];  // workgroups of each lane in THIS launch (0: the lane takes no part)
+};
+template <int CHUNK_A, int CHUNK_AT, bool PINA>
+__global__ __launch_bounds__(kSpmvThreads) void k_trials_small_lanes(const SmallLanesHdr h, const SmallArgs* __restrict__ lanes) {
+  const int lane = (int)blockIdx.x & 7, lb = (int)blockIdx.x >> 3;
+  if (lane >= h.nLanes) return;
+  const int G = h.grid[lane];
+  if (lb >= G) return;
+  typedef const SmallArgs __attribute__((address_space(4))) * ConstArgs;
+  const SmallArgs& a = *(const SmallArgs*)((ConstArgs)lanes + lane);
+  trialsSmallBody<CHUNK_A, CHUNK_AT, 1, PINA>(a, lb, G);
+}
+
 using SmallKernel = void (*)(const SmallArgs);
 template <bool PINA>
 SmallKernel pickT(int chunkA, int chunkAt, int mode) {
@@ -577,6 +608,27 @@ SmallKernel pickT(int chunkA, int chunkAt, int mode) {
   return nullptr;
 }
 SmallKernel pick(int chunkA, int chunkAt, int mode, bool pina = false) { return pina ? pickT<true>(chunkA, chunkAt, mode) : pickT<false>(chunkA, chunkAt, mode); }
+// (lanes: XCD-local mode only, which exists for the 512-entry blocks only)
+using SmallLanesKernel = void (*)(const SmallLanesHdr, const SmallArgs*);
+SmallLanesKernel pickLanes(int chunkA, int chunkAt, bool pina) {
+  if (chunkA != kChunkSmall || chunkAt != kChunkSmall) return nullptr;
+  return pina ? k_trials_small_lanes<kChunkSmall, kChunkSmall, true> : k_trials_small_lanes<kChunkSmall, kChunkSmall, false>;
+}
+
+// the argument record of one launch (everything but the development profile)
+SmallArgs smallArgsOf(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, double* partDY, double* partDX,
+                      double* partInter, unsigned long long* bar, int32_t grid, int32_t maxTrials, int mode, int32_t timeoutMs,
+                      bool failRollCall, bool selfTest, unsigned long long seq, bool primalInA) {
+  SmallArgs a{};
+  a.expect = (mode == 2 ? (unsigned long long)grid : seq * (unsigned long long)grid) + (failRollCall ? 1ull : 0ull);
+  a.selfTest = mode == 1 && selfTest ? 1 : 0;
+  a.primalInA = primalInA ? 1 : 0;
+  a.limit = (unsigned long long)(timeoutMs > 0 ? timeoutMs : 1000) * 100000ull;
+  a.LA = A.lng; a.LAt = At.lng; a.nPartA = A.nPartials; a.nPartAt = At.nPartials;
+  a.A = A.csr; a.At = At.csr; a.v = v; a.st = st; a.partDY = partDY; a.partDX = partDX; a.partInter = partInter; a.bar = bar;
+  a.xcdA = A.xcdMap; a.xcdAt = At.xcdMap; a.maxTrials = maxTrials;
+  return a;
+}
 
 }  // namespace
 
@@ -610,16 +662,9 @@ void launchSmallTrials(const MatView& A, const MatView& At, const IterVecs& v, D
   // keep their words — arrival epochs grow with the trial counter, the roll-call count with the launches (seq = 1, 2, ...
   // since the caller zeroed the buffer), so no memset launch sits between two launches of the loop
   if (mode == 2) (void)hipMemsetAsync(bar, 0, smallBarWords(grid) * sizeof(unsigned long long), s);
-  SmallArgs a{};
-  a.expect = (mode == 2 ? (unsigned long long)grid : seq * (unsigned long long)grid) + (failRollCall ? 1ull : 0ull);
-  a.selfTest = xcdLocal && selfTest ? 1 : 0;
-  a.primalInA = primalInA ? 1 : 0;
+  SmallArgs a = smallArgsOf(A, At, v, st, partDY, partDX, partInter, bar, grid, maxTrials, mode, timeoutMs, failRollCall, selfTest, seq, primalInA);
   if (a.selfTest)  // its words: the tail of the buffer
     (void)hipMemsetAsync(bar + smallBarWords(grid) - (size_t)(2 * grid + 8), 0, (size_t)(2 * grid + 8) * sizeof(unsigned long long), s);
-  a.limit = (unsigned long long)(timeoutMs > 0 ? timeoutMs : 1000) * 100000ull;
-  a.LA = A.lng; a.LAt = At.lng; a.nPartA = A.nPartials; a.nPartAt = At.nPartials;
-  a.A = A.csr; a.At = At.csr; a.v = v; a.st = st; a.partDY = partDY; a.partDX = partDX; a.partInter = partInter; a.bar = bar;
-  a.xcdA = A.xcdMap; a.xcdAt = At.xcdMap; a.maxTrials = maxTrials;
   static unsigned long long* prof = [] {  // PDLP_MI355X_SMALL_PROF=1: per-phase ticks, printed at exit (development)
     unsigned long long* p = nullptr;
     if (devEnv("PDLP_MI355X_SMALL_PROF") && hipMalloc((void**)&p, 64) == hipSuccess) {
@@ -636,6 +681,36 @@ void launchSmallTrials(const MatView& A, const MatView& At, const IterVecs& v, D
   }();
   a.prof = prof;
   hipLaunchKernelGGL(pick(A.csr.chunk, At.csr.chunk, mode, primalInA), dim3(xcdLocal ? 8 * grid : grid), dim3(kSpmvThreads), 0, s, a);
+}
+
+size_t smallLanesSlotBytes() { return kBatchLanes * sizeof(SmallArgs); }
+bool smallLanesSupported(const MatView& A, const MatView& At, bool primalInA) { return pickLanes(A.csr.chunk, At.csr.chunk, primalInA) != nullptr; }
+void fillSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, void* hostSlot) {
+  SmallArgs* out = static_cast<SmallArgs*>(hostSlot);
+  for (int l = 0; l < kBatchLanes; ++l) {
+    if (l >= nLanes || lanes[l].grid <= 0) { out[l] = SmallArgs{}; continue; }
+    const SmallLaneLaunch& q = lanes[l];
+    out[l] = smallArgsOf(q.A, q.At, q.v, q.st, q.partDY, q.partDX, q.partInter, q.bar, q.grid, q.maxTrials, 1, q.timeoutMs, q.failRollCall,
+                         q.selfTest, q.seq, q.primalInA);
+  }
+}
+void launchSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s) {
+  SmallLanesHdr h{};
+  h.nLanes = nLanes;
+  int maxG = 0, first = -1;
+  for (int l = 0; l < nLanes && l < kBatchLanes; ++l) {
+    const SmallLaneLaunch& q = lanes[l];
+    h.grid[l] = q.grid > 0 ? q.grid : 0;
+    if (q.grid <= 0) continue;
+    if (first < 0) first = l;
+    if (q.grid > maxG) maxG = q.grid;
+    if (q.selfTest)  // the self-test's words: the tail of the lane's buffer
+      (void)hipMemsetAsync(q.bar + smallBarWords(q.grid) - (size_t)(2 * q.grid + 8), 0, (size_t)(2 * q.grid + 8) * sizeof(unsigned long long), s);
+  }
+  if (first < 0) return;
+  const SmallLaneLaunch& f = lanes[first];  // (one problem: every lane has the chunks and the variant of the first)
+  hipLaunchKernelGGL(pickLanes(f.A.csr.chunk, f.At.csr.chunk, f.primalInA), dim3(8 * maxG), dim3(kSpmvThreads), 0, s, h,
+                     static_cast<const SmallArgs*>(devSlot));
 }
 
 }  // namespace pdlp

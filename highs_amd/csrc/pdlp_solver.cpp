@@ -1595,6 +1595,8 @@ void Solver::runUntilHalt() {
   }
 }
 
+int32_t Solver::defaultCheckInterval() { return kCheckInterval; }
+
 int32_t Solver::nextCheckIter(int32_t it) const {
   const int32_t interval = opt_.check_interval > 0 ? opt_.check_interval : kCheckInterval;
   int64_t next;
@@ -2012,6 +2014,13 @@ void Solver::doSolveDevice(bool terminate, int32_t target) {
     else if (units > 0 && roundMs > 0.0) aheadMax = std::max(1, std::min(16, (int32_t)(25.0 * units / roundMs)));
     ahead = std::min(ahead * 2, aheadMax);
   }
+  endDeviceLoop(terminate, timeUp, logSinceHeader);
+}
+
+// The end of a device-driven loop (doSolveDevice; a batch lane, pdlp_batch_lanes.cpp): the control record back to the host's
+// mirrors and, after the time limit, the check the reference makes at once.
+void Solver::endDeviceLoop(bool terminate, bool timeUp, int& logSinceHeader) {
+  DevState& s = *hostState_;
   downloadCtl();
   if (timeUp) {
     // The time limit: the reference checks at once and stops (cupdlp_solver.c:953-962).  The device stands right behind
@@ -2091,6 +2100,11 @@ void Solver::run(pdlp_result_t* R) {
   if (hasStart_) log(1, "Hot starting with given column primal values and row dual values\n");
   if (devCheck_ && !profile_) doSolveDevice(true, 0);
   else doSolve(true, 0);
+  finishRun(R);
+}
+
+// What run() does behind its loop (a batch lane ends its run here too): the summary and the post-solve.
+void Solver::finishRun(pdlp_result_t* R) {
   solveSeconds_ = elapsed();
   if (opt_.log_level > 0 && rank_ == 0) {
     const Residuals& r = (termCode_ == PDLP_TERM_OPTIMAL && termIterate_ == 1) ? avg_ : cur_;
@@ -2358,6 +2372,8 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     put(0, !devCheck_ ? 0.0 : sharded_ ? (mesh_ && mesh_->args().fusedWait == 2 ? 14.0 : 26.0) + (hasQoff_ ? 1.0 : 0.0) : persistent_ && checkSmall_ ? 1.0 : 10.0);
   } else if (name == "barrier_fallbacks") {  // times a launch with grid barriers gave up and the loop went on with plain launches
     put(0, (double)barrierFallbacks_);
+  } else if (name == "persistent_launches") {  // persistent trial launches enqueued since create (no-ops behind a termination included)
+    put(0, (double)smallLaunches_);
   } else if (name == "uniform_bound_columns") {  // columns whose lower / upper bound the fused launch takes from a scalar of their block
     put(0, (double)uniLowerCols_); put(1, (double)uniUpperCols_);
   } else if (name == "exchange") {  // 0 = not sharded, 1 = RCCL all-reduce, 3 = direct xGMI mesh, two all-gathers (2 was the removed partials layout)

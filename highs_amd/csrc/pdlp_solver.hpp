@@ -90,6 +90,8 @@ float tuneXcdMap(DeviceMatrix& M, const DevSwitches& sw, const double* in, doubl
 void buildSlabTuned(DeviceMatrix& out, DeviceCsrData& M, const DevSwitches& sw, hipStream_t s);
 
 class Comm;  // RCCL wrapper (pdlp_comm.cpp)
+struct LaneUnit;           // pdlp_batch.hpp
+enum LaneVerdict : int;    // pdlp_batch.hpp
 
 // Host copy of cuPDLP's CUPDLPresobj numbers for one iterate.
 struct Residuals {
@@ -156,6 +158,31 @@ class Solver : public SolverBase {
   void sessionCommit();
   size_t sessionHeldBytes() const;  // HBM kept for reuse beyond a plain solver's
 
+  // ---- what a batch drives (pdlp_batch.hpp; all in pdlp_batch_lanes.cpp) ----
+  // run() cut into the steps of ONE lane of a batch, whose launches are shared with other solvers of the same problem:
+  // laneBegin = run() up to its first round; laneQueue = the units [trial batch][check] of the next round as
+  // doSolveDevice would enqueue them, handed out as launch records and accounted for as if launched (units[0] may be the
+  // entry's check alone); laneDownload / laneAfterRound = syncState + processRecords + the loop's tail; laneFinish = what
+  // run() does behind its loop.  Between laneBegin and laneFinish nothing else may be asked of the solver.
+  // laneSequentialReason: empty, or why this solver's launches cannot be shared (it then runs alone)
+  std::string laneSequentialReason() const;
+  int32_t laneWorkBlocks() const { return smallGrid_; }
+  static int32_t defaultCheckInterval();  // CUPDLP_RELEASE_INTERVAL
+  // the refusals of update(u) that do not depend on the device, with update's words; nothing is changed
+  void validateUpdate(const pdlp_update_t& u) const;
+  void laneBegin();
+  bool laneIdle() const { return lane_.noLoop; }  // the iteration limit is reached before the first round: laneFinish may follow at once
+  void laneQueue(int32_t ahead, std::vector<LaneUnit>& units);
+  void laneDownload(hipStream_t shared);  // the state record -> host mirror, behind the round's launches
+  LaneVerdict laneAfterRound();           // (the shared stream has been synchronised)
+  int32_t laneCommError() const { return lane_.commError; }
+  int32_t laneXcc();                      // the XCC id this solver's workers published at their last placement check, or -1
+  void laneFinish(pdlp_result_t* R);
+  hipStream_t laneStream() const { return stream_; }
+  // the device gate for a round of shared launches on this solver's stream (BarrierRound of doSolveDevice)
+  std::unique_lock<std::mutex> laneBeginRound() { return beginBarrierRound(); }
+  void laneEndRound(std::unique_lock<std::mutex>& gate) { endBarrierRound(gate); }
+
  private:
   // setup
   void construct(const pdlp_problem_t& P, const void* id128);
@@ -201,6 +228,8 @@ class Solver : public SolverBase {
   int32_t nextCheckIter(int32_t it) const;
   void doSolve(bool terminate, int32_t iterBudget);        // check iterations driven by the host (sharded paths, profile mode)
   void doSolveDevice(bool terminate, int32_t iterBudget);  // check iterations on the device, several periods queued ahead
+  void endDeviceLoop(bool terminate, bool timeUp, int& logSinceHeader);
+  void finishRun(pdlp_result_t* R);
   void enqueueCheckDevice();
   void uploadCtl(bool terminate, int64_t iterLim);
   void downloadCtl();
@@ -332,6 +361,12 @@ class Solver : public SolverBase {
     ~BarrierRound();
   };
   int32_t stalledRounds_ = 0, stalledSince_ = 0;  // consecutive device stops without an accepted trial
+  struct LaneRun {  // the locals of doSolveDevice for a run driven as a batch lane
+    int64_t iterLim = 0, seq0 = 0;
+    int32_t iterBefore = 0, trialsBefore = 0, commError = 0;
+    int logSinceHeader = 50;
+    bool noLoop = false, timeUp = false;
+  } lane_;
   // Device-driven check iterations (pdlp_kernels.hpp CheckCtl; PDLP_MI355X_DEVICE_CHECK=0 gives the host-driven loop back)
   bool devCheck_ = true;
   DeviceArray<CheckCtl> dCtl_;

@@ -48,6 +48,8 @@ EXPORTS = [
     "pdlp_mi355x_update_values", "pdlp_mi355x_host_prepare_qp", "pdlp_mi355x_free_prepared_hessian",
     "pdlp_mi355x_session_create", "pdlp_mi355x_session_solve", "pdlp_mi355x_session_info", "pdlp_mi355x_session_release",
     "pdlp_mi355x_session_destroy", "pdlp_mi355x_session_info_size", "pdlp_mi355x_host_classify",
+    "pdlp_mi355x_batch_create", "pdlp_mi355x_batch_run", "pdlp_mi355x_batch_info", "pdlp_mi355x_batch_destroy",
+    "pdlp_mi355x_batch_info_size",
 ]
 
 
@@ -120,6 +122,18 @@ def lib():
         if L.pdlp_mi355x_session_info_size() != C.sizeof(abi.PdlpSessionInfo):
             raise RuntimeError("pdlp_session_info_t: the library's size %d differs from abi.PdlpSessionInfo's %d" %
                                (L.pdlp_mi355x_session_info_size(), C.sizeof(abi.PdlpSessionInfo)))
+        # (a build from before the batches, given through PDLP_MI355X_LIB, has none: tools/batch_bench.py's sequential side)
+        if hasattr(L, "pdlp_mi355x_batch_create"):
+            pB = C.POINTER(abi.PdlpBatchInfo)
+            L.pdlp_mi355x_batch_create.argtypes = [pP, pO, C.c_int32, C.POINTER(H)]
+            L.pdlp_mi355x_batch_run.argtypes = [H, C.c_int32, pU, pR]
+            L.pdlp_mi355x_batch_info.argtypes = [H, pB]
+            L.pdlp_mi355x_batch_destroy.argtypes = [H]
+            L.pdlp_mi355x_batch_destroy.restype = None
+            L.pdlp_mi355x_batch_info_size.restype = C.c_int64
+            if L.pdlp_mi355x_batch_info_size() != C.sizeof(abi.PdlpBatchInfo):
+                raise RuntimeError("pdlp_batch_info_t: the library's size %d differs from abi.PdlpBatchInfo's %d" %
+                                   (L.pdlp_mi355x_batch_info_size(), C.sizeof(abi.PdlpBatchInfo)))
         L.pdlp_mi355x_row_partition.argtypes = [pPrep, C.c_int32, abi.c_i32p]
         pSlab = C.POINTER(abi.PdlpSlabLayout)
         L.pdlp_mi355x_host_slab_layout.argtypes = [pPrep, C.c_int32, C.c_int32, pSlab]
@@ -536,6 +550,80 @@ class DeviceSolver:
         ms = C.c_double()
         _check(lib().pdlp_mi355x_time_kernel(self.h, name.encode(), reps, C.byref(ms)), "time " + name)
         return ms.value
+
+
+class DeviceBatch:
+    """pdlp_mi355x_batch_*: `lanes` (1..8) resident solvers of one LP; run() solves a list of variants of it — each a dict
+    of DeviceSolver.update's arguments (col_cost, col_lower, col_upper, row_lower, row_upper, offset, start; {} = the LP as
+    it is) plus, optionally, iter_limit for that variant alone — and returns one PdlpOutcome per variant, bit for bit what
+    `DeviceSolver(lp, updatable=True, **options)` gives for update(**variant) + solve().  Where the LP's trial loop runs
+    XCD-local the variants run at once, one per XCD (include/pdlp_mi355x.h; info().text says how the last run went)."""
+
+    def __init__(self, lp, lanes=8, params=None, **options):
+        self.params = params or abi.default_params(**options)
+        self.lp = lp
+        self._keep = abi.ProblemHandle(lp)
+        if self._keep.wide:
+            raise ValueError("batches take 32-bit column starts")
+        self.h = C.c_void_p()
+        _check(lib().pdlp_mi355x_batch_create(C.byref(self._keep.struct), C.byref(self.params), int(lanes), C.byref(self.h)),
+               "pdlp_mi355x_batch_create")
+
+    def run(self, variants):
+        import copy
+        K = len(variants)
+        handles, lps, limits = [], [], []
+        U = (abi.PdlpUpdate * max(K, 1))()
+        Rs = (abi.PdlpResult * max(K, 1))()
+        results = []
+        for k, v in enumerate(variants):
+            v = dict(v)
+            limit = v.pop("iter_limit", None)
+            hnd = abi.UpdateHandle(**v)
+            if limit is not None:
+                hnd.struct.reserved = int(limit)
+            handles.append(hnd)
+            U[k] = hnd.struct
+            limits.append(self.params.iter_limit if limit is None else int(limit))
+            lp = copy.copy(self.lp)
+            for name in ("col_cost", "col_lower", "col_upper", "row_lower", "row_upper"):
+                if v.get(name) is not None:
+                    setattr(lp, name, np.array(v[name], dtype=np.float64))
+            if v.get("offset") is not None:
+                lp.offset = float(v["offset"])
+            lps.append(lp)
+            R = abi.ResultHandle(self.lp.num_col, self.lp.num_row)
+            results.append(R)
+            Rs[k] = R.struct
+        _check(lib().pdlp_mi355x_batch_run(self.h, K, U, Rs), "pdlp_mi355x_batch_run")
+        out = []
+        for k in range(K):
+            results[k].struct = Rs[k]
+            R, lp = results[k], lps[k]
+            ms = model_status_from_term(R.term_code, R.num_iter, limits[k], 0)
+            sol = HighsSolution(R.col_value, R.col_dual, R.row_value, R.row_dual, bool(R.value_valid), bool(R.dual_valid))
+            info = kkt_measures(lp, sol.col_value, sol.col_dual, sol.row_value, sol.row_dual)
+            info["pdlp_iteration_count"] = int(R.num_iter)
+            status = kOk if ms == kOptimal or ms == kUnboundedOrInfeasible else kWarning
+            out.append(PdlpOutcome(status, ms, sol, int(R.num_iter), info, R))
+        return out
+
+    def info(self):
+        """About the last run."""
+        I = abi.PdlpBatchInfo()
+        _check(lib().pdlp_mi355x_batch_info(self.h, C.byref(I)), "pdlp_mi355x_batch_info")
+        return I
+
+    def close(self):
+        if self.h:
+            lib().pdlp_mi355x_batch_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class SyntheticProblem:

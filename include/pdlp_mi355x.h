@@ -203,7 +203,7 @@ typedef struct pdlp_update {
   const double* row_lower;  /* [num_row]  NULL = unchanged; lower and upper are given together or not at all */
   const double* row_upper;
   double offset; int32_t has_offset; /* offset is taken only when has_offset != 0 */
-  int32_t reserved;
+  int32_t reserved;  /* pdlp_mi355x_batch_run: > 0 = this variant's iteration limit in place of opt->iter_limit; ignored elsewhere */
   /* start of the next run: all three NULL = cold start (as create without a hot start);
      all three given = hot start with the meaning of pdlp_problem_t.start_* when both valid flags are set */
   const double* start_col_value; const double* start_row_value; const double* start_row_dual;
@@ -341,6 +341,51 @@ int pdlp_mi355x_session_info(const pdlp_mi355x_session_t* S, pdlp_session_info_t
 void pdlp_mi355x_session_release(pdlp_mi355x_session_t* S); /* drop the held solver, keep the session */
 void pdlp_mi355x_session_destroy(pdlp_mi355x_session_t* S);
 int64_t pdlp_mi355x_session_info_size(void); /* sizeof(pdlp_session_info_t); pdlp_mi355x_sizeof keeps its indices */
+
+/* ---- batches: up to eight variants of one small LP solved at once, one per XCD ------------------
+ * For callers with ONE matrix and MANY data sets (scenario sweeps, parametrics, the children of a branch-and-bound node).
+ * A batch holds `lanes` (1..8) resident solvers of one problem P (algorithm 0, one device), each created as
+ * pdlp_mi355x_create(P, opt') with opt' = opt | PDLP_UPDATABLE_DATA.  pdlp_mi355x_batch_run solves K >= 1 variants:
+ * variant k is P with u[k] applied — meaning, checks and messages of pdlp_mi355x_update; u[k] may carry a start, and
+ * u[k].reserved > 0 is an iteration limit of its own.  R[k] is caller-allocated as for pdlp_mi355x_run.
+ *
+ * THE CONTRACT: R[k] is, bit for bit — every solution vector, every count, every scalar except setup_seconds and
+ * solve_seconds — what ONE held solver s, created with opt' on P (and with variant k's iteration limit), gives for
+ * pdlp_mi355x_update(s, &u[k]) followed by pdlp_mi355x_run: by the update's own contract, a fresh create on the modified
+ * problem.  For every K, every lane count and every order in which the variants happen to finish.
+ *
+ * Where the trial loop of P runs XCD-local (at most 32 work blocks: Netlib-class LPs) the lanes' loops and checks share
+ * launches, lane L on XCD L, and a lane whose variant has ended takes the next one while the others carry on.  Nothing is
+ * synchronised between variants; time and iteration limits count per variant, from its own start.  Everywhere else
+ * batch_run is a loop of update + run on one lane; pdlp_batch_info_t.reason says which, and why.
+ *   * All u[k] are validated before anything is changed; a refusal names the variant ("variant 3: ...", then update's
+ *     words) and leaves the batch as it was.
+ *   * HiPDLP, more than one device, forced sharding and lanes outside 1..8 are refused at create, before any device call.
+ *   * A lane whose workgroups of a shared launch were not placed on one XCD, not resident together or did not meet at a
+ *     barrier leaves the shared launches for good; its variant is re-solved alone through the ordinary run
+ *     (fallback_variants counts them).
+ *   * With log_level >= 1 every log line carries a "[variant k] " prefix.
+ * THREADING: one thread uses a batch at a time. */
+typedef struct pdlp_batch_info { /* about the last pdlp_mi355x_batch_run */
+  int32_t lanes;             /* solvers held */
+  int32_t lanes_concurrent;  /* how many ran inside shared launches at once; 1 = one after the other */
+  int32_t variants;
+  int32_t trial_launches;    /* shared launches issued: trial loops, */
+  int32_t check_launches;    /* checks */
+  int32_t fallback_variants; /* variants re-solved alone after their lane left the shared launches */
+  int32_t xcc_of_lane[8];    /* the XCC id each lane's workers published, or -1 */
+  int32_t reserved[2];
+  double wall_seconds;
+  char reason[160];          /* NUL-terminated, e.g. "concurrent: 8 lanes, 21 workgroups each" or
+                                "sequential: 48 work blocks need more than one XCD" */
+} pdlp_batch_info_t;
+typedef struct pdlp_mi355x_batch pdlp_mi355x_batch_t; /* opaque */
+int pdlp_mi355x_batch_create(const pdlp_problem_t* P, const pdlp_params_t* opt, int32_t lanes, pdlp_mi355x_batch_t** out);
+int pdlp_mi355x_batch_run(pdlp_mi355x_batch_t* B, int32_t K, const pdlp_update_t* u, pdlp_result_t* R);
+int pdlp_mi355x_batch_info(const pdlp_mi355x_batch_t* B, pdlp_batch_info_t* out);
+void pdlp_mi355x_batch_destroy(pdlp_mi355x_batch_t* B);
+int64_t pdlp_mi355x_batch_info_size(void); /* sizeof(pdlp_batch_info_t); pdlp_mi355x_sizeof keeps its indices */
+
 /* Host-only restatement of the session's decision for the CPU tests: `held` / held_opt are the problem and options of the
  * previous call (held == NULL: nothing is held), P / opt those of this one.  Same ladder (one function shared with the
  * session), same changed mask, same reason words; the four timings and held_bytes are 0. */
