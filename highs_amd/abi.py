@@ -179,6 +179,35 @@ class PdlpBatchInfo(C.Structure):
         return self.reason.decode()
 
 
+# pdlp_mi355x_solve_many: path[k] (include/pdlp_mi355x.h)
+POOL_NOT_RUN, POOL_SHARED, POOL_ALONE, POOL_FALLBACK = range(4)
+
+
+class PdlpPoolInfo(C.Structure):
+    """pdlp_pool_info_t (include/pdlp_mi355x.h): what a pdlp_mi355x_solve_many did; its size is checked against
+    pdlp_mi355x_pool_info_size()."""
+    _fields_ = [
+        ("problems", C.c_int32),
+        ("lanes", C.c_int32),
+        ("lanes_concurrent", C.c_int32),
+        ("shared_problems", C.c_int32),
+        ("alone_problems", C.c_int32),
+        ("fallback_problems", C.c_int32),
+        ("trial_launches", C.c_int32),
+        ("check_launches", C.c_int32),
+        ("mixed_launches", C.c_int32),
+        ("xcc_of_lane", C.c_int32 * 8),
+        ("reserved", C.c_int32 * 3),
+        ("wall_seconds", C.c_double),
+        ("create_seconds", C.c_double),
+        ("reason", C.c_char * 160),
+    ]
+
+    @property
+    def text(self):
+        return self.reason.decode()
+
+
 class PdlpIterStats(C.Structure):
     _fields_ = [
         ("iters", C.c_int32),

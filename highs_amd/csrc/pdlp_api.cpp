@@ -15,6 +15,7 @@
 #include "pdlp_batch.hpp"
 #include "pdlp_halpern.hpp"
 #include "pdlp_mps.hpp"
+#include "pdlp_pool.hpp"
 #include "pdlp_session.hpp"
 #include "pdlp_solver.hpp"
 #include "pdlp_update.hpp"
@@ -679,6 +680,14 @@ void pdlp_mi355x_batch_destroy(pdlp_mi355x_batch_t* B) {
 }
 
 int64_t pdlp_mi355x_batch_info_size(void) { return sizeof(pdlp_batch_info_t); }
+
+// ---- pools (pdlp_pool.hpp) ----------------------------------------------------------------------------------------------
+int pdlp_mi355x_solve_many(int32_t K, const pdlp_problem_t* const* P, const pdlp_params_t* opt, int32_t lanes, pdlp_result_t* R,
+                           int32_t* path, pdlp_pool_info_t* info) {
+  return guarded([&] { pdlp::solveMany(K, P, opt, lanes, R, path, info); });  // (the refusals come before any HIP call)
+}
+
+int64_t pdlp_mi355x_pool_info_size(void) { return sizeof(pdlp_pool_info_t); }
 
 // Host twin of the session's decision: what the device finds by streaming the staged arrays against the kept ones is
 // found here by walking the two problems; the ladder is the session's own.

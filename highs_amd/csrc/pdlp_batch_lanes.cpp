@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "pdlp_batch.hpp"
+#include "pdlp_pool.hpp"
 #include "pdlp_session.hpp"
 #include "pdlp_solver.hpp"
 #include "pdlp_update.hpp"
@@ -182,25 +183,6 @@ void Solver::laneFinish(pdlp_result_t* R) {
 
 namespace {
 
-// Log lines of a lane: "[variant k] " in front of every line, then the caller's sink (NULL: stdout).
-struct LogTap {
-  void (*sink)(void*, int, const char*) = nullptr;
-  void* sinkCtx = nullptr;
-  std::string prefix;
-  bool lineStart = true;
-  static void write(void* ctx, int level, const char* text) {
-    LogTap& t = *static_cast<LogTap*>(ctx);
-    std::string out;
-    for (const char* p = text; *p; ++p) {
-      if (t.lineStart && *p != '\n') out += t.prefix;
-      t.lineStart = *p == '\n';
-      out += *p;
-    }
-    if (t.sink) t.sink(t.sinkCtx, level, out.c_str());
-    else { fputs(out.c_str(), stdout); fflush(stdout); }
-  }
-};
-
 // The data of P that an update can change, kept on the host: variant k is P with u[k] applied, whatever variant the lane
 // solved before — so what an earlier variant changed on a lane and this one leaves alone goes back to P's values.
 struct BaseData {
@@ -267,73 +249,20 @@ class SolverLane : public BatchLane {
   LogTap tap_;
 };
 
-// The rounds on the device.  Everything of a round goes to lane 0's stream, behind one take of the device gate; the
-// argument records of all its launches are written into pinned host memory first and reach HBM in one copy.
+// The rounds on the device: LaneRounds (pdlp_pool.hpp) on lane 0's stream, behind the gate of lane 0's device.
 class DeviceBackend : public BatchBackend {
  public:
-  explicit DeviceBackend(std::vector<Solver*> solvers) : solvers_(std::move(solvers)) {
-    slotT_ = smallLanesSlotBytes();
-    slotC_ = checkLanesSlotBytes();
-    const size_t bytes = (size_t)kMaxUnits * (slotT_ + slotC_);
-    PDLP_HIP(hipHostMalloc(&host_, bytes, hipHostMallocDefault));
-    PDLP_HIP(hipMalloc(&dev_, bytes));
-  }
-  ~DeviceBackend() override {
-    if (host_) (void)hipHostFree(host_);
-    if (dev_) (void)hipFree(dev_);
-  }
+  DeviceBackend(std::vector<Solver*> solvers, int32_t device)
+      : solvers_(std::move(solvers)), device_(device), rounds_("pdlp_mi355x_batch_run") {}
   void round(const std::vector<LaneUnit>* units, int nLanes, int32_t* trialLaunches, int32_t* checkLaunches) override {
-    size_t J = 0;
-    for (int l = 0; l < nLanes; ++l) J = std::max(J, units[l].size());
-    if (J == 0) return;
-    if (J > (size_t)kMaxUnits) throw std::runtime_error("pdlp_mi355x_batch_run: more units in a round than argument slots");
-    std::vector<SmallLaneLaunch> tl(J * kBatchLanes);
-    std::vector<CheckLaneLaunch> cl(J * kBatchLanes);
-    std::vector<char> anyTrials(J, 0);
-    char* hostT = static_cast<char*>(host_);
-    char* hostC = hostT + J * slotT_;
-    for (size_t j = 0; j < J; ++j) {
-      for (int l = 0; l < nLanes; ++l) {
-        if (j >= units[l].size()) continue;  // (grid 0: the lane takes no part in launch j)
-        const LaneUnit& q = units[l][j];
-        if (q.hasTrials) { tl[j * kBatchLanes + l] = q.trials; anyTrials[j] = 1; }
-        cl[j * kBatchLanes + l] = q.check;
-      }
-      fillSmallTrialsLanes(&tl[j * kBatchLanes], nLanes, hostT + j * slotT_);
-      fillCheckSmallLanes(&cl[j * kBatchLanes], nLanes, hostC + j * slotC_);
-    }
-    Solver& first = *solvers_[0];
-    hipStream_t s = first.laneStream();
-    const char* devT = static_cast<const char*>(dev_);
-    const char* devC = devT + J * slotT_;
-    std::unique_lock<std::mutex> gate = first.laneBeginRound();
-    try {
-      PDLP_HIP(hipMemcpyAsync(dev_, host_, J * (slotT_ + slotC_), hipMemcpyHostToDevice, s));
-      for (size_t j = 0; j < J; ++j) {
-        if (anyTrials[j]) {
-          launchSmallTrialsLanes(&tl[j * kBatchLanes], nLanes, devT + j * slotT_, s);
-          ++*trialLaunches;
-        }
-        launchCheckSmallLanes(&cl[j * kBatchLanes], nLanes, devC + j * slotC_, s);
-        ++*checkLaunches;
-      }
-    } catch (...) {  // the end of the round is marked on every way out (Solver::BarrierRound)
-      try { first.laneEndRound(gate); } catch (...) {}
-      throw;
-    }
-    first.laneEndRound(gate);
-    for (int l = 0; l < nLanes; ++l)
-      if (!units[l].empty()) solvers_[l]->laneDownload(s);
-    PDLP_HIP(hipStreamSynchronize(s));
-    PDLP_HIP(hipGetLastError());  // a launch that failed (bad grid, LDS request, ...) surfaces here
+    int32_t mixed = 0;  // (one problem: never)
+    rounds_.round(units, solvers_.data(), nLanes, device_, solvers_[0]->laneStream(), trialLaunches, checkLaunches, &mixed);
   }
 
  private:
-  static constexpr int kMaxUnits = 20;  // a round queues the entry's check and at most 16 units per lane
   std::vector<Solver*> solvers_;
-  size_t slotT_ = 0, slotC_ = 0;
-  void* host_ = nullptr;
-  void* dev_ = nullptr;
+  int32_t device_;
+  LaneRounds rounds_;
 };
 
 }  // namespace
@@ -370,7 +299,7 @@ Batch::Batch(const pdlp_problem_t& P, const pdlp_params_t& opt, int32_t lanes) :
     ls.push_back(impl_->lanes.back().get());
     ss.push_back(impl_->solvers.back().get());
   }
-  impl_->backend.reset(new DeviceBackend(ss));
+  impl_->backend.reset(new DeviceBackend(ss, o.device));
   driver_.reset(new BatchDriver(ls, impl_->backend.get()));
 }
 

@@ -345,7 +345,8 @@ void launchSmallTrials(const MatView& A, const MatView& At, const IterVecs& v, D
                        double* partInter, unsigned long long* bar, int32_t grid, int32_t maxTrials, int mode, hipStream_t s,
                        int32_t timeoutMs = 1000, bool failRollCall = false, bool selfTest = false, unsigned long long seq = 1,
                        bool primalInA = false);
-// Up to eight XCD-local loops of DIFFERENT solvers of one problem in one launch (k_trials_small_lanes; pdlp_batch.hpp):
+// Up to eight XCD-local loops of DIFFERENT solvers in one launch (k_trials_small_lanes; pdlp_batch.hpp: solvers of one
+// problem; pdlp_pool.hpp: of different problems, whose grids and barriers per trial — primalInA — may differ):
 // workgroup b of 8 * max(grid) works for lane b & 7 as its logical workgroup b >> 3, with that lane's own state, barrier
 // words and vectors.  A lane's record holds what launchSmallTrials takes (mode 1); grid = 0: the lane takes no part in this
 // launch.  The eight argument records of a launch lie in HBM: fill writes them into host memory (smallLanesSlotBytes()
@@ -366,7 +367,8 @@ struct SmallLaneLaunch {
 size_t smallLanesSlotBytes();
 bool smallLanesSupported(const MatView& A, const MatView& At, bool primalInA);
 void fillSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, void* hostSlot);
-void launchSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s);
+// -> true: the launch carried lanes of both kinds, two and three barriers per trial (k_trials_small_lanes_mixed)
+bool launchSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s);
 constexpr int kSmallHierWords = 4 * 16 * 32;  // the XCD-hierarchical barrier's words (pdlp_devfn.hpp HierBar)
 // arrival words, timeout flag, XCC ids of the placement check; behind them (256-byte aligned) the hierarchical barrier's words
 // ... and, last, the words of the XCD-local mode's coherence self-test (grid test words, grid arrival words, flag, failure word)

@@ -580,6 +580,7 @@ __global__ __launch_bounds__(kSpmvThreads) void k_trials_small(const SmallArgs a
 struct SmallLanesHdr {
   int32_t nLanes;
   int32_t grid[8];  // workgroups of each lane in THIS launch (0: the lane takes no part)
+  uint32_t pina;    // bit l: lane l runs the loop of two barriers per trial (primalInA); read by the mixed kernel only
 };
 template <int CHUNK_A, int CHUNK_AT, bool PINA>
 __global__ __launch_bounds__(kSpmvThreads) void k_trials_small_lanes(const SmallLanesHdr h, const SmallArgs* __restrict__ lanes) {
@@ -590,6 +591,20 @@ __global__ __launch_bounds__(kSpmvThreads) void k_trials_small_lanes(const Small
   typedef const SmallArgs __attribute__((address_space(4))) * ConstArgs;
   const SmallArgs& a = *(const SmallArgs*)((ConstArgs)lanes + lane);
   trialsSmallBody<CHUNK_A, CHUNK_AT, 1, PINA>(a, lb, G);
+}
+// The same for lanes of DIFFERENT problems (pdlp_pool.hpp) that differ in barriers per trial: a lane runs the body its solo
+// launch runs, chosen by its bit of the header — a kernel argument, so the branch is uniform per workgroup and costs one
+// scalar test.  Only launches that really mix the two kinds come here (launchSmallTrialsLanes).
+template <int CHUNK_A, int CHUNK_AT>
+__global__ __launch_bounds__(kSpmvThreads) void k_trials_small_lanes_mixed(const SmallLanesHdr h, const SmallArgs* __restrict__ lanes) {
+  const int lane = (int)blockIdx.x & 7, lb = (int)blockIdx.x >> 3;
+  if (lane >= h.nLanes) return;
+  const int G = h.grid[lane];
+  if (lb >= G) return;
+  typedef const SmallArgs __attribute__((address_space(4))) * ConstArgs;
+  const SmallArgs& a = *(const SmallArgs*)((ConstArgs)lanes + lane);
+  if ((h.pina >> lane) & 1u) trialsSmallBody<CHUNK_A, CHUNK_AT, 1, true>(a, lb, G);
+  else trialsSmallBody<CHUNK_A, CHUNK_AT, 1, false>(a, lb, G);
 }
 
 using SmallKernel = void (*)(const SmallArgs);
@@ -694,23 +709,29 @@ void fillSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, void* hostSl
                          q.selfTest, q.seq, q.primalInA);
   }
 }
-void launchSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s) {
+bool launchSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s) {
   SmallLanesHdr h{};
   h.nLanes = nLanes;
   int maxG = 0, first = -1;
+  bool mixed = false;
   for (int l = 0; l < nLanes && l < kBatchLanes; ++l) {
     const SmallLaneLaunch& q = lanes[l];
     h.grid[l] = q.grid > 0 ? q.grid : 0;
     if (q.grid <= 0) continue;
     if (first < 0) first = l;
+    if (q.primalInA) h.pina |= 1u << l;
+    mixed = mixed || q.primalInA != lanes[first].primalInA;
     if (q.grid > maxG) maxG = q.grid;
     if (q.selfTest)  // the self-test's words: the tail of the lane's buffer
       (void)hipMemsetAsync(q.bar + smallBarWords(q.grid) - (size_t)(2 * q.grid + 8), 0, (size_t)(2 * q.grid + 8) * sizeof(unsigned long long), s);
   }
-  if (first < 0) return;
-  const SmallLaneLaunch& f = lanes[first];  // (one problem: every lane has the chunks and the variant of the first)
-  hipLaunchKernelGGL(pickLanes(f.A.csr.chunk, f.At.csr.chunk, f.primalInA), dim3(8 * maxG), dim3(kSpmvThreads), 0, s, h,
-                     static_cast<const SmallArgs*>(devSlot));
+  if (first < 0) return false;
+  // (every lane has 512-entry blocks: smallLanesSupported.)  Lanes that agree on the barriers per trial — the lanes of a
+  // batch always do — take the instantiation of their kind; only a launch that mixes the two kinds takes the mixed kernel.
+  const SmallLaneLaunch& f = lanes[first];
+  SmallLanesKernel k = mixed ? k_trials_small_lanes_mixed<kChunkSmall, kChunkSmall> : pickLanes(f.A.csr.chunk, f.At.csr.chunk, f.primalInA);
+  hipLaunchKernelGGL(k, dim3(8 * maxG), dim3(kSpmvThreads), 0, s, h, static_cast<const SmallArgs*>(devSlot));
+  return mixed;
 }
 
 }  // namespace pdlp

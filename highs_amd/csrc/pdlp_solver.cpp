@@ -380,27 +380,30 @@ Solver::DeviceGate& Solver::deviceGate(int device) {
   static DeviceGate gates[64];
   return gates[device >= 0 && device < 64 ? device : 0];
 }
-std::unique_lock<std::mutex> Solver::beginBarrierRound() {
-  std::unique_lock<std::mutex> gate;
-  if (!(persistent_ || fused_)) return gate;
-  DeviceGate& G = deviceGate(opt_.device);
-  gate = std::unique_lock<std::mutex>(G.mu);
-  if (G.recorded) PDLP_HIP(hipStreamWaitEvent(stream_, G.ev[G.cur], 0));
+std::unique_lock<std::mutex> Solver::sharedBeginRound(int device, hipStream_t s) {
+  DeviceGate& G = deviceGate(device);
+  std::unique_lock<std::mutex> gate(G.mu);
+  if (G.recorded) PDLP_HIP(hipStreamWaitEvent(s, G.ev[G.cur], 0));
   return gate;
 }
-void Solver::endBarrierRound(std::unique_lock<std::mutex>& gate) {
+void Solver::sharedEndRound(int device, hipStream_t s, std::unique_lock<std::mutex>& gate) {
   if (!gate.owns_lock()) return;
-  DeviceGate& G = deviceGate(opt_.device);
+  DeviceGate& G = deviceGate(device);
   const int nxt = G.cur ^ 1;
   if (!G.ev[nxt]) {
-    PDLP_HIP(hipSetDevice(opt_.device));  // (the event belongs to the device of the gate, whichever thread gets here first)
+    PDLP_HIP(hipSetDevice(device));  // (the event belongs to the device of the gate, whichever thread gets here first)
     PDLP_HIP(hipEventCreateWithFlags(&G.ev[nxt], hipEventDisableTiming));
   }
-  PDLP_HIP(hipEventRecord(G.ev[nxt], stream_));
+  PDLP_HIP(hipEventRecord(G.ev[nxt], s));
   G.cur = nxt;
   G.recorded = true;
   gate.unlock();
 }
+std::unique_lock<std::mutex> Solver::beginBarrierRound() {
+  if (!(persistent_ || fused_)) return std::unique_lock<std::mutex>();
+  return sharedBeginRound(opt_.device, stream_);
+}
+void Solver::endBarrierRound(std::unique_lock<std::mutex>& gate) { sharedEndRound(opt_.device, stream_, gate); }
 // The end of a round is recorded on EVERY way out of it: if enqueueing throws (a failed launch or graph capture), the
 // barrier kernels that are already queued on this stream must still be ordered in front of the next context's round.
 Solver::BarrierRound::~BarrierRound() {

@@ -158,7 +158,7 @@ class Solver : public SolverBase {
   void sessionCommit();
   size_t sessionHeldBytes() const;  // HBM kept for reuse beyond a plain solver's
 
-  // ---- what a batch drives (pdlp_batch.hpp; all in pdlp_batch_lanes.cpp) ----
+  // ---- what a batch and a pool drive (pdlp_batch.hpp, pdlp_pool.hpp; all in pdlp_batch_lanes.cpp) ----
   // run() cut into the steps of ONE lane of a batch, whose launches are shared with other solvers of the same problem:
   // laneBegin = run() up to its first round; laneQueue = the units [trial batch][check] of the next round as
   // doSolveDevice would enqueue them, handed out as launch records and accounted for as if launched (units[0] may be the
@@ -179,9 +179,10 @@ class Solver : public SolverBase {
   int32_t laneXcc();                      // the XCC id this solver's workers published at their last placement check, or -1
   void laneFinish(pdlp_result_t* R);
   hipStream_t laneStream() const { return stream_; }
-  // the device gate for a round of shared launches on this solver's stream (BarrierRound of doSolveDevice)
-  std::unique_lock<std::mutex> laneBeginRound() { return beginBarrierRound(); }
-  void laneEndRound(std::unique_lock<std::mutex>& gate) { endBarrierRound(gate); }
+  // the device gate for a round of shared launches (BarrierRound of doSolveDevice) on a stream the caller names: a batch's
+  // lane 0's, or one that is no solver's own (a pool's: its solvers come and go, pdlp_pool.hpp)
+  static std::unique_lock<std::mutex> sharedBeginRound(int device, hipStream_t s);
+  static void sharedEndRound(int device, hipStream_t s, std::unique_lock<std::mutex>& gate);
 
  private:
   // setup

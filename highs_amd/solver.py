@@ -50,6 +50,7 @@ EXPORTS = [
     "pdlp_mi355x_session_destroy", "pdlp_mi355x_session_info_size", "pdlp_mi355x_host_classify",
     "pdlp_mi355x_batch_create", "pdlp_mi355x_batch_run", "pdlp_mi355x_batch_info", "pdlp_mi355x_batch_destroy",
     "pdlp_mi355x_batch_info_size",
+    "pdlp_mi355x_solve_many", "pdlp_mi355x_pool_info_size",
 ]
 
 
@@ -134,6 +135,13 @@ def lib():
             if L.pdlp_mi355x_batch_info_size() != C.sizeof(abi.PdlpBatchInfo):
                 raise RuntimeError("pdlp_batch_info_t: the library's size %d differs from abi.PdlpBatchInfo's %d" %
                                    (L.pdlp_mi355x_batch_info_size(), C.sizeof(abi.PdlpBatchInfo)))
+        # (likewise a build from before the pools: tools/pool_bench.py's sequential side)
+        if hasattr(L, "pdlp_mi355x_solve_many"):
+            L.pdlp_mi355x_solve_many.argtypes = [C.c_int32, C.POINTER(pP), pO, C.c_int32, pR, abi.c_i32p, C.POINTER(abi.PdlpPoolInfo)]
+            L.pdlp_mi355x_pool_info_size.restype = C.c_int64
+            if L.pdlp_mi355x_pool_info_size() != C.sizeof(abi.PdlpPoolInfo):
+                raise RuntimeError("pdlp_pool_info_t: the library's size %d differs from abi.PdlpPoolInfo's %d" %
+                                   (L.pdlp_mi355x_pool_info_size(), C.sizeof(abi.PdlpPoolInfo)))
         L.pdlp_mi355x_row_partition.argtypes = [pPrep, C.c_int32, abi.c_i32p]
         pSlab = C.POINTER(abi.PdlpSlabLayout)
         L.pdlp_mi355x_host_slab_layout.argtypes = [pPrep, C.c_int32, C.c_int32, pSlab]
@@ -624,6 +632,44 @@ class DeviceBatch:
             self.close()
         except Exception:
             pass
+
+
+def solve_many(lps, lanes=8, starts=None, **options):
+    """pdlp_mi355x_solve_many: the LPs of `lps` (HighsLp; the same object may appear more than once) solved with one set of
+    options on `lanes` (1..8) lanes — where an LP's trial loop runs XCD-local, up to eight of them at once, one per XCD.
+    starts: None, or one entry per LP (None, or a dict with col_value, row_value, row_dual as solveLpCupdlp takes it).
+    -> (list of PdlpOutcome, one per LP and bit for bit what solveLpCupdlp(lp, start, **options) gives; abi.PdlpPoolInfo).
+    Each outcome's info["pool_path"] is its abi.POOL_*.  Raises RuntimeError with the library's words when the call is
+    refused or a problem fails."""
+    params = options.pop("params", None) or abi.default_params(**options)
+    lps = list(lps)
+    K = len(lps)
+    starts = [None] * K if starts is None else list(starts)
+    if len(starts) != K:
+        raise ValueError("starts: one entry per LP")
+    handles = [abi.ProblemHandle(lp, st) for lp, st in zip(lps, starts)]
+    if any(h.wide for h in handles):
+        raise ValueError("pools take 32-bit column starts")
+    pP = C.POINTER(abi.PdlpProblem)
+    Ps = (pP * max(K, 1))()
+    Rs = (abi.PdlpResult * max(K, 1))()
+    results = []
+    for k, (lp, h) in enumerate(zip(lps, handles)):
+        Ps[k] = C.pointer(h.struct)
+        R = abi.ResultHandle(lp.num_col, lp.num_row)
+        results.append(R)
+        Rs[k] = R.struct
+    path = np.zeros(max(K, 1), dtype=np.int32)
+    I = abi.PdlpPoolInfo()
+    _check(lib().pdlp_mi355x_solve_many(K, Ps, C.byref(params), int(lanes), Rs, path.ctypes.data_as(abi.c_i32p), C.byref(I)),
+           "pdlp_mi355x_solve_many")
+    out = []
+    for k in range(K):
+        results[k].struct = Rs[k]
+        o = _outcome(lps[k], results[k], params, 0)
+        o.info["pool_path"] = int(path[k])
+        out.append(o)
+    return out, I
 
 
 class SyntheticProblem:

@@ -386,6 +386,55 @@ int pdlp_mi355x_batch_info(const pdlp_mi355x_batch_t* B, pdlp_batch_info_t* out)
 void pdlp_mi355x_batch_destroy(pdlp_mi355x_batch_t* B);
 int64_t pdlp_mi355x_batch_info_size(void); /* sizeof(pdlp_batch_info_t); pdlp_mi355x_sizeof keeps its indices */
 
+/* ---- pools: up to eight DIFFERENT small LPs solved at once, one per XCD ----------------------------
+ * For callers with MANY small problems (a Netlib sweep, decomposition subproblems, per-scenario models whose coefficients
+ * differ, a queue of user models).  One call, no handle, nothing held afterwards: P[0..K) are solved with the options opt
+ * (algorithm 0, one device) on `lanes` (1..8) lanes; R[k] is caller-allocated as for the one-call solve.
+ *
+ * THE CONTRACT: R[k] is, bit for bit — every solution vector, every count, every scalar except setup_seconds and
+ * solve_seconds — what a solver created for P[k] with opt gives for one run: create, run, destroy.  For every K, every lane
+ * count, every order of the problems and every order in which they happen to finish.  A hot start in P[k] is honoured;
+ * P[i] == P[j] is allowed.
+ *
+ * Problems are taken in the caller's order: a free lane creates the next problem's solver (at most lanes + 1 solvers
+ * exist at a time; a finished one is destroyed before its lane refills).  Where that solver's trial loop runs XCD-local (at
+ * most 32 work blocks: Netlib-class LPs) it joins the shared launches of the batches, lane L on XCD L, with a grid and a
+ * number of barriers per trial of its own (PDLP_POOL_SHARED).  A solver that does not qualify — a larger LP — is run right
+ * there in the ordinary way (PDLP_POOL_ALONE; pdlp_pool_info_t.reason holds the reason of the first one) while the lanes
+ * wait.  lanes == 1 or K == 1 is a loop of ordinary solves.
+ *   * Refused before any device call, R and path untouched: null arguments, K < 1, lanes outside 1..8, HiPDLP, more than
+ *     one device, forced sharding, and any P[k] that the one-call solve refuses as malformed or that has more than
+ *     INT32_MAX nonzeros ("problem 3: ...", then the existing words).
+ *   * If a create or a solve fails, the call ends there: every solver is destroyed, the return value is non-zero and the
+ *     message names the problem ("problem k: ...").  R[j] of the problems finished by then stay valid: path[j] != 0.
+ *   * opt->time_limit counts per problem from the start of ITS solve (behind its create), and includes the time its lane
+ *     waited while another problem was created or run alone.  A solve that ends by its time limit is outside the contract,
+ *     as everywhere.
+ *   * A lane whose workgroups of a shared launch were not placed on one XCD, not resident together or did not meet at a
+ *     barrier leaves the shared launches for good; its problem is re-solved alone once the others have finished
+ *     (PDLP_POOL_FALLBACK).
+ *   * With log_level >= 1 every log line carries a "[problem k] " prefix.
+ * THREADING: as the one-call solve. */
+enum { PDLP_POOL_NOT_RUN = 0, PDLP_POOL_SHARED = 1, PDLP_POOL_ALONE = 2, PDLP_POOL_FALLBACK = 3 };
+typedef struct pdlp_pool_info {
+  int32_t problems, lanes;
+  int32_t lanes_concurrent;   /* most problems inside shared launches at once; 1 = one after the other */
+  int32_t shared_problems;    /* solved inside shared launches */
+  int32_t alone_problems;     /* did not qualify (reason of the first one in `reason`): ordinary run */
+  int32_t fallback_problems;  /* left the shared launches by the failure rule, re-solved alone */
+  int32_t trial_launches, check_launches;
+  int32_t mixed_launches;     /* trial launches that carried 2-barrier and 3-barrier lanes together */
+  int32_t xcc_of_lane[8];     /* the XCC id the last problem finished on each lane published, or -1 */
+  int32_t reserved[3];
+  double wall_seconds, create_seconds; /* create_seconds: sum over the problems' creates */
+  char reason[160];           /* NUL-terminated: "concurrent: 8 lanes", "sequential: one lane", or why the first problem
+                                 that ran alone did, e.g. "42 work blocks need more than one XCD" */
+} pdlp_pool_info_t;
+int pdlp_mi355x_solve_many(int32_t K, const pdlp_problem_t* const* P, const pdlp_params_t* opt, int32_t lanes,
+                           pdlp_result_t* R, int32_t* path /* [K] PDLP_POOL_*, may be NULL */,
+                           pdlp_pool_info_t* info /* may be NULL */);
+int64_t pdlp_mi355x_pool_info_size(void); /* sizeof(pdlp_pool_info_t); pdlp_mi355x_sizeof keeps its indices */
+
 /* Host-only restatement of the session's decision for the CPU tests: `held` / held_opt are the problem and options of the
  * previous call (held == NULL: nothing is held), P / opt those of this one.  Same ladder (one function shared with the
  * session), same changed mask, same reason words; the four timings and held_bytes are 0. */
