@@ -21,6 +21,8 @@ const int32_t kCheckInterval = Solver::defaultCheckInterval();
 std::string Solver::laneSequentialReason() const {
   const std::string blocks = std::to_string(smallGrid_) + " work blocks";
   if (sharded_) return "sharded solver";
+  if (!persistent_ && hasQoff_ && qpNotPersistent_)
+    return std::string("the trial loop is not one persistent launch (off-diagonal Hessian: ") + qpNotPersistent_ + ")";
   if (!persistent_) return "the trial loop is not one persistent launch (" + std::to_string(std::max(dA_.nBlocks, dAt_.nBlocks)) + " work blocks)";
   if (!xcdLocal_) {
     if (smallGrid_ > 32) return blocks + " need more than one XCD";
@@ -30,7 +32,8 @@ std::string Solver::laneSequentialReason() const {
   if (!checkSmall_) return blocks + ", but the check is not one launch";
   if (!devCheck_) return blocks + ", but the checks are driven by the host";
   if (profile_) return blocks + ", but the solver is in profile mode";
-  if (!smallLanesSupported(dA_.view(), dAt_.view(), primalInA_) || !checkLanesSupported(dA_.view(), dAt_.view()))
+  const MatView* nv = hasQoff_ ? &smallQp()->N : nullptr;
+  if (!smallLanesSupported(dA_.view(), dAt_.view(), primalInA_, nv) || !checkLanesSupported(dA_.view(), dAt_.view(), nv))
     return blocks + ", but not in 512-entry blocks";
   return std::string();
 }
@@ -93,6 +96,7 @@ void Solver::laneQueue(int32_t ahead, std::vector<LaneUnit>& units) {
     t.selfTest = smallLaunches_ == 0;
     t.seq = ++smallSeq_;
     t.primalInA = primalInA_;
+    if (hasQoff_) { t.qoff = true; t.qp = *smallQp(); }
     ++smallLaunches_;
     return t;
   };
@@ -102,7 +106,8 @@ void Solver::laneQueue(int32_t ahead, std::vector<LaneUnit>& units) {
     rec->ran = 0;
     ++checkSeq_;
     c.A = dA_.view(); c.At = dAt_.view(); c.v = vecs_; c.st = dst(); c.cc = dCtl_.get(); c.rec = rec;
-    c.r = RestartVecs{xAvg_.get(), yAvg_.get(), axAvg_.get(), atyAvg_.get(), nullptr, xLast_.get(), yLast_.get()};
+    c.r = RestartVecs{xAvg_.get(), yAvg_.get(), axAvg_.get(), atyAvg_.get(), hasQoff_ ? nxAvg_.get() : nullptr, xLast_.get(), yLast_.get()};
+    if (hasQoff_) { c.qoff = true; c.N = smallQp()->N; }
     c.rowScale = rowScale_.get(); c.colScale = colScale_.get(); c.scaled = F_.scaled ? 1 : 0;
     c.spC = slackPos_.get(); c.snC = slackNeg_.get(); c.spA = slackPosAvg_.get(); c.snA = slackNegAvg_.get();
     c.statPart = statPart_.get(); c.statStride = statStride_; c.statOut = statOut_.get();

@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
+#include <type_traits>
 
 #include "pdlp_checkfn.hpp"
 #include "pdlp_devfn.hpp"
@@ -47,7 +48,7 @@ __device__ __forceinline__ void restartVecBlock(const IterVecs& v, int c, int ki
         xv = ldChk<AGENT>(r.xAvg + j);
         x[j] = xv;
         v.aty[c][j] = ldChk<AGENT>(r.atyAvg + j);
-        if (v.nx[0]) v.nx[c][j] = r.nxAvg[j];
+        if (v.nx[0]) v.nx[c][j] = AGENT ? ldAgent(r.nxAvg + j) : r.nxAvg[j];  // (one launch: phase S of another workgroup wrote it)
       } else {
         xv = x[j];
       }
@@ -131,6 +132,9 @@ __global__ __launch_bounds__(kVecThreads) void k_restart_finish(DevState* st, Ch
 //     D  residuals, termination, restart decision — in every workgroup      run by workgroup vb % G with the same lanes,
 //     V  (restart) sums cleared, average -> current, norms  | barrier     strides and trees: the same bits
 //     W  primal weight, next halt; workgroup 0 writes the state, the control record and the host's record
+// A QP with off-diagonal Hessian entries (CheckSmallArgsQ, the trial loop's QOFF): phase S also computes N xAvg on the
+// blocks of N (launchSpmvPlain's stream path), phase R takes the N x terms of k_col_stats2 — N x of the current iterate is
+// the trial loop's nx of the current parity, as in the launch sequence — and phase V copies N xAvg with the average.
 // Every per-element expression and the scalar logic are the functions of pdlp_checkfn.hpp that the launch sequence uses.
 struct CheckSmallArgs {
   SpmvMat A, At;
@@ -148,6 +152,10 @@ struct CheckSmallArgs {
   unsigned long long seq;    // number of this launch since the words were zeroed (1, 2, ...)
   unsigned long long limit;
   int32_t statStride, scaled;
+};
+
+struct CheckSmallArgsQ : CheckSmallArgs {  // (a record of its own: the LP kernels' argument segment stays what it was)
+  SpmvMat N;
 };
 
 __device__ __forceinline__ int vecBlocksDev(int len) {
@@ -254,8 +262,10 @@ __device__ __forceinline__ void plainLongBlock(const LongMat& L, int tb, const d
 }
 
 // The body of the launch for workgroup lb of G: shared by k_check_small and k_check_small_lanes.
-template <int CHUNK_A, int CHUNK_AT>
-__device__ __forceinline__ void checkSmallBody(const CheckSmallArgs& a, const int lb, const int G) {
+template <int CHUNK_A, int CHUNK_AT, class ARGS = CheckSmallArgs>
+__device__ __forceinline__ void checkSmallBody(const ARGS& a, const int lb, const int G) {
+  constexpr bool QOFF = std::is_same<ARGS, CheckSmallArgsQ>::value;
+  static_assert(!QOFF || (CHUNK_A == kChunkSmall && CHUNK_AT == kChunkSmall), "QOFF: 512-entry blocks");
   constexpr int kMaxChunk = CHUNK_A > CHUNK_AT ? CHUNK_A : CHUNK_AT;
   __shared__ double prod[kMaxChunk + kMaxChunk / 8 + 8];
   __shared__ double scratch[2 * kColStats][kVecThreads / kWave];
@@ -325,6 +335,9 @@ __device__ __forceinline__ void checkSmallBody(const CheckSmallArgs& a, const in
   for (int tb = lb; tb * (kSpmvThreads / kWave) < a.LA.nTasks; tb += G) plainLongBlock(a.LA, tb, a.xAvg, a.axAvg, scratch[0]);
   for (int b = lb; b < a.At.nBlocks; b += G) plainSpmvBlock<CHUNK_AT>(a.At, b, a.yAvg, a.atyAvg, prod);
   for (int tb = lb; tb * (kSpmvThreads / kWave) < a.LAt.nTasks; tb += G) plainLongBlock(a.LAt, tb, a.yAvg, a.atyAvg, scratch[0]);
+  if constexpr (QOFF) {  // N xAvg (N has no long major: smallTrialsGrid)
+    for (int b = lb; b < a.N.nBlocks; b += G) plainSpmvBlock<kChunkSmall>(a.N, b, a.xAvg, const_cast<double*>(a.r.nxAvg), prod);
+  }
   meet();
   // ---- R: statistics of both iterates on the grids of k_row_stats2 / k_col_stats2 ----
   const int nbM = vecBlocksDev(m > 0 ? m : 1), nbN = vecBlocksDev(n > 0 ? n : 1);
@@ -338,8 +351,8 @@ __device__ __forceinline__ void checkSmallBody(const CheckSmallArgs& a, const in
     __syncthreads();
   }
   {
-    const ColStatPtrs p{v.aty[cur], v.x[cur], a.atyAvg, a.xAvg, v.cost, v.lower, v.upper, a.colScale, v.qdiag, nullptr, nullptr,
-                        a.spC, a.snC, a.spA, a.snA};
+    const ColStatPtrs p{v.aty[cur], v.x[cur], a.atyAvg, a.xAvg, v.cost, v.lower, v.upper, a.colScale, v.qdiag,
+                        QOFF ? v.nx[cur] : nullptr, QOFF ? a.r.nxAvg : nullptr, a.spC, a.snC, a.spA, a.snA};
     for (int vb = lb; vb < nbN; vb += G) {
       double acc[2 * kColStats];
 #pragma unroll
@@ -402,6 +415,10 @@ __global__ __launch_bounds__(kVecThreads) void k_check_small(const CheckSmallArg
   checkSmallBody<CHUNK_A, CHUNK_AT>(a, (int)blockIdx.x, (int)gridDim.x);
 }
 
+__global__ __launch_bounds__(kVecThreads) void k_check_small_qp(const CheckSmallArgsQ a) {
+  checkSmallBody<kChunkSmall, kChunkSmall, CheckSmallArgsQ>(a, (int)blockIdx.x, (int)gridDim.x);
+}
+
 // The checks of up to eight solvers of one problem in one launch (pdlp_batch.hpp), with the lane mapping of
 // k_trials_small_lanes: workgroup b works for lane b & 7 as its workgroup b >> 3 of grid[lane].  Accesses, barrier and
 // roll call of a lane are those of its solo launch (agent scope: right wherever the workgroups sit); a lane whose check is
@@ -420,6 +437,16 @@ __global__ __launch_bounds__(kVecThreads) void k_check_small_lanes(const CheckLa
   typedef const CheckSmallArgs __attribute__((address_space(4))) * ConstArgs;
   const CheckSmallArgs& a = *(const CheckSmallArgs*)((ConstArgs)lanes + lane);
   checkSmallBody<CHUNK_A, CHUNK_AT>(a, lb, G);
+}
+
+__global__ __launch_bounds__(kVecThreads) void k_check_small_lanes_qp(const CheckLanesHdr h, const CheckSmallArgsQ* __restrict__ lanes) {
+  const int lane = (int)blockIdx.x & 7, lb = (int)blockIdx.x >> 3;
+  if (lane >= h.nLanes) return;
+  const int G = h.grid[lane];
+  if (lb >= G) return;
+  typedef const CheckSmallArgsQ __attribute__((address_space(4))) * ConstArgs;
+  const CheckSmallArgsQ& a = *(const CheckSmallArgsQ*)((ConstArgs)lanes + lane);
+  checkSmallBody<kChunkSmall, kChunkSmall, CheckSmallArgsQ>(a, lb, G);
 }
 
 using CheckSmallKernel = void (*)(const CheckSmallArgs);
@@ -452,12 +479,17 @@ void launchRestartFinish(DevState* st, CheckCtl* cc, const double* partX, int32_
 }
 
 // Workgroups the device keeps resident of the one-launch check (0: this pair of operands does not qualify)
-int checkSmallResident(const MatView& A, const MatView& At, int device) {
+static bool checkQpChunks(const MatView& A, const MatView& At, const MatView& N) {
+  return A.csr.chunk == kChunkSmall && At.csr.chunk == kChunkSmall && N.csr.chunk == kChunkSmall && !N.useSlab && N.lng.nTasks == 0;
+}
+int checkSmallResident(const MatView& A, const MatView& At, int device, const MatView* N) {
   if (A.useSlab || At.useSlab || A.lng.contrib != nullptr || At.lng.contrib != nullptr) return 0;
   CheckSmallKernel k = pickCheckSmall(A.csr.chunk, At.csr.chunk);
-  if (!k) return 0;
+  if (!k || (N && !checkQpChunks(A, At, *N))) return 0;
   int perCu = 0, cus = 0;
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k, kVecThreads, 0) != hipSuccess) return 0;
+  const hipError_t e = N ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k_check_small_qp, kVecThreads, 0)
+                         : hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k, kVecThreads, 0);
+  if (e != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
   return (perCu < 4 ? perCu : 4) * cus;
 }
@@ -485,15 +517,43 @@ CheckLanesKernel pickCheckLanes(int chunkA, int chunkAt) {  // (the lanes run XC
 void launchCheckSmall(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, CheckCtl* cc, CheckRecord* rec,
                       const RestartVecs& r, const double* rowScale, const double* colScale, int scaled, double* spC, double* snC,
                       double* spA, double* snA, double* statPart, int32_t statStride, double* statOut, double* partX, double* partY,
-                      unsigned long long* bar, int32_t grid, unsigned long long seq, int32_t timeoutMs, hipStream_t s) {
+                      unsigned long long* bar, int32_t grid, unsigned long long seq, int32_t timeoutMs, hipStream_t s, const MatView* N) {
   const CheckSmallArgs a = checkSmallArgsOf(A, At, v, st, cc, rec, r, rowScale, colScale, scaled, spC, snC, spA, snA, statPart, statStride,
                                             statOut, partX, partY, bar, seq, timeoutMs);
+  if (N) {  // (r.nxAvg and v.nx are set)
+    CheckSmallArgsQ q{};
+    static_cast<CheckSmallArgs&>(q) = a;
+    q.N = N->csr;
+    hipLaunchKernelGGL(k_check_small_qp, dim3(grid), dim3(kVecThreads), 0, s, q);
+    return;
+  }
   hipLaunchKernelGGL(pickCheckSmall(A.csr.chunk, At.csr.chunk), dim3(grid), dim3(kVecThreads), 0, s, a);
 }
 
-size_t checkLanesSlotBytes() { return kBatchLanes * sizeof(CheckSmallArgs); }
-bool checkLanesSupported(const MatView& A, const MatView& At) { return pickCheckLanes(A.csr.chunk, At.csr.chunk) != nullptr; }
+size_t checkLanesSlotBytes() { return kBatchLanes * sizeof(CheckSmallArgsQ); }  // (the larger of the two record kinds)
+bool checkLanesSupported(const MatView& A, const MatView& At, const MatView* N) {
+  return pickCheckLanes(A.csr.chunk, At.csr.chunk) != nullptr && (!N || checkQpChunks(A, At, *N));
+}
+namespace {
+int firstCheckLane(const CheckLaneLaunch* lanes, int nLanes) {
+  for (int l = 0; l < nLanes && l < kBatchLanes; ++l)
+    if (lanes[l].grid > 0) return l;
+  return -1;
+}
+}  // namespace
 void fillCheckSmallLanes(const CheckLaneLaunch* lanes, int nLanes, void* hostSlot) {
+  const int first = firstCheckLane(lanes, nLanes);
+  if (first >= 0 && lanes[first].qoff) {  // lanes of one QP (a batch): records of the QP kind
+    CheckSmallArgsQ* out = static_cast<CheckSmallArgsQ*>(hostSlot);
+    for (int l = 0; l < kBatchLanes; ++l) {
+      if (l >= nLanes || lanes[l].grid <= 0) { out[l] = CheckSmallArgsQ{}; continue; }
+      const CheckLaneLaunch& q = lanes[l];
+      static_cast<CheckSmallArgs&>(out[l]) = checkSmallArgsOf(q.A, q.At, q.v, q.st, q.cc, q.rec, q.r, q.rowScale, q.colScale, q.scaled, q.spC, q.snC,
+                                                              q.spA, q.snA, q.statPart, q.statStride, q.statOut, q.partX, q.partY, q.bar, q.seq, q.timeoutMs);
+      out[l].N = q.N.csr;
+    }
+    return;
+  }
   CheckSmallArgs* out = static_cast<CheckSmallArgs*>(hostSlot);
   for (int l = 0; l < kBatchLanes; ++l) {
     if (l >= nLanes || lanes[l].grid <= 0) { out[l] = CheckSmallArgs{}; continue; }
@@ -513,6 +573,10 @@ void launchCheckSmallLanes(const CheckLaneLaunch* lanes, int nLanes, const void*
     if (lanes[l].grid > maxG) maxG = lanes[l].grid;
   }
   if (first < 0) return;
+  if (lanes[first].qoff) {
+    hipLaunchKernelGGL(k_check_small_lanes_qp, dim3(8 * maxG), dim3(kVecThreads), 0, s, h, static_cast<const CheckSmallArgsQ*>(devSlot));
+    return;
+  }
   hipLaunchKernelGGL(pickCheckLanes(lanes[first].A.csr.chunk, lanes[first].At.csr.chunk), dim3(8 * maxG), dim3(kVecThreads), 0, s, h,
                      static_cast<const CheckSmallArgs*>(devSlot));
 }

@@ -336,7 +336,14 @@ void launchSpmvAtyFusedPrimal(const MatView& At, const IterVecs& v, const DevSta
 // 8 * grid workgroups works (one XCD, one coherent L2: no agent-scope traffic); the launch checks that placement and,
 // if it does not hold, changes nothing and sets commError = 2 in *st — the caller then goes on with another mode.
 // mode 2: all XCDs, XCD-hierarchical barrier (pdlp_devfn.hpp hierBarrier) — what hundreds of workgroups need.
-int smallTrialsGrid(const MatView& A, const MatView& At, int32_t n, int device, int* resident, bool primalInA = false);
+// N (QP with off-diagonal Hessian entries): the off-diagonal part of Q as the loop's third operand — it qualifies in the
+// stream layout with 512-entry blocks and no long major, three barriers per trial; the grid covers the blocks of all three.
+int smallTrialsGrid(const MatView& A, const MatView& At, int32_t n, int device, int* resident, bool primalInA = false,
+                    const MatView* N = nullptr);
+struct SmallQp {  // the third operand of such a QP's loop (v.nx holds N x by parity) and its partials of dx . N dx
+  MatView N;
+  double* partQ = nullptr;
+};
 // Every launch begins with a roll call of its working workgroups (pdlp_devfn.hpp rollCall): if they are not all resident
 // within timeoutMs, the launch changes nothing but commError = 3 in *st (failRollCall: a test asks for exactly that).
 // seq: number of this launch since the caller zeroed `bar` (1, 2, ...): the roll call counts cumulatively.
@@ -344,7 +351,7 @@ int smallTrialsGrid(const MatView& A, const MatView& At, int32_t n, int device, 
 void launchSmallTrials(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, double* partDY, double* partDX,
                        double* partInter, unsigned long long* bar, int32_t grid, int32_t maxTrials, int mode, hipStream_t s,
                        int32_t timeoutMs = 1000, bool failRollCall = false, bool selfTest = false, unsigned long long seq = 1,
-                       bool primalInA = false);
+                       bool primalInA = false, const SmallQp* qp = nullptr);
 // Up to eight XCD-local loops of DIFFERENT solvers in one launch (k_trials_small_lanes; pdlp_batch.hpp: solvers of one
 // problem; pdlp_pool.hpp: of different problems, whose grids and barriers per trial — primalInA — may differ):
 // workgroup b of 8 * max(grid) works for lane b & 7 as its logical workgroup b >> 3, with that lane's own state, barrier
@@ -363,9 +370,11 @@ struct SmallLaneLaunch {
   int32_t grid = 0, maxTrials = 0, timeoutMs = 1000;
   bool failRollCall = false, selfTest = false, primalInA = false;
   unsigned long long seq = 1;
+  bool qoff = false;  // a QP with off-diagonal Hessian entries: qp is its third operand (all lanes of a launch alike)
+  SmallQp qp{};
 };
 size_t smallLanesSlotBytes();
-bool smallLanesSupported(const MatView& A, const MatView& At, bool primalInA);
+bool smallLanesSupported(const MatView& A, const MatView& At, bool primalInA, const MatView* N = nullptr);
 void fillSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, void* hostSlot);
 // -> true: the launch carried lanes of both kinds, two and three barriers per trial (k_trials_small_lanes_mixed)
 bool launchSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s);
@@ -428,7 +437,9 @@ void launchDot(const double* a, const double* b, int32_t len, double* partials, 
 // grid barriers inside one launch of `grid` resident workgroups; same statistics grids, same scalar logic, same bits.
 // bar: grid + 8 words zeroed when the solve starts; seq = 1, 2, ... counts the launches since.  A roll call that fails
 // (shared device) leaves everything untouched and sets commError = 3.
-int checkSmallResident(const MatView& A, const MatView& At, int device);
+// N (QP with off-diagonal Hessian entries, pdlp_small.hip): the check also computes N xAvg and takes the N x terms of the
+// column statistics and of the restart (r.nxAvg and v.nx set); 512-entry blocks in all three operands, no long major in N.
+int checkSmallResident(const MatView& A, const MatView& At, int device, const MatView* N = nullptr);
 struct RestartVecs {  // the vectors of a restart (launchRestartVec below)
   const double* xAvg; const double* yAvg; const double* axAvg; const double* atyAvg; const double* nxAvg;
   double* xLast; double* yLast;
@@ -436,7 +447,8 @@ struct RestartVecs {  // the vectors of a restart (launchRestartVec below)
 void launchCheckSmall(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, CheckCtl* cc, CheckRecord* rec,
                       const RestartVecs& r, const double* rowScale, const double* colScale, int scaled, double* spC, double* snC,
                       double* spA, double* snA, double* statPart, int32_t statStride, double* statOut, double* partX, double* partY,
-                      unsigned long long* bar, int32_t grid, unsigned long long seq, int32_t timeoutMs, hipStream_t s);
+                      unsigned long long* bar, int32_t grid, unsigned long long seq, int32_t timeoutMs, hipStream_t s,
+                      const MatView* N = nullptr);
 
 // The same for up to eight solvers of one problem in one launch (k_check_small_lanes; lane mapping, argument slot and the
 // fill / launch pair as for launchSmallTrialsLanes).  A lane's record holds what launchCheckSmall takes.
@@ -457,9 +469,11 @@ struct CheckLaneLaunch {
   unsigned long long* bar = nullptr;
   int32_t grid = 0, timeoutMs = 1000;
   unsigned long long seq = 1;
+  bool qoff = false;  // a QP with off-diagonal Hessian entries: N is its third operand (all lanes of a launch alike)
+  MatView N{};
 };
 size_t checkLanesSlotBytes();
-bool checkLanesSupported(const MatView& A, const MatView& At);
+bool checkLanesSupported(const MatView& A, const MatView& At, const MatView* N = nullptr);
 void fillCheckSmallLanes(const CheckLaneLaunch* lanes, int nLanes, void* hostSlot);
 void launchCheckSmallLanes(const CheckLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s);
 

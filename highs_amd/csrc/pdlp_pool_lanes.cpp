@@ -92,7 +92,11 @@ class SolverPoolLane : public PoolLane {
     }
     s_.reset(new Solver(P, o, 0, 1, nullptr));
   }
-  std::string sequentialReason() override { return s_->laneSequentialReason(); }
+  std::string sequentialReason() override {
+    // (the shared launches of a pool carry the LP bodies only: pdlp_small.hip k_trials_small_lanes / _mixed)
+    if (s_->hasOffDiagonalHessian()) return "off-diagonal Hessian: not in shared pool launches";
+    return s_->laneSequentialReason();
+  }
   void runAlone(pdlp_result_t* R) override { s_->run(R); }
   void begin() override { s_->laneBegin(); }
   bool idle() override { return s_->laneIdle(); }

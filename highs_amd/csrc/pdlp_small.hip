@@ -40,12 +40,18 @@
 // round trip costs an L2 hit instead of an HBM access.  The placement is CHECKED, never assumed: every worker
 // publishes the XCC id it runs on before the first trial; unless all agree the launch changes nothing and reports it,
 // and the solver continues with agent-scope accesses on all XCDs (the mode above) from then on.
+//   QPs: a diagonal Hessian rides in the primal step (qdiag).  One with off-diagonal entries (QOFF) brings the
+// off-diagonal part N as a THIRD operand: phase P takes the explicit gradient term -tau (N x)_j, phase A also runs the
+// workgroup's block of N (N x+ and the partials of dx . N dx, k_spmv's kQxInteract pass on the same x+: no extra barrier),
+// phase D sums those partials with the others.  Three barriers per trial (phase P needs nx of the iterate), 512-entry blocks,
+// no long major in N; kernels and an argument record of their own, so the LP instantiations stay what they were.
 //   The state record lives in LDS of every workgroup (identical copies: every workgroup takes the same decision
 // from the same partials); workgroup 0 writes it back when the batch ends or the device halts.
 #include <hip/hip_runtime.h>
 
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "pdlp_devfn.hpp"
 #include "pdlp_kernels.hpp"
@@ -71,6 +77,16 @@ struct SmallArgs {
   unsigned long long expect; // workgroups the roll call waits for (= the working workgroups of the launch, unless a test asks for a failure)
   unsigned long long limit;  // 100 MHz ticks a roll call or barrier wait may last
   unsigned long long* prof;  // development: 100 MHz ticks per phase {P, barrier, A, barrier, T, barrier, D}, accumulated by workgroup 0
+};
+
+// The record of a QP with off-diagonal Hessian entries (QOFF): the LP's record and, behind it, the third operand — the
+// off-diagonal part N of Q, rows = columns — with its partials of dx . N dx.  A record of its own: the LP kernels' argument
+// segment, and with it their registers, stay what they were.
+struct SmallArgsQ : SmallArgs {
+  SpmvMat N;
+  double* partQ;
+  int32_t nPartQ;  // partial slots of N (k_decide's nQ)
+  int32_t xcdN;
 };
 
 // (inside a launch that has passed its roll call a wait can only fail on a defect: the timeout raises the flag word,
@@ -212,6 +228,47 @@ __device__ __forceinline__ void smallSpmvBlock(const SmallArgs& a, const SpmvMat
   }
 }
 
+// QOFF, phase A: the pass over the owned block of N — k_spmv's stream path with the kQxInteract epilogue (pdlp_kernels.hip
+// Epi::prefetch / apply): N x+ into nx of the next parity, the partial of dx . N dx into acc.  It gathers the x+ the pass over
+// A gathers (phase P stored it in front of the barrier), so the two passes share a phase.
+template <bool LOCAL>
+__device__ __forceinline__ void smallQxBlock(const SmallArgsQ& a, const OwnBlock<kChunkSmall>& B, int cur, double* prod, double& acc) {
+  const int tid = threadIdx.x, nxt = cur ^ 1;
+  const double* in = a.v.x[nxt];
+  constexpr int kPer = kChunkSmall / kSpmvThreads;
+  const int r0 = B.r0, r1 = B.r1, p0 = B.p0, cnt = B.cnt;
+  const int rFirst = r0 + tid;
+  const int rr = rFirst < r1 ? rFirst : r1 - 1;
+  int qb = B.qb, qe = B.qe;
+  auto prefetch = [&](int r) {
+    Pre p{0.0, 0.0, 0.0, 0.0, 0.0};
+    p.a = ldM<LOCAL>(a.v.x[cur] + r); p.b = ldM<LOCAL>(a.v.x[nxt] + r); p.c = ldM<LOCAL>(a.v.nx[cur] + r);
+    return p;
+  };
+  double xg[kPer];
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) xg[k] = ldM<LOCAL>(in + B.ci[k]);
+  Pre pre = prefetch(rr);
+#pragma unroll
+  for (int k = 0; k < kPer; ++k) {
+    const int q = tid + k * kSpmvThreads;
+    if (q < cnt) prod[slot(q)] = B.va[k] * xg[k];
+  }
+  __syncthreads();
+  for (int r = rFirst; r < r1; r += kSpmvThreads) {
+    if (r != rFirst) {
+      qb = a.N.beg[r] - p0;
+      qe = a.N.beg[r + 1] - p0;
+      pre = prefetch(r);
+    }
+    const double s = majorSum(prod, qb, qe);
+    const double dx = pre.a - pre.b;
+    const double dq = pre.c - s;
+    stM<LOCAL>(a.v.nx[nxt] + r, s);
+    acc += dx * dq;
+  }
+}
+
 
 // The segment tasks of the long majors inside the persistent loop (majors longer than a stream block: standata, standgub,
 // standmps, cplex1 of the reference's instances; dense rows / columns of structured LPs).  Task group tb = one task per
@@ -323,8 +380,13 @@ __device__ __forceinline__ void smallLongBlock(const SmallArgs& a, const LongMat
 // still sums the (dy)^2 partials of this one: those alternate between two halves of partDY with the trial's parity.
 // The body of a launch for logical workgroup lb of G: shared by k_trials_small and k_trials_small_lanes (one lane of the
 // latter is, instruction for instruction, a launch of the former), so the two cannot differ.
-template <int CHUNK_A, int CHUNK_AT, int MODE, bool PINA>
-__device__ __forceinline__ void trialsSmallBody(const SmallArgs& a, const int lb, const int G) {
+// ARGS = SmallArgsQ (QOFF): a QP with off-diagonal Hessian entries.  Phase P takes the explicit gradient term -tau (N x)_j
+// where k_primal_step / k_decide_primal take it, phase A also runs the workgroup's block of N (smallQxBlock), phase D sums
+// the partials of dx . N dx with the others (k_decide).  Three barriers per trial only: phase P needs nx of the iterate.
+template <int CHUNK_A, int CHUNK_AT, int MODE, bool PINA, class ARGS = SmallArgs>
+__device__ __forceinline__ void trialsSmallBody(const ARGS& a, const int lb, const int G) {
+  constexpr bool QOFF = std::is_same<ARGS, SmallArgsQ>::value;
+  static_assert(!QOFF || (!PINA && CHUNK_A == kChunkSmall && CHUNK_AT == kChunkSmall), "QOFF: 512-entry blocks, P phase kept");
   constexpr bool LOCAL = MODE == 1;
   constexpr int kMaxChunk = CHUNK_A > CHUNK_AT ? CHUNK_A : CHUNK_AT;
   __shared__ double prod[kMaxChunk + kMaxChunk / 8 + 8];
@@ -363,6 +425,10 @@ __device__ __forceinline__ void trialsSmallBody(const SmallArgs& a, const int lb
     if (PINA) bA.loadPrimal(a.v);
   }
   if (lb < nAt) bAt.load(a.At, a.xcdAt ? xcdContiguousBlock(lb, nAt) : lb, false, nullptr);
+  std::conditional_t<QOFF, OwnBlock<kChunkSmall>, char> bN{};  // (a workgroup beyond N's blocks skips that pass)
+  if constexpr (QOFF) {
+    if (lb < a.N.nBlocks) bN.load(a.N, a.xcdN ? xcdContiguousBlock(lb, a.N.nBlocks) : lb, false, nullptr);
+  }
   if (LOCAL) {
     // the placement check: XCC ids of all workers (words behind the arrival words and the timeout flag)
     unsigned long long* ids = a.bar + G + 8;
@@ -454,10 +520,12 @@ __device__ __forceinline__ void trialsSmallBody(const SmallArgs& a, const int lb
   const int jc = own0 ? j0 : 0;
   const double c0 = a.v.cost[jc], u0 = a.v.upper[jc], l0 = a.v.lower[jc], q0 = a.v.qdiag ? a.v.qdiag[jc] : 0.0;
   double px[2], pa[2], pxs;
+  double pn[2] = {0.0, 0.0};  // QOFF: (N x)_j of both parities
   auto prefetchPrimal = [&]() {
     px[0] = ldM<LOCAL>(a.v.x[0] + jc); px[1] = ldM<LOCAL>(a.v.x[1] + jc);
     pa[0] = ldM<LOCAL>(a.v.aty[0] + jc); pa[1] = ldM<LOCAL>(a.v.aty[1] + jc);
     pxs = ldM<LOCAL>(a.v.xSum + jc);
+    if constexpr (QOFF) { pn[0] = ldM<LOCAL>(a.v.nx[0] + jc); pn[1] = ldM<LOCAL>(a.v.nx[1] + jc); }
   };
   // PINA: (x, A'y) of the columns phase A gathers, both parities — in flight across the decision like the own column's
   constexpr int kPerA = CHUNK_A / kSpmvThreads;
@@ -486,6 +554,7 @@ __device__ __forceinline__ void trialsSmallBody(const SmallArgs& a, const int lb
       double t = xv;
       t += (-tau) * c0;
       t += tau * (cur ? pa[1] : pa[0]);
+      if constexpr (QOFF) t += (-tau) * (cur ? pn[1] : pn[0]);  // explicit gradient term of the off-diagonal part of Q
       if (a.v.qdiag) t = t / (1.0 + tau * q0);
       t = t < u0 ? t : u0;
       t = t > l0 ? t : l0;
@@ -497,6 +566,7 @@ __device__ __forceinline__ void trialsSmallBody(const SmallArgs& a, const int lb
       double t = xv;
       t += (-tau) * a.v.cost[j];
       t += tau * ldM<LOCAL>(a.v.aty[cur] + j);
+      if constexpr (QOFF) t += (-tau) * ldM<LOCAL>(a.v.nx[cur] + j);
       if (a.v.qdiag) t = t / (1.0 + tau * a.v.qdiag[j]);
       const double u = a.v.upper[j], l = a.v.lower[j];
       t = t < u ? t : u;
@@ -524,6 +594,14 @@ __device__ __forceinline__ void trialsSmallBody(const SmallArgs& a, const int lb
       smallLongBlock<true, LOCAL>(a, a.LA, tb, cur, sigma, avgW, scratch[0], partDY, nullptr);
       __syncthreads();
     }
+    if constexpr (QOFF) {  // N x+ and the partial of dx . N dx: the same x+, no barrier of its own
+      if (bN.have) {
+        double accQ = 0.0;
+        smallQxBlock<LOCAL>(a, bN, cur, prod, accQ);
+        const double t = blockSum<kSpmvThreads>(accQ, scratch[0]);
+        if (tid == 0) stM<LOCAL>(a.partQ + bN.slot_, t);
+      }
+    }
     stamp(2);
     meet(e0 + 2);
     stamp(3);
@@ -548,9 +626,12 @@ __device__ __forceinline__ void trialsSmallBody(const SmallArgs& a, const int lb
     // (the timeout flag of the barriers: fetched next to the partials, looked at behind the decision)
     const unsigned long long timedOut = tid == 0 ? __hip_atomic_load(a.bar + G, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
     double dY2, dX2, inter;
-    trialSumsT<LOCAL ? 2 : 1, (CHUNK_A > kChunkSmall || CHUNK_AT > kChunkSmall)>(partDY, a.nPartA, a.partDX, a.partInter, a.nPartAt, tscr, dY2, dX2, inter);
+    double qint = 0.0;
+    if constexpr (QOFF) trialSumsT<LOCAL ? 2 : 1, false>(partDY, a.nPartA, a.partDX, a.partInter, a.nPartAt, tscr, dY2, dX2, inter, a.partQ, a.nPartQ, &qint);
+    else trialSumsT<LOCAL ? 2 : 1, (CHUNK_A > kChunkSmall || CHUNK_AT > kChunkSmall)>(partDY, a.nPartA, a.partDX, a.partInter, a.nPartAt, tscr, dY2, dX2, inter);
     if (tid == 0) {
-      decideUpdate<true>(&sh, dX2, dY2, inter);
+      if constexpr (QOFF) decideUpdate<true>(&sh, dX2, dY2, inter, qint);
+      else decideUpdate<true>(&sh, dX2, dY2, inter);
       if (timedOut) { sh.commError = 1; sh.halted = 1; }
     }
     __syncthreads();
@@ -567,6 +648,15 @@ __global__ __launch_bounds__(kSpmvThreads) void k_trials_small(const SmallArgs a
   const int lb = LOCAL ? (int)blockIdx.x >> 3 : (int)blockIdx.x;      // logical workgroup
   const int G = LOCAL ? (int)gridDim.x >> 3 : (int)gridDim.x;
   trialsSmallBody<CHUNK_A, CHUNK_AT, MODE, PINA>(a, lb, G);
+}
+
+template <int MODE>
+__global__ __launch_bounds__(kSpmvThreads) void k_trials_small_qp(const SmallArgsQ a) {
+  constexpr bool LOCAL = MODE == 1;
+  if (LOCAL && (blockIdx.x & 7) != 0) return;
+  const int lb = LOCAL ? (int)blockIdx.x >> 3 : (int)blockIdx.x;
+  const int G = LOCAL ? (int)gridDim.x >> 3 : (int)gridDim.x;
+  trialsSmallBody<kChunkSmall, kChunkSmall, MODE, false, SmallArgsQ>(a, lb, G);
 }
 
 // Up to eight INDEPENDENT XCD-local loops in one launch (pdlp_batch.hpp): workgroup b works for lane b & 7 as that lane's
@@ -591,6 +681,16 @@ __global__ __launch_bounds__(kSpmvThreads) void k_trials_small_lanes(const Small
   typedef const SmallArgs __attribute__((address_space(4))) * ConstArgs;
   const SmallArgs& a = *(const SmallArgs*)((ConstArgs)lanes + lane);
   trialsSmallBody<CHUNK_A, CHUNK_AT, 1, PINA>(a, lb, G);
+}
+// ... of a QP with off-diagonal Hessian entries (a batch: the lanes share the problem, so all of them are of this kind)
+__global__ __launch_bounds__(kSpmvThreads) void k_trials_small_lanes_qp(const SmallLanesHdr h, const SmallArgsQ* __restrict__ lanes) {
+  const int lane = (int)blockIdx.x & 7, lb = (int)blockIdx.x >> 3;
+  if (lane >= h.nLanes) return;
+  const int G = h.grid[lane];
+  if (lb >= G) return;
+  typedef const SmallArgsQ __attribute__((address_space(4))) * ConstArgs;
+  const SmallArgsQ& a = *(const SmallArgsQ*)((ConstArgs)lanes + lane);
+  trialsSmallBody<kChunkSmall, kChunkSmall, 1, false, SmallArgsQ>(a, lb, G);
 }
 // The same for lanes of DIFFERENT problems (pdlp_pool.hpp) that differ in barriers per trial: a lane runs the body its solo
 // launch runs, chosen by its bit of the header — a kernel argument, so the branch is uniform per workgroup and costs one
@@ -623,6 +723,12 @@ SmallKernel pickT(int chunkA, int chunkAt, int mode) {
   return nullptr;
 }
 SmallKernel pick(int chunkA, int chunkAt, int mode, bool pina = false) { return pina ? pickT<true>(chunkA, chunkAt, mode) : pickT<false>(chunkA, chunkAt, mode); }
+// QOFF: 512-entry blocks in all three operands, every mode, three barriers per trial
+using SmallQpKernel = void (*)(const SmallArgsQ);
+SmallQpKernel pickQp(int chunkA, int chunkAt, int chunkN, int mode) {
+  if (chunkA != kChunkSmall || chunkAt != kChunkSmall || chunkN != kChunkSmall) return nullptr;
+  return mode == 1 ? k_trials_small_qp<1> : mode == 2 ? k_trials_small_qp<2> : k_trials_small_qp<0>;
+}
 // (lanes: XCD-local mode only, which exists for the 512-entry blocks only)
 using SmallLanesKernel = void (*)(const SmallLanesHdr, const SmallArgs*);
 SmallLanesKernel pickLanes(int chunkA, int chunkAt, bool pina) {
@@ -644,13 +750,36 @@ SmallArgs smallArgsOf(const MatView& A, const MatView& At, const IterVecs& v, De
   a.xcdA = A.xcdMap; a.xcdAt = At.xcdMap; a.maxTrials = maxTrials;
   return a;
 }
+SmallArgsQ smallArgsQOf(const SmallArgs& lp, const SmallQp& qp) {
+  SmallArgsQ a{};
+  static_cast<SmallArgs&>(a) = lp;
+  a.N = qp.N.csr; a.partQ = qp.partQ; a.nPartQ = qp.N.nPartials; a.xcdN = qp.N.xcdMap;
+  return a;
+}
 
 }  // namespace
 
 // Workgroups the persistent launch would use (0: this pair of operands does not qualify) and how many the device
 // keeps resident at once.
-int smallTrialsGrid(const MatView& A, const MatView& At, int32_t n, int device, int* residentOut, bool primalInA) {
+int smallTrialsGrid(const MatView& A, const MatView& At, int32_t n, int device, int* residentOut, bool primalInA, const MatView* N) {
   *residentOut = 0;
+  if (N) {
+    // QP with off-diagonal Hessian entries: the LP's rule, and N streams in 512-entry blocks without a long major (their
+    // segment tasks have no counterpart in the loop); the grid is the maximum over the three operands
+    if (primalInA || N->useSlab || N->lng.nTasks > 0 || N->lng.contrib != nullptr || N->csr.nBlocks <= 0) return 0;
+    if (A.useSlab || At.useSlab || A.lng.contrib != nullptr || At.lng.contrib != nullptr || A.csr.nBlocks <= 0 || At.csr.nBlocks <= 0) return 0;
+    SmallQpKernel kq = pickQp(A.csr.chunk, At.csr.chunk, N->csr.chunk, 2);
+    if (!kq) return 0;
+    int perCu = 0, cus = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, kq, kSpmvThreads, 0) != hipSuccess) return 0;
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
+    *residentOut = (perCu < 4 ? perCu : 4) * cus;
+    int g = A.csr.nBlocks > At.csr.nBlocks ? A.csr.nBlocks : At.csr.nBlocks;
+    if (N->csr.nBlocks > g) g = N->csr.nBlocks;
+    const int gv = (n + kSpmvThreads - 1) / kSpmvThreads;
+    if (gv > g) g = gv < 64 ? gv : (g > 64 ? g : 64);
+    return g;
+  }
   // (long majors ride along as segment tasks; beyond kLongSlotCap of them their contributions need the k_long_groups launch)
   if (A.useSlab || At.useSlab || A.lng.contrib != nullptr || At.lng.contrib != nullptr) return 0;
   // (the long rows' segment tasks gather x+ from memory: with them the P phase stays — standmps 11.2 -> 11.8 us per trial without it)
@@ -670,7 +799,7 @@ int smallTrialsGrid(const MatView& A, const MatView& At, int32_t n, int device, 
 
 void launchSmallTrials(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, double* partDY, double* partDX,
                        double* partInter, unsigned long long* bar, int32_t grid, int32_t maxTrials, int mode, hipStream_t s,
-                       int32_t timeoutMs, bool failRollCall, bool selfTest, unsigned long long seq, bool primalInA) {
+                       int32_t timeoutMs, bool failRollCall, bool selfTest, unsigned long long seq, bool primalInA, const SmallQp* qp) {
   const bool xcdLocal = mode == 1;
   static_assert(kHierBarWords == kSmallHierWords, "barrier buffer layout");
   // mode 2: the hierarchical barrier's counters (and the roll-call word) start from zero in every launch; the other modes
@@ -695,12 +824,38 @@ void launchSmallTrials(const MatView& A, const MatView& At, const IterVecs& v, D
     return p;
   }();
   a.prof = prof;
+  if (qp) {
+    const SmallArgsQ q = smallArgsQOf(a, *qp);
+    hipLaunchKernelGGL(pickQp(A.csr.chunk, At.csr.chunk, qp->N.csr.chunk, mode), dim3(xcdLocal ? 8 * grid : grid), dim3(kSpmvThreads), 0, s, q);
+    return;
+  }
   hipLaunchKernelGGL(pick(A.csr.chunk, At.csr.chunk, mode, primalInA), dim3(xcdLocal ? 8 * grid : grid), dim3(kSpmvThreads), 0, s, a);
 }
 
-size_t smallLanesSlotBytes() { return kBatchLanes * sizeof(SmallArgs); }
-bool smallLanesSupported(const MatView& A, const MatView& At, bool primalInA) { return pickLanes(A.csr.chunk, At.csr.chunk, primalInA) != nullptr; }
+size_t smallLanesSlotBytes() { return kBatchLanes * sizeof(SmallArgsQ); }  // (the larger of the two record kinds)
+bool smallLanesSupported(const MatView& A, const MatView& At, bool primalInA, const MatView* N) {
+  if (N) return !primalInA && pickQp(A.csr.chunk, At.csr.chunk, N->csr.chunk, 1) != nullptr;
+  return pickLanes(A.csr.chunk, At.csr.chunk, primalInA) != nullptr;
+}
+namespace {
+int firstLane(const SmallLaneLaunch* lanes, int nLanes) {
+  for (int l = 0; l < nLanes && l < kBatchLanes; ++l)
+    if (lanes[l].grid > 0) return l;
+  return -1;
+}
+}  // namespace
 void fillSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, void* hostSlot) {
+  const int first = firstLane(lanes, nLanes);
+  if (first >= 0 && lanes[first].qoff) {  // lanes of one QP (a batch): records of the QP kind
+    SmallArgsQ* out = static_cast<SmallArgsQ*>(hostSlot);
+    for (int l = 0; l < kBatchLanes; ++l) {
+      if (l >= nLanes || lanes[l].grid <= 0) { out[l] = SmallArgsQ{}; continue; }
+      const SmallLaneLaunch& q = lanes[l];
+      out[l] = smallArgsQOf(smallArgsOf(q.A, q.At, q.v, q.st, q.partDY, q.partDX, q.partInter, q.bar, q.grid, q.maxTrials, 1, q.timeoutMs,
+                                        q.failRollCall, q.selfTest, q.seq, false), q.qp);
+    }
+    return;
+  }
   SmallArgs* out = static_cast<SmallArgs*>(hostSlot);
   for (int l = 0; l < kBatchLanes; ++l) {
     if (l >= nLanes || lanes[l].grid <= 0) { out[l] = SmallArgs{}; continue; }
@@ -726,6 +881,10 @@ bool launchSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, const void
       (void)hipMemsetAsync(q.bar + smallBarWords(q.grid) - (size_t)(2 * q.grid + 8), 0, (size_t)(2 * q.grid + 8) * sizeof(unsigned long long), s);
   }
   if (first < 0) return false;
+  if (lanes[first].qoff) {  // (never mixed with lanes of another kind: the pool runs such solvers alone)
+    hipLaunchKernelGGL(k_trials_small_lanes_qp, dim3(8 * maxG), dim3(kSpmvThreads), 0, s, h, static_cast<const SmallArgsQ*>(devSlot));
+    return false;
+  }
   // (every lane has 512-entry blocks: smallLanesSupported.)  Lanes that agree on the barriers per trial — the lanes of a
   // batch always do — take the instantiation of their kind; only a launch that mixes the two kinds takes the mixed kernel.
   const SmallLaneLaunch& f = lanes[first];

@@ -340,6 +340,7 @@ DevSwitches DevSwitches::fromEnv() {
   w.gpuSetup = num("PDLP_MI355X_GPU_SETUP", -1);
   w.fused = num("PDLP_MI355X_FUSED", -1);
   w.persistent = num("PDLP_MI355X_PERSISTENT", -1);
+  w.persistentQp = num("PDLP_MI355X_PERSISTENT_QP", -1);
   w.barrierTimeoutMs = num("PDLP_MI355X_BARRIER_TIMEOUT_MS", 1000);
   {
     const char* e = getenv("PDLP_MI355X_EXCHANGE");
@@ -659,7 +660,20 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
     // persistent launch with grid barriers between the phases (pdlp_small.hip); PDLP_MI355X_PERSISTENT=0 turns it off
     int resident = 0;
     int g = 0;
-    if (sw_.persistent != 0 && !hasQoff_) {
+    if (sw_.persistent != 0 && hasQoff_) {
+      // a small QP with off-diagonal Hessian entries: N rides along as the loop's third operand where it streams in
+      // 512-entry blocks without a long major; three barriers per trial (PDLP_MI355X_PERSISTENT_QP=0: launches as before)
+      const MatView nv = dQ_.view();
+      if (sw_.persistentQp == 0) qpNotPersistent_ = "PDLP_MI355X_PERSISTENT_QP=0";
+      else if (nv.useSlab) qpNotPersistent_ = "N is in the slab layout";
+      else if (nv.csr.chunk != kChunkSmall) qpNotPersistent_ = "N streams in 2048-entry blocks";
+      else if (nv.lng.nTasks > 0) qpNotPersistent_ = "N has a long major";
+      else {
+        g = smallTrialsGrid(dA_.view(), at, F_.n, opt_.device, &resident, false, &nv);
+        if (g == 0) qpNotPersistent_ = "A or A' does not qualify";
+        else if (g > resident) qpNotPersistent_ = "its workgroups are not resident at once";
+      }
+    } else if (sw_.persistent != 0) {
       // two barriers per trial instead of three: phase A recomputes x+ of the columns it gathers (PDLP_MI355X_PRIMAL_IN_A=0/1)
       // — where that variant's registers still leave the whole grid resident
       primalInA_ = sw_.primalInA != 0;
@@ -692,7 +706,8 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
     }
     if (persistent_) gridBar_.alloc(smallBarWords(smallGrid_));
     // Netlib-class LPs (at most 64 workgroups): the check iteration as one launch too (PDLP_MI355X_CHECK_SMALL=0: ten launches)
-    checkSmall_ = persistent_ && smallGrid_ <= 64 && sw_.checkSmall != 0 && checkSmallResident(dA_.view(), at, opt_.device) >= smallGrid_;
+    checkSmall_ = persistent_ && smallGrid_ <= 64 && sw_.checkSmall != 0 &&
+                  checkSmallResident(dA_.view(), at, opt_.device, hasQoff_ ? &smallQp()->N : nullptr) >= smallGrid_;
     if (checkSmall_) checkBar_.alloc((size_t)smallGrid_ + 8);
   }
   // check iterations on the device: single GPU, and (round 5) the row-block sharded solve over the mesh exchange — its check
@@ -1442,7 +1457,8 @@ void Solver::enqueueTrial() {
   }
   if (persistent_) {
     launchSmallTrials(dA_.view(), dAt_.view(), vecs_, dst(), partDY_.get(), partDX_.get(), partInter_.get(), gridBar_.get(), smallGrid_, 1,
-                      smallMode(), stream_, sw_.barrierTimeoutMs, sw_.fault == 1 && smallLaunches_ == 0, smallLaunches_ == 0, ++smallSeq_, primalInA_);
+                      smallMode(), stream_, sw_.barrierTimeoutMs, sw_.fault == 1 && smallLaunches_ == 0, smallLaunches_ == 0, ++smallSeq_, primalInA_,
+                      smallQp());
     ++smallLaunches_;
     return;
   }
@@ -1547,7 +1563,7 @@ void Solver::enqueueBatch(int32_t todo) {
   if (persistent_ && !profile_) {  // the whole stretch to the next check (plus spare trials for rejections) in one launch
     launchSmallTrials(dA_.view(), dAt_.view(), vecs_, dst(), partDY_.get(), partDX_.get(), partInter_.get(), gridBar_.get(),
                       smallGrid_, todo + 8, smallMode(), stream_, sw_.barrierTimeoutMs, sw_.fault == 1 && smallLaunches_ == 0,
-                      smallLaunches_ == 0, ++smallSeq_, primalInA_);
+                      smallLaunches_ == 0, ++smallSeq_, primalInA_, smallQp());
     ++smallLaunches_;
     return;
   }
@@ -1838,10 +1854,11 @@ void Solver::enqueueCheckDevice() {
     CheckRecord* rec = hostRing_ + (checkSeq_ % kRingSlots);
     rec->ran = 0;
     ++checkSeq_;
-    const RestartVecs rv{xAvg_.get(), yAvg_.get(), axAvg_.get(), atyAvg_.get(), nullptr, xLast_.get(), yLast_.get()};
+    const RestartVecs rv{xAvg_.get(), yAvg_.get(), axAvg_.get(), atyAvg_.get(), hasQoff_ ? nxAvg_.get() : nullptr, xLast_.get(), yLast_.get()};
     launchCheckSmall(dA_.view(), dAt_.view(), vecs_, st, dCtl_.get(), rec, rv, rowScale_.get(), colScale_.get(), F_.scaled ? 1 : 0,
                      slackPos_.get(), slackNeg_.get(), slackPosAvg_.get(), slackNegAvg_.get(), statPart_.get(), statStride_, statOut_.get(),
-                     partDX_.get(), partRestartY_.get(), checkBar_.get(), smallGrid_, ++checkSmallSeq_, sw_.barrierTimeoutMs, stream_);
+                     partDX_.get(), partRestartY_.get(), checkBar_.get(), smallGrid_, ++checkSmallSeq_, sw_.barrierTimeoutMs, stream_,
+                     hasQoff_ ? &smallQp()->N : nullptr);
     needPrimal_ = true;
     return;
   }

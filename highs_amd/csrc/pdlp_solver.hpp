@@ -30,6 +30,7 @@ struct DevSwitches {
   int touchTail = 1;      // PDLP_MI355X_TOUCH_TAIL=0 (development): no touching of the tail columns' operands in front of the fused trial's barrier
   int constCached = -1;   // PDLP_MI355X_CONST_CACHED=0|1 (development): c, l, u of the primal step non-temporal / ordinary loads (default: by size)
   int fused = -1, persistent = -1, xcdLocal = -1, hierBarrier = -1, deviceCheck = -1, checkSmall = -1;
+  int persistentQp = -1;  // PDLP_MI355X_PERSISTENT_QP=0: small QPs with off-diagonal Hessian entries keep their launches per trial (LPs, diagonal QPs: not read)
   int primalInA = -1;     // PDLP_MI355X_PRIMAL_IN_A: the persistent loop without its P phase (pdlp_small.hip PINA); -1 = where measured faster
   int barrierTimeoutMs = 1000;  // PDLP_MI355X_BARRIER_TIMEOUT_MS: how long a grid barrier / roll call waits for missing workgroups
   int fault = 0;          // PDLP_MI355X_FAULT (tests): 1 = the first persistent launch expects one workgroup too many,
@@ -166,6 +167,7 @@ class Solver : public SolverBase {
   // run() does behind its loop.  Between laneBegin and laneFinish nothing else may be asked of the solver.
   // laneSequentialReason: empty, or why this solver's launches cannot be shared (it then runs alone)
   std::string laneSequentialReason() const;
+  bool hasOffDiagonalHessian() const { return hasQoff_; }
   int32_t laneWorkBlocks() const { return smallGrid_; }
   static int32_t defaultCheckInterval();  // CUPDLP_RELEASE_INTERVAL
   // the refusals of update(u) that do not depend on the device, with update's words; nothing is changed
@@ -298,6 +300,15 @@ class Solver : public SolverBase {
   bool fused_ = false, needPrimal_ = true;
   // Small LPs: a batch of trials is ONE persistent launch (pdlp_small.hip); smallGrid_ = its workgroups
   bool persistent_ = false, xcdLocal_ = false, hierBar_ = false, primalInA_ = false;
+  // QP with off-diagonal Hessian entries inside the persistent loop: N as its third operand (pdlp_small.hip QOFF)
+  mutable SmallQp smallQp_{};
+  const SmallQp* smallQp() const {  // (nullptr: an LP or a diagonal QP)
+    if (!hasQoff_) return nullptr;
+    smallQp_.N = dQ_.view();
+    smallQp_.partQ = partQ_.get();
+    return &smallQp_;
+  }
+  const char* qpNotPersistent_ = nullptr;  // why such a QP keeps its launches per trial (laneSequentialReason)
   int smallMode() const { return xcdLocal_ ? 1 : hierBar_ ? 2 : 0; }
   int32_t smallGrid_ = 0;
   DeviceArray<unsigned long long> gridBar_;
