@@ -264,6 +264,16 @@ class PdlpTaskPlan(C.Structure):
     ]
 
 
+class PdlpStreamPlan(C.Structure):
+    """pdlp_stream_plan_t (csrc/pdlp_api.cpp, a test hook outside the public header): the work plan of a stream-layout
+    operand, for the CPU tests."""
+    _fields_ = [
+        ("chunk", C.c_int32), ("n_blocks", C.c_int32), ("n_long", C.c_int32), ("n_tasks", C.c_int32),
+        ("task_group", C.c_int32), ("long_group", C.c_int32), ("long_slots", C.c_int32), ("small_grid", C.c_int32),
+        ("block_beg", c_i32p), ("long_majors", c_i32p), ("tasks", c_i32p),
+    ]
+
+
 class PdlpMpsModel(C.Structure):
     """pdlp_mps_model_t (include/pdlp_mi355x.h): what pdlp_mi355x_read_mps fills."""
     _fields_ = [

@@ -590,6 +590,61 @@ void pdlp_mi355x_free_task_plan(pdlp_task_plan_t* o) {
   memset(o, 0, sizeof(*o));
 }
 
+// TEST HOOK, not part of the public header (no product code calls it): the work plan of operand `which` (0: A by rows,
+// 1: A' by columns), for the CPU tests of the structural thresholds.  slab_long_limit = 0, the stream layout: planStream and
+// planLong, the same calls as in DeviceMatrix::uploadPlans — work blocks of whole short majors (block_beg: first major, end
+// major, first entry, end entry), the majors beyond the chunk and their segment tasks in workgroups of task_group (records
+// as in pdlp_task_plan_t).  slab_long_limit > 0 (as in pdlp_mi355x_host_slab_layout): this branch only COUNTS the slab
+// layout's long majors, from a layout of the default slab width — it does not plan their tasks as uploadPlans does
+// (planSlabTasks: pdlp_mi355x_host_task_plan shows those).  long_group: long majors per contribution slot (longGroupFor, as
+// uploadPlans).  small_grid: workgroups the persistent trial loop asks for where both operands qualify (smallGridFor over the
+// blocks of A and A'; extra_blocks: those of a third operand, 0 for none).
+struct pdlp_stream_plan_t {
+  int32_t chunk, n_blocks, n_long, n_tasks, task_group, long_group, long_slots, small_grid;
+  int32_t *block_beg, *long_majors, *tasks;  // [4*n_blocks], [n_long], [8*n_tasks]
+};
+int pdlp_mi355x_host_stream_plan(const pdlp_prepared_t* prep, int32_t which, int32_t slab_long_limit, int32_t extra_blocks,
+                                 pdlp_stream_plan_t* out) {
+  return guarded([&] {
+    if (!prep || !out) throw std::runtime_error("null argument");
+    memset(out, 0, sizeof(*out));
+    const int32_t nMajor = which ? prep->n : prep->m, nMinor = which ? prep->m : prep->n;
+    const int32_t* beg = which ? prep->csc_beg : prep->csr_beg;
+    const std::vector<int32_t> hostBeg(beg, beg + nMajor + 1);
+    const int32_t blocks = std::max(std::max(prep->spmv_blocks_ax, prep->spmv_blocks_aty), extra_blocks);
+    out->small_grid = pdlp::smallGridFor(blocks, prep->n);
+    if (slab_long_limit > 0) {
+      pdlp::Compressed c;
+      c.beg = hostBeg;
+      c.idx.assign(which ? prep->csc_idx : prep->csr_idx, (which ? prep->csc_idx : prep->csr_idx) + prep->nnz);
+      c.val.assign(which ? prep->csc_val : prep->csr_val, (which ? prep->csc_val : prep->csr_val) + prep->nnz);
+      pdlp::SlabLayout L;
+      pdlp::buildSlabLayout(c, nMajor, nMinor, slab_long_limit, pdlp::kSlabWidthLog2, which ? pdlp::kSlabMajorCostCols : pdlp::kSlabMajorCostRows, L);
+      out->chunk = slab_long_limit;
+      out->n_long = (int32_t)L.longMap.size();
+      out->long_majors = dupVec(L.longMap);
+    } else {
+      out->chunk = pdlp::spmvChunkFor(hostBeg[nMajor]);
+      const pdlp::StreamPlan plan = pdlp::planStream(hostBeg, nMajor, out->chunk, pdlp::kMaxMajorsPerBlock);
+      out->task_group = pdlp::kSpmvThreads / 64;
+      const pdlp::LongPlan L = pdlp::planLong(hostBeg, plan.longMajors, nullptr, out->task_group);
+      out->n_blocks = plan.nBlocks;
+      out->n_long = L.nLong;
+      out->n_tasks = L.nTasks;
+      std::vector<int32_t> flat((size_t)8 * L.nTasks);
+      if (L.nTasks > 0) memcpy(flat.data(), L.tasks.data(), flat.size() * sizeof(int32_t));
+      out->block_beg = dupVec(plan.blockBeg); out->long_majors = dupVec(plan.longMajors); out->tasks = dupVec(flat);
+    }
+    out->long_group = pdlp::longGroupFor(out->n_long);
+    out->long_slots = (out->n_long + out->long_group - 1) / out->long_group;
+  });
+}
+void pdlp_mi355x_free_stream_plan(pdlp_stream_plan_t* o) {
+  if (!o) return;
+  free(o->block_beg); free(o->long_majors); free(o->tasks);
+  memset(o, 0, sizeof(*o));
+}
+
 void pdlp_mi355x_det_exp_log(int32_t n, const double* x, double* exp_out, double* log_out) {
   for (int32_t i = 0; i < n; ++i) { exp_out[i] = pdlp_det_exp(x[i]); log_out[i] = pdlp_det_log(x[i]); }
 }

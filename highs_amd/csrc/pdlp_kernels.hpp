@@ -122,6 +122,7 @@ struct SpmvMat {
 constexpr int kLongSegment = 512;   // nonzeros per segment task (8 per lane)
 constexpr int kLongMaxSegments = 64;
 constexpr int kLongSlotCap = 2048;  // more long majors than this: contributions are summed in fixed groups (k_long_groups)
+inline int32_t longGroupFor(int32_t nLong) { return nLong > kLongSlotCap ? (nLong + kLongSlotCap - 1) / kLongSlotCap : 1; }  // long majors per slot
 struct LongTask {      // 32 bytes: one scalar load per wave
   int32_t pBeg, pEnd;  // entries of the segment
   int32_t c;           // long-major index (-1: idle task, padding)
@@ -340,6 +341,14 @@ void launchSpmvAtyFusedPrimal(const MatView& At, const IterVecs& v, const DevSta
 // stream layout with 512-entry blocks and no long major, three barriers per trial; the grid covers the blocks of all three.
 int smallTrialsGrid(const MatView& A, const MatView& At, int32_t n, int device, int* resident, bool primalInA = false,
                     const MatView* N = nullptr);
+// its grid for operands of at most `blocks` work blocks and n columns: the column step asks for ceil(n / 256) workgroups, and
+// alone never for more than 64 (beyond them a workgroup strides over the columns)
+inline int smallGridFor(int blocks, int32_t n) {
+  int g = blocks;
+  const int gv = (n + kSpmvThreads - 1) / kSpmvThreads;
+  if (gv > g) g = gv < 64 ? gv : (g > 64 ? g : 64);
+  return g;
+}
 struct SmallQp {  // the third operand of such a QP's loop (v.nx holds N x by parity) and its partials of dx . N dx
   MatView N;
   double* partQ = nullptr;

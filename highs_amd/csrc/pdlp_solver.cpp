@@ -78,7 +78,7 @@ void DeviceMatrix::uploadPlans(const std::vector<int32_t>& hostBeg, int32_t nCsr
   }
   nLong = L.nLong;
   nTasks = L.nTasks;
-  longGroup = nLong > kLongSlotCap ? (nLong + kLongSlotCap - 1) / kLongSlotCap : 1;
+  longGroup = longGroupFor(nLong);
   longSlots = (nLong + longGroup - 1) / longGroup;
   lTasks.alloc((size_t)nTasks);
   lTasks.upload(reinterpret_cast<const LongTask*>(L.tasks.data()), (size_t)nTasks, s);
@@ -2390,6 +2390,11 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     // launch (fusedWait 2) 9 gated kernels + three all-gathers + the two reductions with their all-reduces = 14;
     // 0: the host drives the checks; +1 for a sharded QP with off-diagonal Hessian entries: N xAvg)
     put(0, !devCheck_ ? 0.0 : sharded_ ? (mesh_ && mesh_->args().fusedWait == 2 ? 14.0 : 26.0) + (hasQoff_ ? 1.0 : 0.0) : persistent_ && checkSmall_ ? 1.0 : 10.0);
+  } else if (name == "small_loop") {  // the persistent trial loop as set up: [0] its workgroups (0: no persistent loop), [1] its mode —
+    // 0 agent-scope accesses with the sweep barrier, 1 XCD-local, 2 XCD-hierarchical barrier — [2] 1 = the check is one launch
+    put(0, persistent_ ? (double)smallGrid_ : 0.0);
+    put(1, persistent_ ? (double)smallMode() : -1.0);
+    put(2, persistent_ && checkSmall_ ? 1.0 : 0.0);
   } else if (name == "barrier_fallbacks") {  // times a launch with grid barriers gave up and the loop went on with plain launches
     put(0, (double)barrierFallbacks_);
   } else if (name == "persistent_launches") {  // persistent trial launches enqueued since create (no-ops behind a termination included)

@@ -151,6 +151,11 @@ def lib():
         L.pdlp_mi355x_host_task_plan.argtypes = [pPrep, C.c_int32, C.c_int32, C.c_int32, pTask]
         L.pdlp_mi355x_free_task_plan.argtypes = [pTask]
         L.pdlp_mi355x_free_task_plan.restype = None
+        # (a test hook outside the public header: the stream layout's work plan)
+        pPlan = C.POINTER(abi.PdlpStreamPlan)
+        L.pdlp_mi355x_host_stream_plan.argtypes = [pPrep, C.c_int32, C.c_int32, C.c_int32, pPlan]
+        L.pdlp_mi355x_free_stream_plan.argtypes = [pPlan]
+        L.pdlp_mi355x_free_stream_plan.restype = None
         pMps = C.POINTER(abi.PdlpMpsModel)
         L.pdlp_mi355x_read_mps.argtypes = [C.c_char_p, C.c_int32, pMps]
         L.pdlp_mi355x_read_mps_timed.argtypes = [C.c_char_p, C.c_int32, C.c_double, pMps]
@@ -731,6 +736,34 @@ def host_prepare_qp(lp, a_value=None, q_value=None, update=None, update_then=Non
     lib().pdlp_mi355x_free_prepared(C.byref(F))
     lib().pdlp_mi355x_free_prepared_hessian(C.byref(Q))
     return form, hess
+
+
+def stream_plan(form, which, slab_long_limit=0, extra_blocks=0):
+    """pdlp_mi355x_host_stream_plan: the work plan of operand `which` (0: A by rows, 1: A' by columns) of a prepared form
+    as the device set-up builds it.  form: a Prepared, or a dict with n, m, nnz, csr_beg / csr_idx / csr_val, csc_beg / csc_idx /
+    csc_val, spmv_blocks_ax, spmv_blocks_aty (the first dict of host_prepare_qp).  slab_long_limit = 0: the stream layout —
+    blocks [n_blocks, 4] (first major, end major, first entry, end entry), long_majors, tasks [n_tasks, 8] (pdlp_task_plan_t's
+    records; column 2 is -1 for an idle task); > 0: the slab layout's long majors only.  long_group: long majors per
+    contribution slot; small_grid: workgroups of the persistent trial loop where the operands qualify (extra_blocks: work blocks
+    of a third operand)."""
+    get = (lambda k: form[k]) if isinstance(form, dict) else (lambda k: getattr(form, k))
+    F = abi.PdlpPrepared()
+    F.n, F.m, F.nnz = int(get("n")), int(get("m")), int(get("nnz"))
+    F.spmv_blocks_ax, F.spmv_blocks_aty = int(get("spmv_blocks_ax")), int(get("spmv_blocks_aty"))
+    keep = {}
+    for k, dt, ty in (("csr_beg", np.int32, abi.c_i32p), ("csr_idx", np.int32, abi.c_i32p), ("csr_val", np.float64, abi.c_f64p),
+                      ("csc_beg", np.int32, abi.c_i32p), ("csc_idx", np.int32, abi.c_i32p), ("csc_val", np.float64, abi.c_f64p)):
+        keep[k] = np.ascontiguousarray(get(k), dtype=dt)
+        setattr(F, k, keep[k].ctypes.data_as(ty))
+    SP = abi.PdlpStreamPlan()
+    _check(lib().pdlp_mi355x_host_stream_plan(C.byref(F), which, slab_long_limit, extra_blocks, C.byref(SP)), "stream_plan")
+    g = lambda p, k: np.ctypeslib.as_array(p, shape=(max(k, 1),))[:k].astype(np.int64).copy() if p else np.zeros(0, np.int64)
+    out = dict(chunk=SP.chunk, n_blocks=SP.n_blocks, n_long=SP.n_long, n_tasks=SP.n_tasks, task_group=SP.task_group,
+               long_group=SP.long_group, long_slots=SP.long_slots, small_grid=SP.small_grid,
+               blocks=g(SP.block_beg, 4 * SP.n_blocks).reshape(-1, 4), long_majors=g(SP.long_majors, SP.n_long),
+               tasks=g(SP.tasks, 8 * SP.n_tasks).reshape(-1, 8))
+    lib().pdlp_mi355x_free_stream_plan(C.byref(SP))
+    return out
 
 
 class Prepared:
