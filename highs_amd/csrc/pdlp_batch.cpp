@@ -109,10 +109,9 @@ void BatchDriver::runConcurrent(int32_t K, const pdlp_update_t* u, pdlp_result_t
       }
       variantOf[l] = -1;
     }
-    // queue depth, as one solver chooses it: ~25 ms of work per round, at most 16 units, doubling from 1
+    // queue depth, as one solver chooses it (pdlp_round.hpp), by the deepest lane's units
     const double roundMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - roundBeg).count();
-    if (deepest > 0 && roundMs > 0.0) aheadMax = std::max(1, std::min(16, (int32_t)(25.0 * (double)deepest / roundMs)));
-    ahead = std::min(ahead * 2, aheadMax);
+    ahead = nextQueueDepth(ahead, aheadMax, (int32_t)deepest, roundMs, false);
   }
   info_.lanes_concurrent = std::max(most, 1);
   for (int32_t l = 0; l < nLanes; ++l)

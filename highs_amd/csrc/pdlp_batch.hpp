@@ -17,16 +17,18 @@
 
 #include "pdlp_kernels.hpp"
 #include "pdlp_host.hpp"
+#include "pdlp_round.hpp"
 
 namespace pdlp {
 
 class Solver;
 
-// One unit of a lane's queue: [trial batch to the next scheduled check][check], as launch records.
+// One unit of a lane's queue: [trial batch to the next scheduled check][check] of the round's plan (pdlp_round.hpp), as
+// launch records.
 struct LaneUnit {
   bool hasTrials = false;  // false: the entry's check alone
-  SmallLaneLaunch trials;
-  CheckLaneLaunch check;
+  SmallTrialsLaunch trials;
+  CheckSmallLaunch check;
 };
 
 enum LaneVerdict : int { kLaneGoOn = 0, kLaneOver = 1, kLaneFailed = 2 };

@@ -1,7 +1,6 @@
 // pdlp_batch_lanes.cpp — the device side of a batch (pdlp_batch.hpp): Solver's lane steps, i.e. Solver::run cut into the
 // pieces the driver calls per lane; the lane and the backend the driver works with on a device; the batch itself.
 #include <algorithm>
-#include <climits>
 #include <cstdio>
 #include <cstring>
 
@@ -12,10 +11,6 @@
 #include "pdlp_update.hpp"
 
 namespace pdlp {
-
-namespace {
-const int32_t kCheckInterval = Solver::defaultCheckInterval();
-}
 
 // ---- Solver: one run as a lane ------------------------------------------------------------------------------------------
 std::string Solver::laneSequentialReason() const {
@@ -51,92 +46,29 @@ void Solver::validateUpdate(const pdlp_update_t& u) const {
   }
 }
 
-// run() up to the first round of doSolveDevice
+// run() up to the first round of its device-driven loop
 void Solver::laneBegin() {
   reset();
   solveBeg_ = std::chrono::steady_clock::now();
   if (hasStart_) log(1, "Hot starting with given column primal values and row dual values\n");
-  lane_ = LaneRun();
-  DevState& s = *hostState_;
-  lane_.iterLim = (int64_t)opt_.iter_limit;
-  if (s.nIter >= lane_.iterLim) {
-    lane_.noLoop = true;
-    return;
-  }
-  uploadCtl(true, lane_.iterLim);
-  checkSeen_ = checkSeq_;
-  // entry: a check is due right here (iteration 0 is on every schedule)
-  const int32_t interval = opt_.check_interval > 0 ? opt_.check_interval : kCheckInterval;
-  if (s.nIter < 10 || s.nIter % interval == 0 || s.nIter == opt_.iter_limit - 1) {
-    s.haltIter = s.nIter;
-    s.halted = 1;
-  } else {
-    s.haltIter = nextCheckIter(s.nIter);
-    s.halted = 0;
-  }
-  pushState(false);
-  PDLP_HIP(hipStreamSynchronize(stream_));  // (the round's launches come on the batch's stream)
+  if (!beginDeviceLoop(true, (int64_t)opt_.iter_limit)) return;
+  PDLP_HIP(hipStreamSynchronize(stream_));  // (only a lane: the round's launches come on another stream, the batch's)
 }
 
-// The units of doSolveDevice's next round, as launch records: enqueueBatch's persistent launch and enqueueCheckDevice's
-// one-launch check, with their bookkeeping (launch counters, the ring's record) done as if launched here.
+// The units of the next round as launch records (a solver alone launches the same records itself: doSolveDevice)
 void Solver::laneQueue(int32_t ahead, std::vector<LaneUnit>& units) {
-  DevState& s = *hostState_;
-  const int64_t iterLim = lane_.iterLim;
-  lane_.iterBefore = s.nIter;
-  lane_.trialsBefore = s.nTrials;
-  lane_.seq0 = checkSeq_;
-  auto haltAfter = [&](int64_t it) { return (int64_t)nextCheckIter((int32_t)it); };
-  auto trials = [&](int32_t todo) {
-    SmallLaneLaunch t;
-    t.A = dA_.view(); t.At = dAt_.view(); t.v = vecs_; t.st = dst();
-    t.partDY = partDY_.get(); t.partDX = partDX_.get(); t.partInter = partInter_.get(); t.bar = gridBar_.get();
-    t.grid = smallGrid_; t.maxTrials = todo + 8; t.timeoutMs = sw_.barrierTimeoutMs;
-    t.failRollCall = sw_.fault == 1 && smallLaunches_ == 0;
-    t.selfTest = smallLaunches_ == 0;
-    t.seq = ++smallSeq_;
-    t.primalInA = primalInA_;
-    if (hasQoff_) { t.qoff = true; t.qp = *smallQp(); }
-    ++smallLaunches_;
-    return t;
-  };
-  auto check = [&]() {
-    CheckLaneLaunch c;
-    CheckRecord* rec = hostRing_ + (checkSeq_ % kRingSlots);
-    rec->ran = 0;
-    ++checkSeq_;
-    c.A = dA_.view(); c.At = dAt_.view(); c.v = vecs_; c.st = dst(); c.cc = dCtl_.get(); c.rec = rec;
-    c.r = RestartVecs{xAvg_.get(), yAvg_.get(), axAvg_.get(), atyAvg_.get(), hasQoff_ ? nxAvg_.get() : nullptr, xLast_.get(), yLast_.get()};
-    if (hasQoff_) { c.qoff = true; c.N = smallQp()->N; }
-    c.rowScale = rowScale_.get(); c.colScale = colScale_.get(); c.scaled = F_.scaled ? 1 : 0;
-    c.spC = slackPos_.get(); c.snC = slackNeg_.get(); c.spA = slackPosAvg_.get(); c.snA = slackNegAvg_.get();
-    c.statPart = statPart_.get(); c.statStride = statStride_; c.statOut = statOut_.get();
-    c.partX = partDX_.get(); c.partY = partRestartY_.get(); c.bar = checkBar_.get();
-    c.grid = smallGrid_; c.timeoutMs = sw_.barrierTimeoutMs; c.seq = ++checkSmallSeq_;
-    needPrimal_ = true;
-    return c;
-  };
-  int64_t itExp = s.nIter, haltExp = s.haltIter;
-  if (s.halted) {  // (entry only: every batch below is followed by its check)
+  const RoundPlan plan = beginRound(ahead);
+  if (plan.entryCheck) {
     LaneUnit e;
-    e.check = check();
+    e.check = checkSmallLaunch();
     units.push_back(e);
-    haltExp = haltAfter(itExp);
   }
-  int64_t queuedTrials = 0;  // (the tabulated powers of the step rule reach 4096 trials beyond the last refresh)
-  for (int32_t u = 0; u < ahead && queuedTrials < 3000; ++u) {
-    int64_t todo = haltExp - itExp;
-    if (todo < 1) todo = 1;
-    if (todo > 4 * kCheckInterval) todo = 4 * kCheckInterval;
+  for (int32_t u = 0; u < plan.nTodo; ++u) {
     LaneUnit unit;
     unit.hasTrials = true;
-    unit.trials = trials((int32_t)todo);
-    unit.check = check();
+    unit.trials = smallTrialsLaunch(plan.todo[u] + kRoundSpareTrials);
+    unit.check = checkSmallLaunch();
     units.push_back(unit);
-    queuedTrials += todo + 8;
-    itExp = std::min(itExp + todo, haltExp);
-    if (itExp >= iterLim - 1) break;  // the check that ends the solve
-    if (itExp == haltExp) haltExp = haltAfter(itExp);
   }
 }
 
@@ -144,33 +76,19 @@ void Solver::laneDownload(hipStream_t shared) {
   PDLP_HIP(hipMemcpyAsync(hostState_, dst(), sizeof(DevState), hipMemcpyDeviceToHost, shared));
 }
 
-// syncState (the stream is idle, the state record is here) + processRecords + the tail of doSolveDevice's loop
+// syncState (the stream is idle, the state record is here) + the round's verdict
 LaneVerdict Solver::laneAfterRound() {
   DevState& s = *hostState_;
-  if (s.commError) {  // 2: placement, 3: roll call (the launch changed nothing for this lane); 1: barrier timeout (the lane is stopped)
-    lane_.commError = s.commError;
+  // Only a lane, and before anything else: a commError is its driver's to handle (a solver alone takes its fall-backs
+  // inside syncState).  2: placement, 3: roll call (the launch changed nothing for this lane); 1: barrier timeout (the lane is stopped)
+  if (s.commError) {
+    loop_.commError = s.commError;
     log(1, "Note: this lane's workgroups of a shared launch %s; its variant is solved alone\n",
         s.commError == 2 ? "were not placed on one XCD" : s.commError == 3 ? "were not resident together in time" : "did not meet at a barrier in time");
     return kLaneFailed;
   }
-  processRecords(true, lane_.iterLim, lane_.logSinceHeader);
-  bool over = false;
-  for (int64_t q = lane_.seq0; q < checkSeq_; ++q) over = over || (hostRing_[q % kRingSlots].ran && hostRing_[q % kRingSlots].terminated);
-  if (over) return kLaneOver;
-  if (s.nIter == lane_.iterBefore && s.nTrials - lane_.trialsBefore > 0) {
-    if (++stalledRounds_ >= 50)
-      throw std::runtime_error("pdlp_mi355x: the adaptive step-size search does not terminate (no trial step accepted in " +
-                               std::to_string(s.nTrials - stalledSince_) + " trials: NaN or Inf in the problem data?)");
-  } else {
-    stalledRounds_ = 0;
-    stalledSince_ = s.nTrials;
-  }
-  if (timeIsUp()) {
-    lane_.timeUp = true;
-    return kLaneOver;
-  }
-  if (s.powRed && s.nTrials + 4096 >= s.powBase + s.powCount) pushState(true);
-  return kLaneGoOn;
+  // (only a lane: the next launches come on another stream, so refreshed powers are waited for)
+  return afterRound(true) ? kLaneGoOn : kLaneOver;
 }
 
 int32_t Solver::laneXcc() {
@@ -182,7 +100,7 @@ int32_t Solver::laneXcc() {
 }
 
 void Solver::laneFinish(pdlp_result_t* R) {
-  if (!lane_.noLoop) endDeviceLoop(true, lane_.timeUp, lane_.logSinceHeader);
+  if (!loop_.noLoop) endDeviceLoop();
   finishRun(R);
 }
 

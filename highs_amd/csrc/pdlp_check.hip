@@ -494,19 +494,22 @@ int checkSmallResident(const MatView& A, const MatView& At, int device, const Ma
   return (perCu < 4 ? perCu : 4) * cus;
 }
 namespace {
-CheckSmallArgs checkSmallArgsOf(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, CheckCtl* cc, CheckRecord* rec,
-                                const RestartVecs& r, const double* rowScale, const double* colScale, int scaled, double* spC, double* snC,
-                                double* spA, double* snA, double* statPart, int32_t statStride, double* statOut, double* partX,
-                                double* partY, unsigned long long* bar, unsigned long long seq, int32_t timeoutMs) {
+CheckSmallArgs checkSmallArgsOf(const CheckSmallLaunch& q) {
   CheckSmallArgs a{};
-  a.A = A.csr; a.At = At.csr; a.LA = A.lng; a.LAt = At.lng; a.v = v; a.st = st; a.cc = cc; a.rec = rec; a.r = r;
-  a.xAvg = const_cast<double*>(r.xAvg); a.yAvg = const_cast<double*>(r.yAvg);
-  a.axAvg = const_cast<double*>(r.axAvg); a.atyAvg = const_cast<double*>(r.atyAvg);
-  a.rowScale = rowScale; a.colScale = colScale; a.scaled = scaled;
-  a.spC = spC; a.snC = snC; a.spA = spA; a.snA = snA;
-  a.statPart = statPart; a.statStride = statStride; a.statOut = statOut; a.partX = partX; a.partY = partY;
-  a.bar = bar; a.seq = seq;
-  a.limit = (unsigned long long)(timeoutMs > 0 ? timeoutMs : 1000) * 100000ull;
+  a.A = q.A.csr; a.At = q.At.csr; a.LA = q.A.lng; a.LAt = q.At.lng; a.v = q.v; a.st = q.st; a.cc = q.cc; a.rec = q.rec; a.r = q.r;
+  a.xAvg = const_cast<double*>(q.r.xAvg); a.yAvg = const_cast<double*>(q.r.yAvg);
+  a.axAvg = const_cast<double*>(q.r.axAvg); a.atyAvg = const_cast<double*>(q.r.atyAvg);
+  a.rowScale = q.rowScale; a.colScale = q.colScale; a.scaled = q.scaled;
+  a.spC = q.spC; a.snC = q.snC; a.spA = q.spA; a.snA = q.snA;
+  a.statPart = q.statPart; a.statStride = q.statStride; a.statOut = q.statOut; a.partX = q.partX; a.partY = q.partY;
+  a.bar = q.bar; a.seq = q.seq;
+  a.limit = (unsigned long long)(q.timeoutMs > 0 ? q.timeoutMs : 1000) * 100000ull;
+  return a;
+}
+CheckSmallArgsQ checkSmallArgsQOf(const CheckSmallLaunch& q) {  // (q.r.nxAvg and q.v.nx are set)
+  CheckSmallArgsQ a{};
+  static_cast<CheckSmallArgs&>(a) = checkSmallArgsOf(q);
+  a.N = q.N.csr;
   return a;
 }
 using CheckLanesKernel = void (*)(const CheckLanesHdr, const CheckSmallArgs*);
@@ -514,20 +517,9 @@ CheckLanesKernel pickCheckLanes(int chunkA, int chunkAt) {  // (the lanes run XC
   return chunkA == kChunkSmall && chunkAt == kChunkSmall ? k_check_small_lanes<kChunkSmall, kChunkSmall> : nullptr;
 }
 }  // namespace
-void launchCheckSmall(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, CheckCtl* cc, CheckRecord* rec,
-                      const RestartVecs& r, const double* rowScale, const double* colScale, int scaled, double* spC, double* snC,
-                      double* spA, double* snA, double* statPart, int32_t statStride, double* statOut, double* partX, double* partY,
-                      unsigned long long* bar, int32_t grid, unsigned long long seq, int32_t timeoutMs, hipStream_t s, const MatView* N) {
-  const CheckSmallArgs a = checkSmallArgsOf(A, At, v, st, cc, rec, r, rowScale, colScale, scaled, spC, snC, spA, snA, statPart, statStride,
-                                            statOut, partX, partY, bar, seq, timeoutMs);
-  if (N) {  // (r.nxAvg and v.nx are set)
-    CheckSmallArgsQ q{};
-    static_cast<CheckSmallArgs&>(q) = a;
-    q.N = N->csr;
-    hipLaunchKernelGGL(k_check_small_qp, dim3(grid), dim3(kVecThreads), 0, s, q);
-    return;
-  }
-  hipLaunchKernelGGL(pickCheckSmall(A.csr.chunk, At.csr.chunk), dim3(grid), dim3(kVecThreads), 0, s, a);
+void launchCheckSmall(const CheckSmallLaunch& q, hipStream_t s) {
+  if (q.qoff) hipLaunchKernelGGL(k_check_small_qp, dim3(q.grid), dim3(kVecThreads), 0, s, checkSmallArgsQOf(q));
+  else hipLaunchKernelGGL(pickCheckSmall(q.A.csr.chunk, q.At.csr.chunk), dim3(q.grid), dim3(kVecThreads), 0, s, checkSmallArgsOf(q));
 }
 
 size_t checkLanesSlotBytes() { return kBatchLanes * sizeof(CheckSmallArgsQ); }  // (the larger of the two record kinds)
@@ -535,34 +527,22 @@ bool checkLanesSupported(const MatView& A, const MatView& At, const MatView* N) 
   return pickCheckLanes(A.csr.chunk, At.csr.chunk) != nullptr && (!N || checkQpChunks(A, At, *N));
 }
 namespace {
-int firstCheckLane(const CheckLaneLaunch* lanes, int nLanes) {
-  for (int l = 0; l < nLanes && l < kBatchLanes; ++l)
-    if (lanes[l].grid > 0) return l;
-  return -1;
+void setLaneArgs(CheckSmallArgs& out, const CheckSmallLaunch& q) { out = checkSmallArgsOf(q); }
+void setLaneArgs(CheckSmallArgsQ& out, const CheckSmallLaunch& q) { out = checkSmallArgsQOf(q); }
+template <class Args>
+void fillLanes(const CheckSmallLaunch* lanes, int nLanes, Args* out) {
+  for (int l = 0; l < kBatchLanes; ++l) {
+    if (l < nLanes && lanes[l].grid > 0) setLaneArgs(out[l], lanes[l]);
+    else out[l] = Args{};
+  }
 }
 }  // namespace
-void fillCheckSmallLanes(const CheckLaneLaunch* lanes, int nLanes, void* hostSlot) {
-  const int first = firstCheckLane(lanes, nLanes);
-  if (first >= 0 && lanes[first].qoff) {  // lanes of one QP (a batch): records of the QP kind
-    CheckSmallArgsQ* out = static_cast<CheckSmallArgsQ*>(hostSlot);
-    for (int l = 0; l < kBatchLanes; ++l) {
-      if (l >= nLanes || lanes[l].grid <= 0) { out[l] = CheckSmallArgsQ{}; continue; }
-      const CheckLaneLaunch& q = lanes[l];
-      static_cast<CheckSmallArgs&>(out[l]) = checkSmallArgsOf(q.A, q.At, q.v, q.st, q.cc, q.rec, q.r, q.rowScale, q.colScale, q.scaled, q.spC, q.snC,
-                                                              q.spA, q.snA, q.statPart, q.statStride, q.statOut, q.partX, q.partY, q.bar, q.seq, q.timeoutMs);
-      out[l].N = q.N.csr;
-    }
-    return;
-  }
-  CheckSmallArgs* out = static_cast<CheckSmallArgs*>(hostSlot);
-  for (int l = 0; l < kBatchLanes; ++l) {
-    if (l >= nLanes || lanes[l].grid <= 0) { out[l] = CheckSmallArgs{}; continue; }
-    const CheckLaneLaunch& q = lanes[l];
-    out[l] = checkSmallArgsOf(q.A, q.At, q.v, q.st, q.cc, q.rec, q.r, q.rowScale, q.colScale, q.scaled, q.spC, q.snC, q.spA, q.snA, q.statPart,
-                              q.statStride, q.statOut, q.partX, q.partY, q.bar, q.seq, q.timeoutMs);
-  }
+void fillCheckSmallLanes(const CheckSmallLaunch* lanes, int nLanes, void* hostSlot) {
+  const int first = firstTakingLane(lanes, nLanes);
+  if (first >= 0 && lanes[first].qoff) fillLanes(lanes, nLanes, static_cast<CheckSmallArgsQ*>(hostSlot));  // lanes of one QP (a batch)
+  else fillLanes(lanes, nLanes, static_cast<CheckSmallArgs*>(hostSlot));
 }
-void launchCheckSmallLanes(const CheckLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s) {
+void launchCheckSmallLanes(const CheckSmallLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s) {
   CheckLanesHdr h{};
   h.nLanes = nLanes;
   int maxG = 0, first = -1;

@@ -357,18 +357,9 @@ struct SmallQp {  // the third operand of such a QP's loop (v.nx holds N x by pa
 // within timeoutMs, the launch changes nothing but commError = 3 in *st (failRollCall: a test asks for exactly that).
 // seq: number of this launch since the caller zeroed `bar` (1, 2, ...): the roll call counts cumulatively.
 // primalInA: two barriers per trial — phase A's gathers recompute x+ themselves (partDY then needs 2 * A.nPartials slots).
-void launchSmallTrials(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, double* partDY, double* partDX,
-                       double* partInter, unsigned long long* bar, int32_t grid, int32_t maxTrials, int mode, hipStream_t s,
-                       int32_t timeoutMs = 1000, bool failRollCall = false, bool selfTest = false, unsigned long long seq = 1,
-                       bool primalInA = false, const SmallQp* qp = nullptr);
-// Up to eight XCD-local loops of DIFFERENT solvers in one launch (k_trials_small_lanes; pdlp_batch.hpp: solvers of one
-// problem; pdlp_pool.hpp: of different problems, whose grids and barriers per trial — primalInA — may differ):
-// workgroup b of 8 * max(grid) works for lane b & 7 as its logical workgroup b >> 3, with that lane's own state, barrier
-// words and vectors.  A lane's record holds what launchSmallTrials takes (mode 1); grid = 0: the lane takes no part in this
-// launch.  The eight argument records of a launch lie in HBM: fill writes them into host memory (smallLanesSlotBytes()
-// bytes), the caller copies them to devSlot in stream order in front of the launch.
-constexpr int kBatchLanes = 8;
-struct SmallLaneLaunch {
+// The launch is described by its record: one solver's launch (launchSmallTrials) and its share of a launch of several
+// solvers (launchSmallTrialsLanes) take the same one.
+struct SmallTrialsLaunch {
   MatView A, At;
   IterVecs v;
   DevState* st = nullptr;
@@ -382,11 +373,25 @@ struct SmallLaneLaunch {
   bool qoff = false;  // a QP with off-diagonal Hessian entries: qp is its third operand (all lanes of a launch alike)
   SmallQp qp{};
 };
+void launchSmallTrials(const SmallTrialsLaunch& q, int mode, hipStream_t s);
+// Up to eight XCD-local loops of DIFFERENT solvers in one launch (k_trials_small_lanes; pdlp_batch.hpp: solvers of one
+// problem; pdlp_pool.hpp: of different problems, whose grids and barriers per trial — primalInA — may differ):
+// workgroup b of 8 * max(grid) works for lane b & 7 as its logical workgroup b >> 3, with that lane's own state, barrier
+// words and vectors.  A lane's record is what launchSmallTrials takes, run in mode 1; grid = 0: the lane takes no part in this
+// launch.  The eight argument records of a launch lie in HBM: fill writes them into host memory (smallLanesSlotBytes()
+// bytes), the caller copies them to devSlot in stream order in front of the launch.
+constexpr int kBatchLanes = 8;
+template <class Launch>
+int firstTakingLane(const Launch* lanes, int nLanes) {  // -1: no lane takes part in the launch
+  for (int l = 0; l < nLanes && l < kBatchLanes; ++l)
+    if (lanes[l].grid > 0) return l;
+  return -1;
+}
 size_t smallLanesSlotBytes();
 bool smallLanesSupported(const MatView& A, const MatView& At, bool primalInA, const MatView* N = nullptr);
-void fillSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, void* hostSlot);
+void fillSmallTrialsLanes(const SmallTrialsLaunch* lanes, int nLanes, void* hostSlot);
 // -> true: the launch carried lanes of both kinds, two and three barriers per trial (k_trials_small_lanes_mixed)
-bool launchSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s);
+bool launchSmallTrialsLanes(const SmallTrialsLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s);
 constexpr int kSmallHierWords = 4 * 16 * 32;  // the XCD-hierarchical barrier's words (pdlp_devfn.hpp HierBar)
 // arrival words, timeout flag, XCC ids of the placement check; behind them (256-byte aligned) the hierarchical barrier's words
 // ... and, last, the words of the XCD-local mode's coherence self-test (grid test words, grid arrival words, flag, failure word)
@@ -453,15 +458,7 @@ struct RestartVecs {  // the vectors of a restart (launchRestartVec below)
   const double* xAvg; const double* yAvg; const double* axAvg; const double* atyAvg; const double* nxAvg;
   double* xLast; double* yLast;
 };
-void launchCheckSmall(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, CheckCtl* cc, CheckRecord* rec,
-                      const RestartVecs& r, const double* rowScale, const double* colScale, int scaled, double* spC, double* snC,
-                      double* spA, double* snA, double* statPart, int32_t statStride, double* statOut, double* partX, double* partY,
-                      unsigned long long* bar, int32_t grid, unsigned long long seq, int32_t timeoutMs, hipStream_t s,
-                      const MatView* N = nullptr);
-
-// The same for up to eight solvers of one problem in one launch (k_check_small_lanes; lane mapping, argument slot and the
-// fill / launch pair as for launchSmallTrialsLanes).  A lane's record holds what launchCheckSmall takes.
-struct CheckLaneLaunch {
+struct CheckSmallLaunch {  // the record of one such check
   MatView A, At;
   IterVecs v;
   DevState* st = nullptr;
@@ -481,10 +478,13 @@ struct CheckLaneLaunch {
   bool qoff = false;  // a QP with off-diagonal Hessian entries: N is its third operand (all lanes of a launch alike)
   MatView N{};
 };
+void launchCheckSmall(const CheckSmallLaunch& q, hipStream_t s);
+// The same for up to eight solvers in one launch (k_check_small_lanes; lane mapping, argument slot and the fill / launch
+// pair as for launchSmallTrialsLanes), every lane with the record launchCheckSmall takes.
 size_t checkLanesSlotBytes();
 bool checkLanesSupported(const MatView& A, const MatView& At, const MatView* N = nullptr);
-void fillCheckSmallLanes(const CheckLaneLaunch* lanes, int nLanes, void* hostSlot);
-void launchCheckSmallLanes(const CheckLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s);
+void fillCheckSmallLanes(const CheckSmallLaunch* lanes, int nLanes, void* hostSlot);
+void launchCheckSmallLanes(const CheckSmallLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s);
 
 // ---- the scalar side of a device-driven check (pdlp_check.hip) ------------------------------------------------------
 // stat: the 2*kRowStats + 2*kColStats statistics (launchFinalReduce2).  Residuals of both iterates, termination

@@ -165,10 +165,8 @@ void PoolDriver::runConcurrent(int32_t K, pdlp_result_t* R, int32_t* path) {
       }
       taking[l] = nullptr;
     }
-    // queue depth, as one solver chooses it: ~25 ms of work per round, at most 16 units, doubling from 1
-    const double roundMs = since(roundBeg) * 1e3;
-    if (deepest > 0 && roundMs > 0.0) aheadMax = std::max(1, std::min(16, (int32_t)(25.0 * (double)deepest / roundMs)));
-    ahead = std::min(ahead * 2, aheadMax);
+    // queue depth, as one solver chooses it (pdlp_round.hpp), by the deepest lane's units
+    ahead = nextQueueDepth(ahead, aheadMax, (int32_t)deepest, since(roundBeg) * 1e3, false);
   }
   info_.lanes_concurrent = std::max(most, 1);
   for (int32_t l = 0; l < nLanes; ++l) {

@@ -37,8 +37,8 @@ void LaneRounds::round(const std::vector<LaneUnit>* units, Solver* const* solver
   for (int l = 0; l < nLanes; ++l) J = std::max(J, units[l].size());
   if (J == 0) return;
   if (J > (size_t)kMaxUnits) throw std::runtime_error(who_ + ": more units in a round than argument slots");
-  std::vector<SmallLaneLaunch> tl(J * kBatchLanes);
-  std::vector<CheckLaneLaunch> cl(J * kBatchLanes);
+  std::vector<SmallTrialsLaunch> tl(J * kBatchLanes);
+  std::vector<CheckSmallLaunch> cl(J * kBatchLanes);
   std::vector<char> anyTrials(J, 0);
   char* hostT = static_cast<char*>(host_);
   char* hostC = hostT + J * slotT_;

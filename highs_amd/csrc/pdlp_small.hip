@@ -737,17 +737,15 @@ SmallLanesKernel pickLanes(int chunkA, int chunkAt, bool pina) {
 }
 
 // the argument record of one launch (everything but the development profile)
-SmallArgs smallArgsOf(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, double* partDY, double* partDX,
-                      double* partInter, unsigned long long* bar, int32_t grid, int32_t maxTrials, int mode, int32_t timeoutMs,
-                      bool failRollCall, bool selfTest, unsigned long long seq, bool primalInA) {
+SmallArgs smallArgsOf(const SmallTrialsLaunch& q, int mode) {
   SmallArgs a{};
-  a.expect = (mode == 2 ? (unsigned long long)grid : seq * (unsigned long long)grid) + (failRollCall ? 1ull : 0ull);
-  a.selfTest = mode == 1 && selfTest ? 1 : 0;
-  a.primalInA = primalInA ? 1 : 0;
-  a.limit = (unsigned long long)(timeoutMs > 0 ? timeoutMs : 1000) * 100000ull;
-  a.LA = A.lng; a.LAt = At.lng; a.nPartA = A.nPartials; a.nPartAt = At.nPartials;
-  a.A = A.csr; a.At = At.csr; a.v = v; a.st = st; a.partDY = partDY; a.partDX = partDX; a.partInter = partInter; a.bar = bar;
-  a.xcdA = A.xcdMap; a.xcdAt = At.xcdMap; a.maxTrials = maxTrials;
+  a.expect = (mode == 2 ? (unsigned long long)q.grid : q.seq * (unsigned long long)q.grid) + (q.failRollCall ? 1ull : 0ull);
+  a.selfTest = mode == 1 && q.selfTest ? 1 : 0;
+  a.primalInA = q.primalInA && !q.qoff ? 1 : 0;  // (a QP's loop keeps its P phase: smallTrialsGrid)
+  a.limit = (unsigned long long)(q.timeoutMs > 0 ? q.timeoutMs : 1000) * 100000ull;
+  a.LA = q.A.lng; a.LAt = q.At.lng; a.nPartA = q.A.nPartials; a.nPartAt = q.At.nPartials;
+  a.A = q.A.csr; a.At = q.At.csr; a.v = q.v; a.st = q.st; a.partDY = q.partDY; a.partDX = q.partDX; a.partInter = q.partInter; a.bar = q.bar;
+  a.xcdA = q.A.xcdMap; a.xcdAt = q.At.xcdMap; a.maxTrials = q.maxTrials;
   return a;
 }
 SmallArgsQ smallArgsQOf(const SmallArgs& lp, const SmallQp& qp) {
@@ -763,48 +761,44 @@ SmallArgsQ smallArgsQOf(const SmallArgs& lp, const SmallQp& qp) {
 // keeps resident at once.
 int smallTrialsGrid(const MatView& A, const MatView& At, int32_t n, int device, int* residentOut, bool primalInA, const MatView* N) {
   *residentOut = 0;
+  const void* k = nullptr;  // the kernel the occupancy query is asked about
+  int g = A.csr.nBlocks > At.csr.nBlocks ? A.csr.nBlocks : At.csr.nBlocks;
   if (N) {
     // QP with off-diagonal Hessian entries: the LP's rule, and N streams in 512-entry blocks without a long major (their
     // segment tasks have no counterpart in the loop); the grid is the maximum over the three operands
     if (primalInA || N->useSlab || N->lng.nTasks > 0 || N->lng.contrib != nullptr || N->csr.nBlocks <= 0) return 0;
     if (A.useSlab || At.useSlab || A.lng.contrib != nullptr || At.lng.contrib != nullptr || A.csr.nBlocks <= 0 || At.csr.nBlocks <= 0) return 0;
-    SmallQpKernel kq = pickQp(A.csr.chunk, At.csr.chunk, N->csr.chunk, 2);
-    if (!kq) return 0;
-    int perCu = 0, cus = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, kq, kSpmvThreads, 0) != hipSuccess) return 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
-    *residentOut = (perCu < 4 ? perCu : 4) * cus;
-    int g = A.csr.nBlocks > At.csr.nBlocks ? A.csr.nBlocks : At.csr.nBlocks;
+    k = reinterpret_cast<const void*>(pickQp(A.csr.chunk, At.csr.chunk, N->csr.chunk, 2));
+    if (!k) return 0;
     if (N->csr.nBlocks > g) g = N->csr.nBlocks;
-    return smallGridFor(g, n);
+  } else {
+    // (long majors ride along as segment tasks; beyond kLongSlotCap of them their contributions need the k_long_groups launch)
+    if (A.useSlab || At.useSlab || A.lng.contrib != nullptr || At.lng.contrib != nullptr) return 0;
+    // (the long rows' segment tasks gather x+ from memory: with them the P phase stays — standmps 11.2 -> 11.8 us per trial without it)
+    if (primalInA && A.lng.nTasks > 0) return 0;
+    // (the variants of one chunk pair differ little; mode 2 exists for all)
+    k = reinterpret_cast<const void*>(pick(A.csr.chunk, At.csr.chunk, 2, primalInA));
+    if (!k || A.csr.nBlocks <= 0 || At.csr.nBlocks <= 0) return 0;
   }
-  // (long majors ride along as segment tasks; beyond kLongSlotCap of them their contributions need the k_long_groups launch)
-  if (A.useSlab || At.useSlab || A.lng.contrib != nullptr || At.lng.contrib != nullptr) return 0;
-  // (the long rows' segment tasks gather x+ from memory: with them the P phase stays — standmps 11.2 -> 11.8 us per trial without it)
-  if (primalInA && A.lng.nTasks > 0) return 0;
-  SmallKernel k = pick(A.csr.chunk, At.csr.chunk, 2, primalInA);  // (the variants of one chunk pair differ little; mode 2 exists for all)
-  if (!k || A.csr.nBlocks <= 0 || At.csr.nBlocks <= 0) return 0;
   int perCu = 0, cus = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&perCu, k, kSpmvThreads, 0) != hipSuccess) return 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) return 0;
   // (blocks of >= 82 SGPRs: the hardware admits fewer per CU than the occupancy query says — MI355X_MICROARCH.md; stay far below)
   *residentOut = (perCu < 4 ? perCu : 4) * cus;
-  const int g = A.csr.nBlocks > At.csr.nBlocks ? A.csr.nBlocks : At.csr.nBlocks;
   return smallGridFor(g, n);  // the primal step alone never asks for more than 64 workgroups
 }
 
-void launchSmallTrials(const MatView& A, const MatView& At, const IterVecs& v, DevState* st, double* partDY, double* partDX,
-                       double* partInter, unsigned long long* bar, int32_t grid, int32_t maxTrials, int mode, hipStream_t s,
-                       int32_t timeoutMs, bool failRollCall, bool selfTest, unsigned long long seq, bool primalInA, const SmallQp* qp) {
+void launchSmallTrials(const SmallTrialsLaunch& q, int mode, hipStream_t s) {
   const bool xcdLocal = mode == 1;
+  const int32_t grid = q.grid;
   static_assert(kHierBarWords == kSmallHierWords, "barrier buffer layout");
   // mode 2: the hierarchical barrier's counters (and the roll-call word) start from zero in every launch; the other modes
   // keep their words — arrival epochs grow with the trial counter, the roll-call count with the launches (seq = 1, 2, ...
   // since the caller zeroed the buffer), so no memset launch sits between two launches of the loop
-  if (mode == 2) (void)hipMemsetAsync(bar, 0, smallBarWords(grid) * sizeof(unsigned long long), s);
-  SmallArgs a = smallArgsOf(A, At, v, st, partDY, partDX, partInter, bar, grid, maxTrials, mode, timeoutMs, failRollCall, selfTest, seq, primalInA);
+  if (mode == 2) (void)hipMemsetAsync(q.bar, 0, smallBarWords(grid) * sizeof(unsigned long long), s);
+  SmallArgs a = smallArgsOf(q, mode);
   if (a.selfTest)  // its words: the tail of the buffer
-    (void)hipMemsetAsync(bar + smallBarWords(grid) - (size_t)(2 * grid + 8), 0, (size_t)(2 * grid + 8) * sizeof(unsigned long long), s);
+    (void)hipMemsetAsync(q.bar + smallBarWords(grid) - (size_t)(2 * grid + 8), 0, (size_t)(2 * grid + 8) * sizeof(unsigned long long), s);
   static unsigned long long* prof = [] {  // PDLP_MI355X_SMALL_PROF=1: per-phase ticks, printed at exit (development)
     unsigned long long* p = nullptr;
     if (devEnv("PDLP_MI355X_SMALL_PROF") && hipMalloc((void**)&p, 64) == hipSuccess) {
@@ -820,12 +814,12 @@ void launchSmallTrials(const MatView& A, const MatView& At, const IterVecs& v, D
     return p;
   }();
   a.prof = prof;
-  if (qp) {
-    const SmallArgsQ q = smallArgsQOf(a, *qp);
-    hipLaunchKernelGGL(pickQp(A.csr.chunk, At.csr.chunk, qp->N.csr.chunk, mode), dim3(xcdLocal ? 8 * grid : grid), dim3(kSpmvThreads), 0, s, q);
+  if (q.qoff) {
+    const SmallArgsQ aq = smallArgsQOf(a, q.qp);
+    hipLaunchKernelGGL(pickQp(q.A.csr.chunk, q.At.csr.chunk, q.qp.N.csr.chunk, mode), dim3(xcdLocal ? 8 * grid : grid), dim3(kSpmvThreads), 0, s, aq);
     return;
   }
-  hipLaunchKernelGGL(pick(A.csr.chunk, At.csr.chunk, mode, primalInA), dim3(xcdLocal ? 8 * grid : grid), dim3(kSpmvThreads), 0, s, a);
+  hipLaunchKernelGGL(pick(q.A.csr.chunk, q.At.csr.chunk, mode, q.primalInA), dim3(xcdLocal ? 8 * grid : grid), dim3(kSpmvThreads), 0, s, a);
 }
 
 size_t smallLanesSlotBytes() { return kBatchLanes * sizeof(SmallArgsQ); }  // (the larger of the two record kinds)
@@ -834,39 +828,29 @@ bool smallLanesSupported(const MatView& A, const MatView& At, bool primalInA, co
   return pickLanes(A.csr.chunk, At.csr.chunk, primalInA) != nullptr;
 }
 namespace {
-int firstLane(const SmallLaneLaunch* lanes, int nLanes) {
-  for (int l = 0; l < nLanes && l < kBatchLanes; ++l)
-    if (lanes[l].grid > 0) return l;
-  return -1;
+// the eight argument records of a launch, of the LP or of the QP kind (a lane runs the XCD-local mode)
+void setLaneArgs(SmallArgs& out, const SmallTrialsLaunch& q) { out = smallArgsOf(q, 1); }
+void setLaneArgs(SmallArgsQ& out, const SmallTrialsLaunch& q) { out = smallArgsQOf(smallArgsOf(q, 1), q.qp); }
+template <class Args>
+void fillLanes(const SmallTrialsLaunch* lanes, int nLanes, Args* out) {
+  for (int l = 0; l < kBatchLanes; ++l) {
+    if (l < nLanes && lanes[l].grid > 0) setLaneArgs(out[l], lanes[l]);
+    else out[l] = Args{};
+  }
 }
 }  // namespace
-void fillSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, void* hostSlot) {
-  const int first = firstLane(lanes, nLanes);
-  if (first >= 0 && lanes[first].qoff) {  // lanes of one QP (a batch): records of the QP kind
-    SmallArgsQ* out = static_cast<SmallArgsQ*>(hostSlot);
-    for (int l = 0; l < kBatchLanes; ++l) {
-      if (l >= nLanes || lanes[l].grid <= 0) { out[l] = SmallArgsQ{}; continue; }
-      const SmallLaneLaunch& q = lanes[l];
-      out[l] = smallArgsQOf(smallArgsOf(q.A, q.At, q.v, q.st, q.partDY, q.partDX, q.partInter, q.bar, q.grid, q.maxTrials, 1, q.timeoutMs,
-                                        q.failRollCall, q.selfTest, q.seq, false), q.qp);
-    }
-    return;
-  }
-  SmallArgs* out = static_cast<SmallArgs*>(hostSlot);
-  for (int l = 0; l < kBatchLanes; ++l) {
-    if (l >= nLanes || lanes[l].grid <= 0) { out[l] = SmallArgs{}; continue; }
-    const SmallLaneLaunch& q = lanes[l];
-    out[l] = smallArgsOf(q.A, q.At, q.v, q.st, q.partDY, q.partDX, q.partInter, q.bar, q.grid, q.maxTrials, 1, q.timeoutMs, q.failRollCall,
-                         q.selfTest, q.seq, q.primalInA);
-  }
+void fillSmallTrialsLanes(const SmallTrialsLaunch* lanes, int nLanes, void* hostSlot) {
+  const int first = firstTakingLane(lanes, nLanes);
+  if (first >= 0 && lanes[first].qoff) fillLanes(lanes, nLanes, static_cast<SmallArgsQ*>(hostSlot));  // lanes of one QP (a batch)
+  else fillLanes(lanes, nLanes, static_cast<SmallArgs*>(hostSlot));
 }
-bool launchSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s) {
+bool launchSmallTrialsLanes(const SmallTrialsLaunch* lanes, int nLanes, const void* devSlot, hipStream_t s) {
   SmallLanesHdr h{};
   h.nLanes = nLanes;
   int maxG = 0, first = -1;
   bool mixed = false;
   for (int l = 0; l < nLanes && l < kBatchLanes; ++l) {
-    const SmallLaneLaunch& q = lanes[l];
+    const SmallTrialsLaunch& q = lanes[l];
     h.grid[l] = q.grid > 0 ? q.grid : 0;
     if (q.grid <= 0) continue;
     if (first < 0) first = l;
@@ -883,7 +867,7 @@ bool launchSmallTrialsLanes(const SmallLaneLaunch* lanes, int nLanes, const void
   }
   // (every lane has 512-entry blocks: smallLanesSupported.)  Lanes that agree on the barriers per trial — the lanes of a
   // batch always do — take the instantiation of their kind; only a launch that mixes the two kinds takes the mixed kernel.
-  const SmallLaneLaunch& f = lanes[first];
+  const SmallTrialsLaunch& f = lanes[first];
   SmallLanesKernel k = mixed ? k_trials_small_lanes_mixed<kChunkSmall, kChunkSmall> : pickLanes(f.A.csr.chunk, f.At.csr.chunk, f.primalInA);
   hipLaunchKernelGGL(k, dim3(8 * maxG), dim3(kSpmvThreads), 0, s, h, static_cast<const SmallArgs*>(devSlot));
   return mixed;

@@ -24,7 +24,7 @@ constexpr int kStatRowCur = 0, kStatRowAvg = kRowStats, kStatColCur = 2 * kRowSt
 // gap between two graph launches is ~40 us on this runtime, which was 4 us per iteration on small LPs.
 constexpr int kGraphTrials = 42;
 constexpr int kGraphMinTodo = 30;  // fewer trials than this to the next halt: launched one by one
-constexpr int kCheckInterval = 40;  // CUPDLP_RELEASE_INTERVAL, cupdlp_defs.h:39
+constexpr int kCheckInterval = kReleaseInterval;
 }  // namespace
 
 namespace {
@@ -1425,6 +1425,22 @@ void Solver::profCollect(int32_t realTrials) {
   profTrialsQueued_ = 0;
 }
 
+// The record of the next persistent trial launch, counted as launched: the first launch since create carries the XCD-local
+// mode's coherence self-test (and the roll-call fault a test asks for), every launch its number since gridBar_ was zeroed.
+SmallTrialsLaunch Solver::smallTrialsLaunch(int32_t maxTrials) {
+  SmallTrialsLaunch t;
+  t.A = dA_.view(); t.At = dAt_.view(); t.v = vecs_; t.st = dst();
+  t.partDY = partDY_.get(); t.partDX = partDX_.get(); t.partInter = partInter_.get(); t.bar = gridBar_.get();
+  t.grid = smallGrid_; t.maxTrials = maxTrials; t.timeoutMs = sw_.barrierTimeoutMs;
+  t.failRollCall = sw_.fault == 1 && smallLaunches_ == 0;
+  t.selfTest = smallLaunches_ == 0;
+  t.seq = ++smallSeq_;
+  t.primalInA = primalInA_;
+  if (hasQoff_) { t.qoff = true; t.qp = *smallQp(); }
+  ++smallLaunches_;
+  return t;
+}
+
 void Solver::enqueueTrial() {
   if (meshMode_) {
     // direct-exchange sequence (pdlp_mesh.hpp): X all-gather, Y all-gather, S scalars
@@ -1456,10 +1472,7 @@ void Solver::enqueueTrial() {
     return;
   }
   if (persistent_) {
-    launchSmallTrials(dA_.view(), dAt_.view(), vecs_, dst(), partDY_.get(), partDX_.get(), partInter_.get(), gridBar_.get(), smallGrid_, 1,
-                      smallMode(), stream_, sw_.barrierTimeoutMs, sw_.fault == 1 && smallLaunches_ == 0, smallLaunches_ == 0, ++smallSeq_, primalInA_,
-                      smallQp());
-    ++smallLaunches_;
+    launchSmallTrials(smallTrialsLaunch(1), smallMode(), stream_);
     return;
   }
   if (!sharded_ && fused_) {
@@ -1561,10 +1574,7 @@ void Solver::captureGraph() {
 // period of 40; single launches (the first ten iterations, profile mode) carry none — the caller looks at the state.
 void Solver::enqueueBatch(int32_t todo) {
   if (persistent_ && !profile_) {  // the whole stretch to the next check (plus spare trials for rejections) in one launch
-    launchSmallTrials(dA_.view(), dAt_.view(), vecs_, dst(), partDY_.get(), partDX_.get(), partInter_.get(), gridBar_.get(),
-                      smallGrid_, todo + 8, smallMode(), stream_, sw_.barrierTimeoutMs, sw_.fault == 1 && smallLaunches_ == 0,
-                      smallLaunches_ == 0, ++smallSeq_, primalInA_, smallQp());
-    ++smallLaunches_;
+    launchSmallTrials(smallTrialsLaunch(todo + kRoundSpareTrials), smallMode(), stream_);
     return;
   }
   if (useGraph_ && !persistent_ && !profile_ && (!sharded_ || meshMode_) && todo >= kGraphMinTodo) {
@@ -1586,7 +1596,7 @@ void Solver::runUntilHalt() {
   for (;;) {
     int64_t remaining = (int64_t)hostState_->haltIter - hostState_->nIter;
     if (remaining < 1) remaining = 1;
-    if (remaining > 4 * kCheckInterval) remaining = 4 * kCheckInterval;
+    if (remaining > kRoundMaxTodo) remaining = kRoundMaxTodo;
     int32_t todo = (int32_t)remaining;
     const int32_t trialsBefore = hostState_->nTrials;
     BarrierRound round{*this, beginBarrierRound()};
@@ -1597,16 +1607,7 @@ void Solver::runUntilHalt() {
     syncState();
     if (profile_) profCollect(hostState_->nTrials - trialsBefore);
     if (hostState_->halted) return;
-    // The reference's step-size search is a `while (!accepted)` loop: with NaN / Inf in the data it never ends.
-    // Here every stop checks that the search still makes progress.
-    if (hostState_->nIter == iterBefore && hostState_->nTrials - trialsBefore > 0) {
-      if (++stalledRounds_ >= 50)
-        throw std::runtime_error("pdlp_mi355x: the adaptive step-size search does not terminate (no trial step accepted in " +
-                                 std::to_string(hostState_->nTrials - stalledSince_) + " trials: NaN or Inf in the problem data?)");
-    } else {
-      stalledRounds_ = 0;
-      stalledSince_ = hostState_->nTrials;
-    }
+    checkStepSearch(iterBefore, trialsBefore);
     if (timeIsUp()) return;
     // a stretch without check iterations (check_interval beyond the host's 160-iteration rounds): keep the tabulated
     // powers of the step rule ahead of the trial counter (the fused / persistent kernels take no other)
@@ -1614,18 +1615,22 @@ void Solver::runUntilHalt() {
   }
 }
 
-int32_t Solver::defaultCheckInterval() { return kCheckInterval; }
-
-int32_t Solver::nextCheckIter(int32_t it) const {
-  const int32_t interval = opt_.check_interval > 0 ? opt_.check_interval : kCheckInterval;
-  int64_t next;
-  if (it + 1 < 10) next = it + 1;
-  else next = ((int64_t)it / interval + 1) * interval;
-  const int64_t last = (int64_t)opt_.iter_limit - 1;
-  if (last > it && last < next) next = last;
-  if (next > INT_MAX) next = INT_MAX;
-  return (int32_t)next;
+// The reference's step-size search is a `while (!accepted)` loop: with NaN / Inf in the data it never ends.  Here every
+// stop of the device (a host-driven stretch, a round of the device-driven loop, a lane's round) checks that the search
+// still makes progress.
+void Solver::checkStepSearch(int32_t iterBefore, int32_t trialsBefore) {
+  const DevState& s = *hostState_;
+  if (s.nIter == iterBefore && s.nTrials - trialsBefore > 0) {
+    if (++stalledRounds_ >= 50)
+      throw std::runtime_error("pdlp_mi355x: the adaptive step-size search does not terminate (no trial step accepted in " +
+                               std::to_string(s.nTrials - stalledSince_) + " trials: NaN or Inf in the problem data?)");
+  } else {
+    stalledRounds_ = 0;
+    stalledSince_ = s.nTrials;
+  }
 }
+
+int32_t Solver::nextCheckIter(int32_t it) const { return pdlp::nextCheckIter(it, checkInterval(), opt_.iter_limit); }
 
 // ---- check iteration -----------------------------------------------------------
 // PDHG_Compute_Average_Iterate, cupdlp_step.c:377-420
@@ -1843,6 +1848,24 @@ void Solver::downloadCtl() {
   if (c.terminated) { termCode_ = c.termCode; termIterate_ = c.termIterate; }
 }
 
+// The record of the next one-launch check, counted as launched: its slot of the ring, its number since checkBar_ was zeroed.
+CheckSmallLaunch Solver::checkSmallLaunch() {
+  CheckSmallLaunch c;
+  CheckRecord* rec = hostRing_ + (checkSeq_ % kRingSlots);
+  rec->ran = 0;
+  ++checkSeq_;
+  c.A = dA_.view(); c.At = dAt_.view(); c.v = vecs_; c.st = dst(); c.cc = dCtl_.get(); c.rec = rec;
+  c.r = RestartVecs{xAvg_.get(), yAvg_.get(), axAvg_.get(), atyAvg_.get(), hasQoff_ ? nxAvg_.get() : nullptr, xLast_.get(), yLast_.get()};
+  if (hasQoff_) { c.qoff = true; c.N = smallQp()->N; }
+  c.rowScale = rowScale_.get(); c.colScale = colScale_.get(); c.scaled = F_.scaled ? 1 : 0;
+  c.spC = slackPos_.get(); c.snC = slackNeg_.get(); c.spA = slackPosAvg_.get(); c.snA = slackNegAvg_.get();
+  c.statPart = statPart_.get(); c.statStride = statStride_; c.statOut = statOut_.get();
+  c.partX = partDX_.get(); c.partY = partRestartY_.get(); c.bar = checkBar_.get();
+  c.grid = smallGrid_; c.timeoutMs = sw_.barrierTimeoutMs; c.seq = ++checkSmallSeq_;
+  needPrimal_ = true;
+  return c;
+}
+
 // One check iteration behind whatever is queued: flush + averages, A xAvg, A'yAvg, the two statistics passes, their
 // reduction, then the scalar logic and the restart — every kernel a no-op unless the device has halted at a scheduled
 // iteration (checkDue).  10 launches, no host synchronisation.
@@ -1851,15 +1874,7 @@ void Solver::enqueueCheckDevice() {
   const CheckGate g{st, dCtl_.get()};
   if (persistent_ && checkSmall_) {
     // the small-LP form: the whole check is ONE launch of the trial loop's workgroups (pdlp_check.hip k_check_small)
-    CheckRecord* rec = hostRing_ + (checkSeq_ % kRingSlots);
-    rec->ran = 0;
-    ++checkSeq_;
-    const RestartVecs rv{xAvg_.get(), yAvg_.get(), axAvg_.get(), atyAvg_.get(), hasQoff_ ? nxAvg_.get() : nullptr, xLast_.get(), yLast_.get()};
-    launchCheckSmall(dA_.view(), dAt_.view(), vecs_, st, dCtl_.get(), rec, rv, rowScale_.get(), colScale_.get(), F_.scaled ? 1 : 0,
-                     slackPos_.get(), slackNeg_.get(), slackPosAvg_.get(), slackNegAvg_.get(), statPart_.get(), statStride_, statOut_.get(),
-                     partDX_.get(), partRestartY_.get(), checkBar_.get(), smallGrid_, ++checkSmallSeq_, sw_.barrierTimeoutMs, stream_,
-                     hasQoff_ ? &smallQp()->N : nullptr);
-    needPrimal_ = true;
+    launchCheckSmall(checkSmallLaunch(), stream_);
     return;
   }
   if (sharded_) {
@@ -1951,96 +1966,90 @@ void Solver::processRecords(bool terminate, int64_t iterLim, int& logSinceHeader
 // after once per round instead of once per check.  What the device does between two looks is exactly what the
 // host-driven loop (doSolve) does: same kernels for the trials, same statistics, the same scalar arithmetic.
 void Solver::doSolveDevice(bool terminate, int32_t target) {
-  DevState& s = *hostState_;
-  const int64_t iterLim = terminate ? (int64_t)opt_.iter_limit : (int64_t)target;
-  const int32_t interval = opt_.check_interval > 0 ? opt_.check_interval : kCheckInterval;
-  if (s.nIter >= iterLim) return;
-  uploadCtl(terminate, iterLim);
-  checkSeen_ = checkSeq_;
-  auto onSchedule = [&](int64_t it) { return it < 10 || it % interval == 0 || (terminate && it == (int64_t)opt_.iter_limit - 1); };
-  auto haltAfter = [&](int64_t it) {
-    int64_t h = nextCheckIter((int32_t)it);
-    if (!terminate && h > iterLim) h = iterLim;
-    return h;
-  };
-  // entry: a check is due right here (the device "halts" at the current iteration), or the device runs on to the next one
-  if (onSchedule(s.nIter)) {
-    s.haltIter = s.nIter;
-    s.halted = 1;
-  } else {
-    s.haltIter = (int32_t)haltAfter(s.nIter);
-    s.halted = 0;
-  }
-  pushState(false);
-  int logSinceHeader = 50;
+  if (!beginDeviceLoop(terminate, terminate ? (int64_t)opt_.iter_limit : (int64_t)target)) return;
   int32_t ahead = 1, aheadMax = 16;
-  bool timeUp = false;
   for (;;) {
     const auto roundBeg = std::chrono::steady_clock::now();
-    const int32_t iterBefore = s.nIter, trialsBefore = s.nTrials;
-    const int64_t seq0 = checkSeq_;
     BarrierRound round{*this, beginBarrierRound()};
-    std::unique_lock<std::mutex>& gate = round.gate;
-    int64_t itExp = s.nIter, haltExp = s.haltIter;
-    if (s.halted) {  // (entry only: every batch below is followed by its check)
-      enqueueCheckDevice();
-      haltExp = haltAfter(itExp);
-    }
-    int32_t units = 0;
-    int64_t queuedTrials = 0;  // (the tabulated powers of the step rule reach 4096 trials beyond the last refresh)
-    for (int32_t u = 0; u < ahead && queuedTrials < 3000; ++u) {
-      int64_t todo = haltExp - itExp;
-      if (todo < 1) todo = 1;
-      if (todo > 4 * kCheckInterval) todo = 4 * kCheckInterval;
-      // single launches carry their own spare trials (a rejected trial must not cost a host round trip)
+    const RoundPlan plan = beginRound(ahead);
+    if (plan.entryCheck) enqueueCheckDevice();
+    for (int32_t u = 0; u < plan.nTodo; ++u) {
+      const int32_t todo = plan.todo[u];
+      // Only here, never in a lane (its loop is persistent): single launches carry their own spare trials (a rejected
+      // trial must not cost a host round trip)
       const bool batched = persistent_ || (useGraph_ && todo >= kGraphMinTodo);
-      enqueueBatch((int32_t)todo + (batched ? 0 : todo >= 8 ? 2 : 1));
+      enqueueBatch(todo + (batched ? 0 : todo >= 8 ? 2 : 1));
       enqueueCheckDevice();
-      ++units;
-      queuedTrials += todo + 8;
-      itExp = std::min(itExp + todo, haltExp);
-      if (itExp >= iterLim || (terminate && itExp >= iterLim - 1)) break;  // the target / the check that ends the solve
-      if (itExp == haltExp) haltExp = haltAfter(itExp);
     }
-    endBarrierRound(gate);
-    syncState();
+    endBarrierRound(round.gate);
+    syncState();  // (with this path's fall-backs for a commError; a lane hands them to its driver: laneAfterRound)
     if (meshMode_) {  // (sharded: the exchange's error flag and the checksum guard of the replicated iterates, once per round)
+      const DevState& s = *hostState_;
       mesh_->checkError(stream_);
       mesh_->verifyReplicated(x_[s.cur].get(), F_.n, stream_);
       mesh_->verifyReplicated(y_[s.cur].get(), F_.m, stream_);
     }
-    processRecords(terminate, iterLim, logSinceHeader);
-    bool over = false;  // a check of this round has ended the solve (everything queued behind it was a no-op)
-    for (int64_t q = seq0; q < checkSeq_; ++q) over = over || (hostRing_[q % kRingSlots].ran && hostRing_[q % kRingSlots].terminated);
-    if (over) break;
-    if (!terminate && s.nIter >= iterLim) break;
-    // The reference's step-size search is a `while (!accepted)` loop: with NaN / Inf in the data it never ends.
-    if (s.nIter == iterBefore && s.nTrials - trialsBefore > 0) {
-      if (++stalledRounds_ >= 50)
-        throw std::runtime_error("pdlp_mi355x: the adaptive step-size search does not terminate (no trial step accepted in " +
-                                 std::to_string(s.nTrials - stalledSince_) + " trials: NaN or Inf in the problem data?)");
-    } else {
-      stalledRounds_ = 0;
-      stalledSince_ = s.nTrials;
-    }
-    if (timeIsUp()) { timeUp = true; break; }
-    // tabulated powers of the step rule: kept ahead of the trial counter while the stream is idle
-    if (s.powRed && s.nTrials + 4096 >= s.powBase + s.powCount) pushState(false);
-    // queue depth: ~25 ms of work, at most 16 units
+    // (the stream is idle and the next launches come on it: the refreshed powers need not be waited for)
+    if (!afterRound(false)) break;
     const double roundMs = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - roundBeg).count();
-    // (sharded: every rank must queue the same units per round — the rounds end in collectives — so the depth does not
-    // follow this rank's clock there: 1, 2, 4, 4, ...)
-    if (sharded_) aheadMax = 4;
-    else if (units > 0 && roundMs > 0.0) aheadMax = std::max(1, std::min(16, (int32_t)(25.0 * units / roundMs)));
-    ahead = std::min(ahead * 2, aheadMax);
+    ahead = nextQueueDepth(ahead, aheadMax, plan.nTodo, roundMs, sharded_);  // (sharded: only a solver alone can be)
   }
-  endDeviceLoop(terminate, timeUp, logSinceHeader);
+  endDeviceLoop();
+}
+
+// The head of a device-driven loop: the control record up, the entry rule (pdlp_round.hpp) into the state record, the state
+// pushed without waiting for it.  terminate == false (the fixed-work loop up to iterLim) is known to iterate() only.
+bool Solver::beginDeviceLoop(bool terminate, int64_t iterLim) {
+  DevState& s = *hostState_;
+  loop_ = DeviceLoop();
+  loop_.sched = RoundLoop{iterLim, terminate, checkInterval(), opt_.iter_limit};
+  if (s.nIter >= iterLim) {
+    loop_.noLoop = true;
+    return false;
+  }
+  uploadCtl(terminate, iterLim);
+  checkSeen_ = checkSeq_;
+  const RoundEntry e = roundEntry(s.nIter, loop_.sched);
+  s.haltIter = e.haltIter;
+  s.halted = e.halted;
+  pushState(false);
+  return true;
+}
+
+// The plan of the next round from the state record as the last round left it; what afterRound compares with is noted.
+RoundPlan Solver::beginRound(int32_t ahead) {
+  const DevState& s = *hostState_;
+  loop_.iterBefore = s.nIter;
+  loop_.trialsBefore = s.nTrials;
+  loop_.seq0 = checkSeq_;
+  return planRound(s.nIter, s.haltIter, s.halted != 0, ahead, loop_.sched);
+}
+
+// The host's look at a round once its state record is here: log and restart notes, whether a check of the round has ended
+// the solve (or the fixed-work target is reached), the stall guard, the time limit (-> loop_.timeUp), the tabulated powers.
+bool Solver::afterRound(bool pushWaits) {
+  const DevState& s = *hostState_;
+  processRecords(loop_.sched.terminate, loop_.sched.iterLim, loop_.logSinceHeader);
+  bool over = false;  // a check of this round has ended the solve (everything queued behind it was a no-op)
+  for (int64_t q = loop_.seq0; q < checkSeq_; ++q) over = over || (hostRing_[q % kRingSlots].ran && hostRing_[q % kRingSlots].terminated);
+  if (over) return false;
+  if (!loop_.sched.terminate && s.nIter >= loop_.sched.iterLim) return false;
+  checkStepSearch(loop_.iterBefore, loop_.trialsBefore);
+  if (timeIsUp()) {
+    loop_.timeUp = true;
+    return false;
+  }
+  // tabulated powers of the step rule: kept ahead of the trial counter while the stream is idle
+  if (s.powRed && s.nTrials + 4096 >= s.powBase + s.powCount) pushState(pushWaits);
+  return true;
 }
 
 // The end of a device-driven loop (doSolveDevice; a batch lane, pdlp_batch_lanes.cpp): the control record back to the host's
 // mirrors and, after the time limit, the check the reference makes at once.
-void Solver::endDeviceLoop(bool terminate, bool timeUp, int& logSinceHeader) {
+void Solver::endDeviceLoop() {
   DevState& s = *hostState_;
+  const bool terminate = loop_.sched.terminate, timeUp = loop_.timeUp;
+  int& logSinceHeader = loop_.logSinceHeader;
   downloadCtl();
   if (timeUp) {
     // The time limit: the reference checks at once and stops (cupdlp_solver.c:953-962).  The device stands right behind

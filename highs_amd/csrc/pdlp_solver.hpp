@@ -15,6 +15,7 @@
 #include "pdlp_host.hpp"
 #include "pdlp_kernels.hpp"
 #include "pdlp_mesh.hpp"
+#include "pdlp_round.hpp"
 #include "pdlp_setup.hpp"
 
 namespace pdlp {
@@ -160,24 +161,24 @@ class Solver : public SolverBase {
   size_t sessionHeldBytes() const;  // HBM kept for reuse beyond a plain solver's
 
   // ---- what a batch and a pool drive (pdlp_batch.hpp, pdlp_pool.hpp; all in pdlp_batch_lanes.cpp) ----
-  // run() cut into the steps of ONE lane of a batch, whose launches are shared with other solvers of the same problem:
-  // laneBegin = run() up to its first round; laneQueue = the units [trial batch][check] of the next round as
-  // doSolveDevice would enqueue them, handed out as launch records and accounted for as if launched (units[0] may be the
-  // entry's check alone); laneDownload / laneAfterRound = syncState + processRecords + the loop's tail; laneFinish = what
-  // run() does behind its loop.  Between laneBegin and laneFinish nothing else may be asked of the solver.
+  // run() cut into the steps of ONE lane of a batch, whose launches are shared with other solvers of the same problem.
+  // The steps are the pieces doSolveDevice is made of (beginDeviceLoop, beginRound, afterRound, endDeviceLoop): laneBegin =
+  // run() up to its first round; laneQueue = the units [trial batch][check] of the next round, handed out as launch
+  // records and accounted for as if launched (units[0] may be the entry's check alone); laneDownload / laneAfterRound =
+  // syncState + the round's verdict; laneFinish = what run() does behind its loop.  Between laneBegin and laneFinish
+  // nothing else may be asked of the solver.
   // laneSequentialReason: empty, or why this solver's launches cannot be shared (it then runs alone)
   std::string laneSequentialReason() const;
   bool hasOffDiagonalHessian() const { return hasQoff_; }
   int32_t laneWorkBlocks() const { return smallGrid_; }
-  static int32_t defaultCheckInterval();  // CUPDLP_RELEASE_INTERVAL
   // the refusals of update(u) that do not depend on the device, with update's words; nothing is changed
   void validateUpdate(const pdlp_update_t& u) const;
   void laneBegin();
-  bool laneIdle() const { return lane_.noLoop; }  // the iteration limit is reached before the first round: laneFinish may follow at once
+  bool laneIdle() const { return loop_.noLoop; }  // the iteration limit is reached before the first round: laneFinish may follow at once
   void laneQueue(int32_t ahead, std::vector<LaneUnit>& units);
   void laneDownload(hipStream_t shared);  // the state record -> host mirror, behind the round's launches
   LaneVerdict laneAfterRound();           // (the shared stream has been synchronised)
-  int32_t laneCommError() const { return lane_.commError; }
+  int32_t laneCommError() const { return loop_.commError; }
   int32_t laneXcc();                      // the XCC id this solver's workers published at their last placement check, or -1
   void laneFinish(pdlp_result_t* R);
   hipStream_t laneStream() const { return stream_; }
@@ -228,10 +229,19 @@ class Solver : public SolverBase {
   bool checkTermination(const Residuals& r) const;
   bool checkInfeasibility();
   void restartIterate();
+  int32_t checkInterval() const { return opt_.check_interval > 0 ? opt_.check_interval : kReleaseInterval; }
   int32_t nextCheckIter(int32_t it) const;
+  void checkStepSearch(int32_t iterBefore, int32_t trialsBefore);  // throws once 50 stops in a row have accepted no trial
   void doSolve(bool terminate, int32_t iterBudget);        // check iterations driven by the host (sharded paths, profile mode)
   void doSolveDevice(bool terminate, int32_t iterBudget);  // check iterations on the device, several periods queued ahead
-  void endDeviceLoop(bool terminate, bool timeUp, int& logSinceHeader);
+  // ... in the pieces a lane of a batch is driven by as well (pdlp_batch_lanes.cpp); their state between the calls is loop_
+  bool beginDeviceLoop(bool terminate, int64_t iterLim);  // false: the limit is reached, there is no loop (and no endDeviceLoop)
+  RoundPlan beginRound(int32_t ahead);                    // the units to queue now (pdlp_round.hpp)
+  bool afterRound(bool pushWaits);                        // the host's look at a finished round; true: queue the next one
+  void endDeviceLoop();
+  // the records of a persistent trial launch and of a one-launch check, accounted for as launched: every caller's way to them
+  SmallTrialsLaunch smallTrialsLaunch(int32_t maxTrials);
+  CheckSmallLaunch checkSmallLaunch();
   void finishRun(pdlp_result_t* R);
   void enqueueCheckDevice();
   void uploadCtl(bool terminate, int64_t iterLim);
@@ -373,12 +383,14 @@ class Solver : public SolverBase {
     ~BarrierRound();
   };
   int32_t stalledRounds_ = 0, stalledSince_ = 0;  // consecutive device stops without an accepted trial
-  struct LaneRun {  // the locals of doSolveDevice for a run driven as a batch lane
-    int64_t iterLim = 0, seq0 = 0;
-    int32_t iterBefore = 0, trialsBefore = 0, commError = 0;
+  struct DeviceLoop {  // a device-driven loop between its pieces: beginDeviceLoop .. endDeviceLoop
+    RoundLoop sched{};
+    int64_t seq0 = 0;                                 // the round under way: its first check, the counters in front of it
+    int32_t iterBefore = 0, trialsBefore = 0;
+    int32_t commError = 0;                            // (a lane: why it left its shared launches)
     int logSinceHeader = 50;
     bool noLoop = false, timeUp = false;
-  } lane_;
+  } loop_;
   // Device-driven check iterations (pdlp_kernels.hpp CheckCtl; PDLP_MI355X_DEVICE_CHECK=0 gives the host-driven loop back)
   bool devCheck_ = true;
   DeviceArray<CheckCtl> dCtl_;

@@ -1,6 +1,6 @@
 """pdlp_mi355x_batch_* without a GPU: the fixed points of the ABI, the refusals of batch_create that are decided before
-any device call (pinned by their words), and the batch driver behind canned lanes under AddressSanitizer + UBSan as a
-stand-alone program."""
+any device call (pinned by their words), and the batch driver behind canned lanes and the schedule of a device-driven
+round under AddressSanitizer + UBSan as stand-alone programs."""
 import ctypes as C
 import os
 import subprocess
@@ -90,5 +90,14 @@ def test_driver_behind_canned_lanes_under_sanitizers(tmp_path):
     (csrc/pdlp_batch.cpp) with lanes that replay canned verdicts: a host program of its own, never loaded into Python."""
     env = dict(os.environ, OUT=str(tmp_path / "batch_driver_check"))
     r = subprocess.run(["bash", os.path.join(ROOT, "tools", "batch_driver_check.sh")], env=env, capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "all scenarios passed" in r.stdout
+
+
+def test_round_plan_follows_the_reference_schedule_under_sanitizers(tmp_path):
+    """The planner, the entry rule and the queue-depth rule of csrc/pdlp_round.hpp, driven round after round by a host
+    program of its own that plays the device (tools/round_plan_check.cpp), never loaded into Python."""
+    env = dict(os.environ, OUT=str(tmp_path / "round_plan_check"))
+    r = subprocess.run(["bash", os.path.join(ROOT, "tools", "round_plan_check.sh")], env=env, capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "all scenarios passed" in r.stdout

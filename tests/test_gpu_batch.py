@@ -9,6 +9,8 @@ import re
 import numpy as np
 import pytest
 
+import oraclelib as O
+import qp_small_cases as QC
 import update_cases as UC
 from highs_amd import solver
 from highs_amd import lp as L
@@ -195,3 +197,41 @@ def test_a_solo_solve_next_to_a_batch_keeps_its_bits():
     _run_and_compare(name, batch, tagged)
     batch.close()
     _assert_same_result(solver.solveLpCupdlp(lp, **OPTIONS).result, before.result, "solo after the batch is gone")
+
+
+# What no bit-exact test sees: how the host cuts the trials into launches.  A solve's bits do not depend on it, its host
+# round trips do.  Inputs and limit are chosen so that the oracle rejects at most 8 trials in the WHOLE solve (with
+# kkt_tolerance 1e-4 and a limit of 300 iterations it ends afiro at iteration 200 after 201 trials, one rejection, and
+# portfolio64 at iteration 120 after 128 trials, eight rejections): then no period can outrun the 8 spare trials of its
+# launch, and every scheduled check behind the start costs exactly one persistent launch.
+ROUND = dict(kkt_tolerance=1e-4, pdlp_iteration_limit=300)
+
+
+@pytest.mark.parametrize("name", ["afiro", "portfolio64"])
+def test_one_persistent_launch_per_period_alone_and_in_a_batch(name, monkeypatch):
+    monkeypatch.setenv("PDLP_MI355X_SLAB", "0")  # (the oracle's layout)
+    lp = QC.portfolio() if name == "portfolio64" else _lp(name)
+    cpu = O.oracle_solve(lp, device_reduction_order=True, device_layout="csr", **ROUND)
+    print(name, "oracle: iterations", cpu.num_iter, "trials", cpu.num_trials)
+    assert 0 <= cpu.num_trials - cpu.num_iter <= 8  # the precondition
+    ds = solver.DeviceSolver(lp, **ROUND)
+    before = ds.stage("persistent_launches", 1)[0]
+    R = ds.solve().result
+    launches = int(ds.stage("persistent_launches", 1)[0] - before)
+    ds.close()
+    assert (R.num_iter, R.num_trials) == (cpu.num_iter, cpu.num_trials)  # (the run the precondition speaks of)
+    N, limit = R.num_iter, ROUND["pdlp_iteration_limit"]
+    # the scheduled checks in (0, N], by the reference's rule (cupdlp_solver.c:953-962)
+    U = sum(1 for it in range(1, N + 1) if it < 10 or it % 40 == 0 or it == limit - 1)
+    print(name, "iterations", N, "scheduled checks", U, "persistent launches", launches)
+    # (the 15: the units of a last round of 16 that lay behind the terminating one)
+    assert U <= launches <= U + 15, (U, launches)
+    batch = solver.DeviceBatch(lp, lanes=2, **ROUND)
+    out = batch.run([{}, {}])
+    I = batch.info()
+    batch.close()
+    print(name, "batch info:", I.text, I.lanes_concurrent, I.trial_launches, I.check_launches)
+    assert (I.lanes_concurrent, I.fallback_variants) == (2, 0), I.text
+    assert [o.result.num_iter for o in out] == [N, N]
+    assert U <= I.trial_launches <= U + 15, (U, I.trial_launches)
+    assert I.check_launches == I.trial_launches + 1
