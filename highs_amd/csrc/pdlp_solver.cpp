@@ -2274,8 +2274,11 @@ std::pair<double*, int64_t> Solver::lookup(const std::string& name) {
   if (name == "row_scale") return {rowScale_.get(), m};
   if (name == "slack_pos") return {slackPos_.get(), n};
   if (name == "slack_neg") return {slackNeg_.get(), n};
+  if (name == "slack_pos_avg") return {slackPosAvg_.get(), n};
+  if (name == "slack_neg_avg") return {slackNegAvg_.get(), n};
   if (qdiag_.size() && name == "qdiag") return {qdiag_.get(), n};
   if (hasQoff_ && name == "nx") return {nx_[c].get(), n};
+  if (hasQoff_ && name == "nx_avg") return {nxAvg_.get(), n};
   if (hasQoff_ && name == "nx_next") return {nx_[u].get(), n};
   throw std::runtime_error("unknown vector name: " + name);
 }
@@ -2419,6 +2422,46 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     put(0, cur_.pObj); put(1, cur_.dObj); put(2, cur_.pFeas); put(3, cur_.dFeas);
     put(4, avg_.pObj); put(5, avg_.dObj); put(6, avg_.pFeas); put(7, avg_.dFeas);
     put(8, cur_.pInfObj); put(9, cur_.pInfRes); put(10, cur_.dInfObj); put(11, cur_.dInfRes);
+  } else if (name == "check_stats") {  // launches nothing: [0, 30) the sums as the last executed check left them (row current,
+    // row average, column current, column average), [30, 40) the ten numbers of the current iterate in the order of
+    // Residuals, [40, 50) those of the average iterate
+    double stats[kStatTotal];
+    PDLP_HIP(hipMemcpyAsync(stats, statOut_.get(), sizeof(stats), hipMemcpyDeviceToHost, stream_));
+    PDLP_HIP(hipStreamSynchronize(stream_));
+    for (int k = 0; k < kStatTotal; ++k) put(k, stats[k]);
+    const Residuals* both[2] = {&cur_, &avg_};
+    for (int k = 0; k < 2; ++k) {
+      const Residuals& r = *both[k];
+      const double v[10] = {r.pObj, r.dObj, r.gap, r.relGap, r.pFeas, r.dFeas, r.pInfObj, r.pInfRes, r.dInfObj, r.dInfRes};
+      for (int q = 0; q < 10; ++q) put(kStatTotal + 10 * k + q, v[q]);
+    }
+  } else if (name == "check_device") {  // exactly one check of the present state in the device-driven form this solver's loop
+    // uses (enqueueCheckDevice): the fixed-work loop's control record with target nIter + 1 and restarts off, so that no
+    // vector is rewritten but by the flush of the pending averages; [0] = the record's `ran`.  Never forced: an iteration
+    // that is not on the schedule is refused.  A reset() restores everything this touches.
+    if (!devCheck_ || sharded_) throw std::runtime_error("check_device: the checks of this solver are not driven by one device");
+    DevState& s = *hostState_;
+    const int32_t it = s.nIter;
+    if (!(it < 10 || it % checkInterval() == 0))
+      throw std::runtime_error("check_device: iteration " + std::to_string(it) + " is not a check iteration");
+    CheckRecord* rec = nullptr;
+    {
+      BarrierRound round{*this, beginBarrierRound()};
+      const bool restartWas = restartOn_;
+      restartOn_ = false;
+      uploadCtl(false, (int64_t)it + 1);
+      restartOn_ = restartWas;
+      s.haltIter = it;
+      s.halted = 1;
+      pushState(false);
+      rec = hostRing_ + (checkSeq_ % kRingSlots);
+      enqueueCheckDevice();
+      endBarrierRound(round.gate);
+    }
+    syncState();
+    downloadCtl();
+    checkSeen_ = checkSeq_;
+    put(0, (double)rec->ran);
   } else {
     throw std::runtime_error("unknown stage: " + name);
   }

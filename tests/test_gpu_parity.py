@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import check_cases as K
 import oraclelib as O
 from highs_amd import abi, solver
 from highs_amd import lp as L
@@ -211,6 +212,19 @@ def test_residuals_match_numpy_restatement():
     dfeas = np.linalg.norm((rc - sp_ + sn_) * Fv.col_scale)
     assert np.allclose(out[:4], [pobj, dobj, pfeas, dfeas], rtol=1e-11, atol=1e-13)
     assert np.array_equal(S.get("slack_pos", n), sp_) and np.array_equal(S.get("slack_neg", n), sn_)
+    # the other eight: the same four of the average iterate, then the two rays of the current one (objective and residual of
+    # the primal and of the dual infeasibility certificate) — from the reference of tests/check_cases.py on the vectors
+    # the check has left (numpy sums here too: the same tolerance)
+    v = dict(cost=Fv.cost, rhs=Fv.rhs, lower=Fv.lower, upper=Fv.upper, col_scale=Fv.col_scale, row_scale=Fv.row_scale, x=x, y=y, ax=ax, aty=aty,
+             x_avg=S.get("x_avg", n), y_avg=S.get("y_avg", m), ax_avg=S.get("ax_avg", m), aty_avg=S.get("aty_avg", n))
+    ref = K.reference_stats(v, Fv.n_eqs, True)
+    d = dict(zip([k + i for i in ("_cur", "_avg") for k in K.DERIVED_NAMES],
+                 K.derived([float(np.sum(q.terms)) for q in ref["q"]], False, lp.sense, lp.offset)))
+    assert np.allclose(out[:4], [d["pObj_cur"], d["dObj_cur"], d["pFeas_cur"], d["dFeas_cur"]], rtol=1e-11, atol=1e-13)
+    want = [d["pObj_avg"], d["dObj_avg"], d["pFeas_avg"], d["dFeas_avg"], d["pInfObj_cur"], d["pInfRes_cur"], d["dInfObj_cur"], d["dInfRes_cur"]]
+    print("residuals stage [4, 12):", out[4:12], "restated:", want)
+    assert np.allclose(out[4:12], want, rtol=1e-11, atol=1e-13)
+    assert np.array_equal(S.get("slack_pos_avg", n), ref["slack_pos_avg"]) and np.array_equal(S.get("slack_neg_avg", n), ref["slack_neg_avg"])
     S.close()
 
 
