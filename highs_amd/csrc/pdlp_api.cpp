@@ -404,9 +404,8 @@ int pdlp_mi355x_host_prepare_updated(const pdlp_problem_t* P, const pdlp_params_
     if (!P || !opt || !out) throw std::runtime_error("null argument");
     if (!u) throw std::runtime_error("pdlp_mi355x_update: null update");
     // the refusals of pdlp_mi355x_update that depend on how the solver was created
-    if (opt->algorithm == 1) throw std::runtime_error("pdlp_mi355x_update: HiPDLP solvers (algorithm = 1) do not take updates");
-    if (!opt->updatable)
-      throw std::runtime_error("pdlp_mi355x_update: the solver was not created for updates (pdlp_params_t.updatable = 0)");
+    if (opt->algorithm == 1) pdlp::refuseHipdlp(pdlp::kEntryUpdate);
+    if (!opt->updatable) pdlp::refuseNotUpdatable(pdlp::kEntryUpdate);
     hostPrepare(P, opt, u, out);
   });
 }
@@ -418,14 +417,9 @@ int pdlp_mi355x_host_prepare_updated_matrix_then(const pdlp_problem_t* P, const 
   return guarded([&] {
     if (!P || !opt || !out) throw std::runtime_error("null argument");
     // the refusals of pdlp_mi355x_update_matrix that depend on how the solver was created
-    if (opt->algorithm == 1)
-      throw std::runtime_error("pdlp_mi355x_update_matrix: HiPDLP solvers (algorithm = 1) do not take updates");
-    if (!(opt->updatable & PDLP_UPDATABLE_MATRIX))
-      throw std::runtime_error("pdlp_mi355x_update_matrix: the solver was not created for matrix updates (pdlp_params_t.updatable "
-                               "lacks PDLP_UPDATABLE_MATRIX)");
-    if (pdlp::hessianHasOffDiagonal(*P))
-      throw std::runtime_error("pdlp_mi355x_update_matrix: QPs whose Hessian has off-diagonal entries do not take matrix updates "
-                               "(the scaled copy of the Hessian follows the column factors; left for a later change)");
+    if (opt->algorithm == 1) pdlp::refuseHipdlp(pdlp::kEntryUpdateMatrix);
+    if (!(opt->updatable & PDLP_UPDATABLE_MATRIX)) pdlp::refuseNoMatrixBit(pdlp::kEntryUpdateMatrix);
+    if (pdlp::hessianHasOffDiagonal(*P)) pdlp::refuseOffDiagonalHessian(pdlp::kEntryUpdateMatrix);
     if (!a_value) throw std::runtime_error("pdlp_mi355x_update_matrix: a_value is NULL");
     hostPrepare(P, opt, u_then, out, a_value, u);
   });
@@ -448,14 +442,9 @@ int pdlp_mi355x_host_prepare_qp_then(const pdlp_problem_t* P, const pdlp_params_
     const bool change = a_value || q_value || u || u_then;
     const bool keepQ = (opt->updatable & PDLP_UPDATABLE_HESSIAN) != 0;
     if (change) {  // the refusals of pdlp_mi355x_update_values that depend on how the solver was created
-      if (opt->algorithm == 1)
-        throw std::runtime_error("pdlp_mi355x_update_values: HiPDLP solvers (algorithm = 1) do not take updates");
-      if (!keepQ)
-        throw std::runtime_error("pdlp_mi355x_update_values: the solver was not created for Hessian updates (pdlp_params_t.updatable "
-                                 "lacks PDLP_UPDATABLE_HESSIAN)");
-      if (a_value && !(opt->updatable & PDLP_UPDATABLE_MATRIX))
-        throw std::runtime_error("pdlp_mi355x_update_values: a_value given, but the solver was not created for matrix updates "
-                                 "(pdlp_params_t.updatable lacks PDLP_UPDATABLE_MATRIX)");
+      if (opt->algorithm == 1) pdlp::refuseHipdlp(pdlp::kEntryUpdateValues);
+      if (!keepQ) pdlp::refuseNoHessianBit(pdlp::kEntryUpdateValues);
+      if (a_value && !(opt->updatable & PDLP_UPDATABLE_MATRIX)) pdlp::refuseNoMatrixBit(pdlp::kEntryUpdateValues);
     }
     if (opt->algorithm == 1) throw std::runtime_error("pdlp_mi355x_host_prepare_qp: the cuPDLP-C form only (algorithm = 0)");
     pdlp::StandardForm F;
@@ -475,10 +464,7 @@ int pdlp_mi355x_host_prepare_qp_then(const pdlp_problem_t* P, const pdlp_params_
         static const pdlp_update_t kNoData{};
         const pdlp_update_t& ud = u ? *u : kNoData;
         pdlp::checkUpdateShape(ud);
-        if (pdlp::updateMask(ud) & pdlp::kUpdRows) {
-          const int32_t bad = pdlp::firstKindChange(F.rowKind.data(), F.m, ud.row_lower, ud.row_upper);
-          if (bad < F.m) pdlp::throwKindChange(bad, F.rowKind[bad], pdlp::rowKindOf(ud.row_lower[bad], ud.row_upper[bad]));
-        }
+        if (pdlp::updateMask(ud) & pdlp::kUpdRows) pdlp::refuseKindChange(F.rowKind.data(), F.m, ud.row_lower, ud.row_upper);
         if (q_value) pdlp::hostReplayHessianUpdate(q_value, F);  // (validates before it writes; u has been validated above)
         pdlp::hostReplayUpdate(ud, F);
       }

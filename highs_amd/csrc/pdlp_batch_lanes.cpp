@@ -34,16 +34,11 @@ std::string Solver::laneSequentialReason() const {
 }
 
 void Solver::validateUpdate(const pdlp_update_t& u) const {
-  if (sharded_)
-    throw std::runtime_error("pdlp_mi355x_update: sharded solvers (pdlp_mi355x_create_sharded) do not take updates");
-  if (!updatable_)
-    throw std::runtime_error("pdlp_mi355x_update: the solver was not created for updates (pdlp_params_t.updatable = 0)");
+  if (sharded_) refuseSharded(kEntryUpdate);
+  if (!updatable_) refuseNotUpdatable(kEntryUpdate);
   checkUpdateShape(u);
-  if (u.row_lower) {  // (the rule of the device's validation kernel, on the host's copy of the kinds)
-    const int32_t m = F_.m;
-    const int32_t bad = firstKindChange(F_.rowKind.data(), m, u.row_lower, u.row_upper);
-    if (bad < m) throwKindChange(bad, F_.rowKind[bad], rowKindOf(u.row_lower[bad], u.row_upper[bad]));
-  }
+  // (the rule of the device's validation kernel, on the host's copy of the kinds)
+  if (u.row_lower) refuseKindChange(F_.rowKind.data(), F_.m, u.row_lower, u.row_upper);
 }
 
 // run() up to the first round of its device-driven loop

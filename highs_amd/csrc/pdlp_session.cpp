@@ -158,17 +158,17 @@ void Solver::sessionAdopt(const pdlp_problem_t& P) {
   if (qSlots > 0 && (!hessianUpdatable_ || hk_.nSlots != qSlots))
     throw std::runtime_error("pdlp_mi355x_session_solve: the solver kept nothing for Hessian updates");
   PDLP_HIP(hipSetDevice(opt_.device));
-  sessIn_.alloc((size_t)3 * n0 + (size_t)2 * m);
+  sessIn_.alloc(DataStage::count(n0, m));
   sessMat_.alloc((size_t)nnzIn_);
-  double* d = sessIn_.get();
+  const DataStage d = DataStage::over(sessIn_.get(), n0, m);
   auto put = [&](double* dev, const double* host, int64_t count) {
     if (count > 0) PDLP_HIP(hipMemcpyAsync(dev, host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, stream_));
   };
-  put(d, P.col_cost, n0);
-  put(d + n0, P.col_lower, n0);
-  put(d + 2 * (size_t)n0, P.col_upper, n0);
-  put(d + 3 * (size_t)n0, P.row_lower, m);
-  put(d + 3 * (size_t)n0 + m, P.row_upper, m);
+  put(d.cost, P.col_cost, n0);
+  put(d.colLower, P.col_lower, n0);
+  put(d.colUpper, P.col_upper, n0);
+  put(d.rowLower, P.row_lower, m);
+  put(d.rowUpper, P.row_upper, m);
   put(sessMat_.get(), P.a_value, nnzIn_);
   sessQDim_ = 0;
   if (qSlots > 0) {
@@ -183,10 +183,7 @@ void Solver::sessionAdopt(const pdlp_problem_t& P) {
   if (!hostRec_) PDLP_HIP(hipHostMalloc((void**)&hostRec_, 2 * sizeof(int32_t)));
   // the staging buffers every later call fills, with the sizes the updates give them: what is held stays the same from
   // call to call
-  if (updIn_.size() == 0) {
-    updIn_.alloc((size_t)3 * n0 + (size_t)2 * m);
-    updBad_.alloc(1);
-  }
+  ensureDataStaging();
   if (updMat_.size() == 0) updMat_.alloc((size_t)nnzIn_);
   if (qSlots > 0 && updQ_.size() == 0) updQ_.alloc((size_t)qSlots);
   updPat_.alloc((size_t)n0 + 1 + (size_t)nnzIn_ + (qSlots > 0 ? (size_t)P.q_dim + 1 + (size_t)qSlots : 0));
@@ -203,19 +200,18 @@ void Solver::sessionStage(const pdlp_problem_t& P, int32_t* changed, int32_t* ki
   PDLP_HIP(hipStreamSynchronize(stream_));
   if (updIn_.size() == 0 || updMat_.size() == 0 || updPat_.size() != nPat || (qSlots > 0 && updQ_.size() == 0))
     throw std::runtime_error("pdlp_mi355x_session_solve: the staging buffers are missing");
-  double* in = updIn_.get();
-  const double* held = sessIn_.get();
+  const DataStage in = DataStage::over(updIn_.get(), n0, m), held = DataStage::over(sessIn_.get(), n0, m);
   int32_t* pat = updPat_.get();
   auto put = [&](void* dev, const void* host, size_t bytes) {
     if (bytes > 0) PDLP_HIP(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, stream_));
   };
   put(pat, P.a_start, sizeof(int32_t) * ((size_t)n0 + 1));
   put(pat + n0 + 1, P.a_index, sizeof(int32_t) * (size_t)nnz0);
-  put(in, P.col_cost, sizeof(double) * (size_t)n0);
-  put(in + n0, P.col_lower, sizeof(double) * (size_t)n0);
-  put(in + 2 * (size_t)n0, P.col_upper, sizeof(double) * (size_t)n0);
-  put(in + 3 * (size_t)n0, P.row_lower, sizeof(double) * (size_t)m);
-  put(in + 3 * (size_t)n0 + m, P.row_upper, sizeof(double) * (size_t)m);
+  put(in.cost, P.col_cost, sizeof(double) * (size_t)n0);
+  put(in.colLower, P.col_lower, sizeof(double) * (size_t)n0);
+  put(in.colUpper, P.col_upper, sizeof(double) * (size_t)n0);
+  put(in.rowLower, P.row_lower, sizeof(double) * (size_t)m);
+  put(in.rowUpper, P.row_upper, sizeof(double) * (size_t)m);
   put(updMat_.get(), P.a_value, sizeof(double) * (size_t)nnz0);
   DiffJobs J;
   auto job = [&](const void* a, const void* b, int64_t count, int32_t width, int32_t bit) {
@@ -226,11 +222,11 @@ void Solver::sessionStage(const pdlp_problem_t& P, int32_t* changed, int32_t* ki
   job(pat, mk_.aStart.get(), (int64_t)n0 + 1, 4, PDLP_CHANGED_PATTERN);
   job(pat + n0 + 1, mk_.aIndex.get(), nnz0, 4, PDLP_CHANGED_PATTERN);
   job(updMat_.get(), sessMat_.get(), nnz0, 8, PDLP_CHANGED_MATRIX_VALUES);
-  job(in, held, n0, 8, PDLP_CHANGED_COST);
-  job(in + n0, held + n0, n0, 8, PDLP_CHANGED_COL_LOWER);
-  job(in + 2 * (size_t)n0, held + 2 * (size_t)n0, n0, 8, PDLP_CHANGED_COL_UPPER);
-  job(in + 3 * (size_t)n0, held + 3 * (size_t)n0, m, 8, PDLP_CHANGED_ROW_BOUNDS);
-  job(in + 3 * (size_t)n0 + m, held + 3 * (size_t)n0 + m, m, 8, PDLP_CHANGED_ROW_BOUNDS);
+  job(in.cost, held.cost, n0, 8, PDLP_CHANGED_COST);
+  job(in.colLower, held.colLower, n0, 8, PDLP_CHANGED_COL_LOWER);
+  job(in.colUpper, held.colUpper, n0, 8, PDLP_CHANGED_COL_UPPER);
+  job(in.rowLower, held.rowLower, m, 8, PDLP_CHANGED_ROW_BOUNDS);
+  job(in.rowUpper, held.rowUpper, m, 8, PDLP_CHANGED_ROW_BOUNDS);
   if (qSlots > 0) {
     int32_t* qpat = pat + n0 + 1 + nnz0;
     put(qpat, P.q_start, sizeof(int32_t) * ((size_t)sessQDim_ + 1));
@@ -241,8 +237,8 @@ void Solver::sessionStage(const pdlp_problem_t& P, int32_t* changed, int32_t* ki
   }
   PDLP_HIP(hipStreamSynchronize(stream_));  // (only to tell the uploads' time from the comparison's)
   *uploadSeconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-  J.rowLower = in + 3 * (size_t)n0;
-  J.rowUpper = in + 3 * (size_t)n0 + m;
+  J.rowLower = in.rowLower;
+  J.rowUpper = in.rowUpper;
   J.rowKind = rowKindDev_.get();
   J.m = m;
   hostRec_[0] = 0;
@@ -264,12 +260,9 @@ void Solver::sessionCommit() {
 }
 
 size_t Solver::sessionHeldBytes() const {
-  return sizeof(double) * (csPass_.size() + rsPass_.size() + updIn_.size() + updMat_.size() + updQ_.size() + sessIn_.size() +
-                           sessMat_.size() + sessQ_.size()) +
-         sizeof(int32_t) * (rowKindDev_.size() + rowNewIdxDev_.size() + slackRowDev_.size() + updBad_.size() + srcAVal_.size() +
-                            srcASlab_.size() + srcAtVal_.size() + srcAtSlab_.size() + srcQVal_.size() + srcQSlab_.size() +
-                            sessQPat_.size() + updPat_.size() + sessRec_.size()) +
-         mk_.bytes() + hk_.bytes();
+  return dataKeptBytes() + matrixKeptBytes() + hessianKeptBytes() +  // ... and the session's own six buffers
+         sizeof(double) * (sessIn_.size() + sessMat_.size() + sessQ_.size()) +
+         sizeof(int32_t) * (sessQPat_.size() + updPat_.size() + sessRec_.size());
 }
 
 // ---- the session ------------------------------------------------------------------------------------------------------

@@ -2358,36 +2358,34 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     }
   } else if (name == "update_seconds") {  // the parts of the last pdlp_mi355x_update: upload + validation, replay kernels, norms +
     // sums, per-block bounds, graph capture, reset; [6] = the whole update (= setup_seconds of the run that follows)
-    for (int k = 0; k < 6; ++k) put(k, updSeconds_[k]);
-    put(6, setupSeconds_);
+    for (int k = 0; k < kUpdSlots; ++k) put(k, updSeconds_[k]);
+    put(kUpdSlots, setupSeconds_);
   } else if (name == "update_state") {  // [0] bytes of HBM an updatable solver keeps besides a plain one's (pass factors, row
     // bookkeeping, staging of the caller's arrays once an update has run), [1] pass count, [2] IterVecs::lowerUniform,
     // [3] 1 = a captured trial graph exists
-    put(0, (double)(sizeof(double) * (csPass_.size() + rsPass_.size() + updIn_.size()) +
-                    sizeof(int32_t) * (rowKindDev_.size() + rowNewIdxDev_.size() + slackRowDev_.size() + updBad_.size())));
+    put(0, (double)dataKeptBytes());
     put(1, (double)nPass_);
     put(2, (double)vecs_.lowerUniform);
     put(3, graphExec_ ? 1.0 : 0.0);
     // [4] bytes of HBM a matrix-updatable solver keeps on top of [0] (PDLP_UPDATABLE_MATRIX: the pattern of both orders, a
     // source index per value slot, the unscaled data, staging of a_value once a matrix update has run), [5] 1 = it is one
-    put(4, (double)(mk_.bytes() + sizeof(int32_t) * (srcAVal_.size() + srcASlab_.size() + srcAtVal_.size() + srcAtSlab_.size()) +
-                    sizeof(double) * updMat_.size()));
+    put(4, (double)matrixKeptBytes());
     put(5, matrixUpdatable_ ? 1.0 : 0.0);
     // [6] bytes of HBM a Hessian-updatable solver keeps on top of [0] and [4] (PDLP_UPDATABLE_HESSIAN: the assembly map,
     // row and column of every off-diagonal slot, the unscaled and the scaled off-diagonal values, a source index per
     // value slot of the N operand, staging of q_value once a Hessian update has run), [7] 1 = it is one
-    put(6, (double)(hk_.bytes() + sizeof(int32_t) * (srcQVal_.size() + srcQSlab_.size()) + sizeof(double) * updQ_.size()));
+    put(6, (double)hessianKeptBytes());
     put(7, hessianUpdatable_ ? 1.0 : 0.0);
   } else if (name == "update_values_seconds") {  // the Hessian's parts of the last pdlp_mi355x_update_values: upload +
     // validation, assembly, replay, refill of the N operand; [4] 1 = that update (or the last update of any kind) captured
     // the trial graph again; [5] = the whole update.  The data / matrix parts are in update_seconds / update_matrix_seconds
-    for (int k = 0; k < 4; ++k) put(k, updHessSeconds_[k]);
-    put(4, (double)updRecaptured_);
-    put(5, setupSeconds_);
+    for (int k = 0; k < kHessSlots; ++k) put(k, updHessSeconds_[k]);
+    put(kHessSlots, (double)updRecaptured_);
+    put(kHessSlots + 1, setupSeconds_);
   } else if (name == "update_matrix_seconds") {  // the parts of the last pdlp_mi355x_update_matrix: upload + validation, formulate,
     // scaling passes, refills, norms + sums, per-block bounds, graph capture, reset; [8] = the whole update
-    for (int k = 0; k < 8; ++k) put(k, updMatSeconds_[k]);
-    put(8, setupSeconds_);
+    for (int k = 0; k < kMatSlots; ++k) put(k, updMatSeconds_[k]);
+    put(kMatSlots, setupSeconds_);
   } else if (name == "trial_launches") {  // kernels per trial step of the hot loop (2 = fused decision + primal step)
     // mesh: 9 with single-block wait kernels, 7 with consumers that wait themselves, 5 with an exchange per launch
     // (fusedWait 0 / 1 / 2)

@@ -92,6 +92,7 @@ float tuneXcdMap(DeviceMatrix& M, const DevSwitches& sw, const double* in, doubl
 void buildSlabTuned(DeviceMatrix& out, DeviceCsrData& M, const DevSwitches& sw, hipStream_t s);
 
 class Comm;  // RCCL wrapper (pdlp_comm.cpp)
+struct DataStage;          // pdlp_update.hpp
 struct LaneUnit;           // pdlp_batch.hpp
 enum LaneVerdict : int;    // pdlp_batch.hpp
 
@@ -215,6 +216,22 @@ class Solver : public SolverBase {
   void applyHessian(bool assemble, bool replayDiag);
   void updateImpl(const pdlp_update_t& u, const double* qValue);
   void updateMatrixImpl(const double* aValue, int64_t numNz, const pdlp_update_t* u, const double* qValue);
+  // what the two share (pdlp_update.cpp): refusals, HEAD (ensureDataStaging, stageRowsAndValidate, ..., stageColumns), each
+  // one's own middle, TAIL (refreshScaledSums, refreshBoundsFlipsUniform, finishUpdate)
+  void ensureDataStaging();  // updIn_, updBad_ on first use
+  void stagePut(double* dev, const double* host, int64_t count);  // an upload, unless staged_
+  void stageRowsAndValidate(const pdlp_update_t& ud, int32_t mask, const DataStage& D);  // throws on a kind change
+  void stageColumns(const pdlp_update_t& ud, int32_t mask, const DataStage& D);
+  void replayData(int32_t mask, const DataStage& D, const double* csPass, const double* rsPass, int32_t nPass, double* cost,
+                  double* lower, double* upper, double* rhs);
+  void refreshScaledSums(bool cost, bool rhs);  // sumCost2_ / sumRhs2_ from a download of cost_ / rhs_; one synchronisation
+  bool refreshBoundsFlipsUniform();             // refreshBlockBounds(); true: IterVecs::lowerUniform flipped
+  void finishUpdate(const pdlp_update_t& ud, bool recapture, double* resetSeconds, double* captureSeconds,
+                    std::chrono::steady_clock::time_point t0);
+  // stage "update_state" [0], [4], [6]: HBM kept for data / matrix / Hessian updates (sessionHeldBytes adds the session's own)
+  size_t dataKeptBytes() const;
+  size_t matrixKeptBytes() const;
+  size_t hessianKeptBytes() const;
   bool refreshBlockBounds();              // fused slab trial: colBlockUni_ / colBlockBounds_ from lower_ / upper_; returns allLower
   // hot loop
   void enqueueTrial();
@@ -341,7 +358,8 @@ class Solver : public SolverBase {
   MatrixKeep mk_;
   DeviceArray<int32_t> srcAVal_, srcASlab_, srcAtVal_, srcAtSlab_;
   DeviceArray<double> updMat_;
-  double updMatSeconds_[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // upload + validation, formulate, scaling passes, refills, norms + sums, block bounds, graph capture, reset
+  enum { kMatStage, kMatFormulate, kMatPasses, kMatRefills, kMatSums, kMatBounds, kMatCapture, kMatReset, kMatSlots };
+  double updMatSeconds_[kMatSlots] = {};  // upload + validation, formulate, scaling passes, refills, norms + sums, block bounds, graph capture, reset
   // Hessian-updatable solvers (PDLP_UPDATABLE_HESSIAN): the assembly map from the caller's q_value slots (HessianMap), row
   // and column of every qoff slot, the unscaled Hessian (the diagonal lives in mk_.qdiag0 when the solver is matrix-
   // updatable as well), the scaled off-diagonal values dQ_ is refilled from, and per value array of dQ_'s layouts the qoff
@@ -359,7 +377,8 @@ class Solver : public SolverBase {
   double* qdiag0Dev() { return matrixUpdatable_ ? mk_.qdiag0.get() : hk_.qdiag0.get(); }
   DeviceArray<int32_t> srcQVal_, srcQSlab_;
   DeviceArray<double> updQ_;
-  double updHessSeconds_[4] = {0, 0, 0, 0};  // upload + validation, assembly, replay, refill of dQ_ (stage "update_values_seconds")
+  enum { kHessStage, kHessAssemble, kHessReplay, kHessRefill, kHessSlots };
+  double updHessSeconds_[kHessSlots] = {};  // upload + validation, assembly, replay, refill of dQ_ (stage "update_values_seconds")
   int32_t updRecaptured_ = 0;                // 1 = the last update captured the trial graph again
   // Session-held solvers (pdlp_session.hpp): the caller's arrays of the last call (sessIn_ laid out as updIn_, sessMat_ as
   // updMat_, sessQ_ as updQ_, sessQPat_ = q_start then q_index), staging of the pattern (a_start, a_index, q_start,
@@ -369,7 +388,8 @@ class Solver : public SolverBase {
   DeviceArray<int32_t> sessQPat_, updPat_, sessRec_;
   int32_t* hostRec_ = nullptr;
   int32_t sessQDim_ = 0;
-  double updSeconds_[6] = {0, 0, 0, 0, 0, 0};  // upload + validation, kernels, norms + sums, block bounds, graph capture, reset
+  enum { kUpdStage, kUpdKernels, kUpdSums, kUpdBounds, kUpdCapture, kUpdReset, kUpdSlots };
+  double updSeconds_[kUpdSlots] = {};  // upload + validation, kernels, norms + sums, block bounds, graph capture, reset
   int32_t barrierFallbacks_ = 0, smallLaunches_ = 0;
   unsigned long long smallSeq_ = 0;  // persistent launches since gridBar_ was zeroed (their roll call counts cumulatively)
   // (barrier rounds of the contexts of one device: ordered on the DEVICE by an event chain, see pdlp_solver.cpp)

@@ -22,7 +22,23 @@ const char* kindName(int32_t k) {
     default: return "unknown";
   }
 }
+[[noreturn]] void refuse(const char* entry, const char* sentence) { throw std::runtime_error(std::string(entry) + ": " + sentence); }
 }  // namespace
+
+void refuseHipdlp(const char* entry) { refuse(entry, "HiPDLP solvers (algorithm = 1) do not take updates"); }
+void refuseSharded(const char* entry) { refuse(entry, "sharded solvers (pdlp_mi355x_create_sharded) do not take updates"); }
+void refuseNotUpdatable(const char* entry) { refuse(entry, "the solver was not created for updates (pdlp_params_t.updatable = 0)"); }
+void refuseNoMatrixBit(const char* entry) {
+  const std::string given = entry == std::string(kEntryUpdateValues) ? "a_value given, but " : "";
+  refuse(entry, (given + "the solver was not created for matrix updates (pdlp_params_t.updatable lacks PDLP_UPDATABLE_MATRIX)").c_str());
+}
+void refuseNoHessianBit(const char* entry) {
+  refuse(entry, "the solver was not created for Hessian updates (pdlp_params_t.updatable lacks PDLP_UPDATABLE_HESSIAN)");
+}
+void refuseOffDiagonalHessian(const char* entry) {
+  refuse(entry, "QPs whose Hessian has off-diagonal entries do not take matrix updates (the scaled copy of the Hessian follows "
+                "the column factors; left for a later change)");
+}
 
 void checkUpdateShape(const pdlp_update_t& u) {
   if ((u.row_lower != nullptr) != (u.row_upper != nullptr))
@@ -34,15 +50,15 @@ void checkUpdateShape(const pdlp_update_t& u) {
                              "all three (hot start) or none (cold start), " + std::to_string(given) + " of 3 are given");
 }
 
-int32_t firstKindChange(const int32_t* rowKind, int32_t m, const double* rowLower, const double* rowUpper) {
+void refuseKindChange(const int32_t* rowKind, int32_t m, const double* rowLower, const double* rowUpper) {
   for (int32_t i = 0; i < m; ++i)
-    if (rowKindOf(rowLower[i], rowUpper[i]) != rowKind[i]) return i;
-  return m;
+    if (rowKindOf(rowLower[i], rowUpper[i]) != rowKind[i]) refuseKindChangeAt(rowKind, i, rowLower, rowUpper);
 }
 
-void throwKindChange(int32_t row, int32_t was, int32_t now) {
-  throw std::runtime_error("pdlp_mi355x_update: row " + std::to_string(row) + " would change its kind from " + kindName(was) +
-                           " to " + kindName(now) + " (the kind decides row order, slack columns and signs: create a new solver)");
+void refuseKindChangeAt(const int32_t* rowKind, int32_t row, const double* rowLower, const double* rowUpper) {
+  throw std::runtime_error("pdlp_mi355x_update: row " + std::to_string(row) + " would change its kind from " + kindName(rowKind[row]) +
+                           " to " + kindName(rowKindOf(rowLower[row], rowUpper[row])) +
+                           " (the kind decides row order, slack columns and signs: create a new solver)");
 }
 
 void hostReplayUpdate(const pdlp_update_t& u, StandardForm& F) {
@@ -50,10 +66,7 @@ void hostReplayUpdate(const pdlp_update_t& u, StandardForm& F) {
   if (!F.keepPasses) throw std::runtime_error("pdlp_mi355x_update: the form did not keep its scaling passes");
   const int32_t n0 = F.n0, n = F.n, m = F.m;
   const int32_t mask = updateMask(u);
-  if (mask & kUpdRows) {
-    const int32_t bad = firstKindChange(F.rowKind.data(), m, u.row_lower, u.row_upper);
-    if (bad < m) throwKindChange(bad, F.rowKind[bad], rowKindOf(u.row_lower[bad], u.row_upper[bad]));
-  }
+  if (mask & kUpdRows) refuseKindChange(F.rowKind.data(), m, u.row_lower, u.row_upper);
   const double kInf = std::numeric_limits<double>::infinity();
   auto infLo = [&](double v) { return v < -1e20 ? -kInf : v; };
   auto infUp = [&](double v) { return v > 1e20 ? kInf : v; };
@@ -181,10 +194,7 @@ void hostReplayMatrixUpdate(const pdlp_problem_t& P, const double* aValue, const
     throw std::runtime_error("pdlp_mi355x_update_matrix: the form did not keep its unscaled data");
   if (u) {
     checkUpdateShape(*u);
-    if (updateMask(*u) & kUpdRows) {
-      const int32_t bad = firstKindChange(F.rowKind.data(), F.m, u->row_lower, u->row_upper);
-      if (bad < F.m) throwKindChange(bad, F.rowKind[bad], rowKindOf(u->row_lower[bad], u->row_upper[bad]));
-    }
+    if (updateMask(*u) & kUpdRows) refuseKindChange(F.rowKind.data(), F.m, u->row_lower, u->row_upper);
   }
   bool anyNonzero = false;
   for (int64_t p = 0; p < nnz0 && !anyNonzero; ++p) anyNonzero = aValue[p] != 0.0;
@@ -205,135 +215,108 @@ void hostReplayMatrixUpdate(const pdlp_problem_t& P, const double* aValue, const
   if (doScale) scale(F);           // the set-up's own passes; keeps the NEW factors for later updates
 }
 
-void SolverBase::update(const pdlp_update_t&) {
-  throw std::runtime_error("pdlp_mi355x_update: HiPDLP solvers (algorithm = 1) do not take updates");
-}
-
-void SolverBase::updateMatrix(const double*, int64_t, const pdlp_update_t*) {
-  throw std::runtime_error("pdlp_mi355x_update_matrix: HiPDLP solvers (algorithm = 1) do not take updates");
-}
-
-void SolverBase::updateValues(const double*, int64_t, const double*, int64_t, const pdlp_update_t*) {
-  throw std::runtime_error("pdlp_mi355x_update_values: HiPDLP solvers (algorithm = 1) do not take updates");
-}
+void SolverBase::update(const pdlp_update_t&) { refuseHipdlp(kEntryUpdate); }
+void SolverBase::updateMatrix(const double*, int64_t, const pdlp_update_t*) { refuseHipdlp(kEntryUpdateMatrix); }
+void SolverBase::updateValues(const double*, int64_t, const double*, int64_t, const pdlp_update_t*) { refuseHipdlp(kEntryUpdateValues); }
 
 void SolverBase::setRuntimeOptions(const pdlp_params_t&) {
   throw std::runtime_error("pdlp_mi355x: HiPDLP solvers (algorithm = 1) are not held across solves: no new options");
 }
 
-// The held solver is brought to the state of a fresh create() on the modified problem.  Everything that can be refused
-// is refused before the first write to the solver's vectors: the caller's row bounds go to a staging buffer, the
-// validation kernel reads only that and the kept kinds.
-void Solver::update(const pdlp_update_t& u) { updateImpl(u, nullptr); }
+namespace {
+using clock = std::chrono::steady_clock;
+double since(clock::time_point a) { return std::chrono::duration<double>(clock::now() - a).count(); }
+}  // namespace
 
-// qValue (or nullptr): new Hessian values as well (pdlp_mi355x_update_values without a_value; the count is checked there)
-void Solver::updateImpl(const pdlp_update_t& u, const double* qValue) {
-  using clock = std::chrono::steady_clock;
-  const auto t0 = clock::now();
-  auto since = [](clock::time_point a) { return std::chrono::duration<double>(clock::now() - a).count(); };
-  if (sharded_)
-    throw std::runtime_error("pdlp_mi355x_update: sharded solvers (pdlp_mi355x_create_sharded) do not take updates");
-  if (!updatable_)
-    throw std::runtime_error("pdlp_mi355x_update: the solver was not created for updates (pdlp_params_t.updatable = 0)");
-  checkUpdateShape(u);
-  const int32_t n0 = F_.n0, n = F_.n, m = F_.m;
-  const int32_t mask = updateMask(u);
-  PDLP_HIP(hipSetDevice(opt_.device));
-  PDLP_HIP(hipStreamSynchronize(stream_));
-  if (updIn_.size() == 0) {
-    updIn_.alloc((size_t)3 * n0 + (size_t)2 * m);
-    updBad_.alloc(1);
-  }
-  double* dCost = updIn_.get();
-  double* dColLo = dCost + n0;
-  double* dColUp = dColLo + n0;
-  double* dRowLo = dColUp + n0;
-  double* dRowUp = dRowLo + m;
-  auto put = [&](double* dev, const double* host, int32_t count) {  // (a session has staged them already)
-    if (count > 0 && !staged_) PDLP_HIP(hipMemcpyAsync(dev, host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, stream_));
-  };
-  if (mask & kUpdRows) {
-    put(dRowLo, u.row_lower, m);
-    put(dRowUp, u.row_upper, m);
-    int32_t bad = m;
-    PDLP_HIP(hipMemcpyAsync(updBad_.get(), &bad, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-    launchUpdateValidate(dRowLo, dRowUp, rowKindDev_.get(), m, updBad_.get(), stream_);
-    PDLP_HIP(hipMemcpyAsync(&bad, updBad_.get(), sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-    PDLP_HIP(hipStreamSynchronize(stream_));
-    if (bad < m) throwKindChange(bad, F_.rowKind[bad], rowKindOf(u.row_lower[bad], u.row_upper[bad]));
-  }
-  if (qValue) stageHessian(qValue);
-  // ---- nothing below is refused ----
-  if (mask & kUpdCost) put(dCost, u.col_cost, n0);
-  if (mask & kUpdColLower) put(dColLo, u.col_lower, n0);
-  if (mask & kUpdColUpper) put(dColUp, u.col_upper, n0);
-  PDLP_HIP(hipStreamSynchronize(stream_));
-  updSeconds_[0] = since(t0);
+// ---- what the update entries share: the staging head, the scaled sums, the finishing tail --------------------------------
+size_t Solver::dataKeptBytes() const {
+  return sizeof(double) * (csPass_.size() + rsPass_.size() + updIn_.size()) +
+         sizeof(int32_t) * (rowKindDev_.size() + rowNewIdxDev_.size() + slackRowDev_.size() + updBad_.size());
+}
+size_t Solver::matrixKeptBytes() const {
+  return mk_.bytes() + sizeof(int32_t) * (srcAVal_.size() + srcASlab_.size() + srcAtVal_.size() + srcAtSlab_.size()) +
+         sizeof(double) * updMat_.size();
+}
+size_t Solver::hessianKeptBytes() const {
+  return hk_.bytes() + sizeof(int32_t) * (srcQVal_.size() + srcQSlab_.size()) + sizeof(double) * updQ_.size();
+}
 
-  auto t1 = clock::now();
-  launchUpdateCols(mask, dCost, dColLo, dColUp, dRowLo, dRowUp, slackRowDev_.get(), F_.sense, n0, n, csPass_.get(), nPass_,
-                   cost_.get(), lower_.get(), upper_.get(), stream_);
+void Solver::ensureDataStaging() {
+  if (updIn_.size() != 0) return;
+  updIn_.alloc(DataStage::count(F_.n0, F_.m));
+  updBad_.alloc(1);
+}
+
+void Solver::stagePut(double* dev, const double* host, int64_t count) {  // (a session has staged them already)
+  if (count > 0 && !staged_) PDLP_HIP(hipMemcpyAsync(dev, host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, stream_));
+}
+
+// The head: the caller's row bounds into the staging buffer, the validation kernel on that and the kept kinds.  Nothing
+// of the solver is written.
+void Solver::stageRowsAndValidate(const pdlp_update_t& ud, int32_t mask, const DataStage& D) {
+  if (!(mask & kUpdRows)) return;
+  const int32_t m = F_.m;
+  stagePut(D.rowLower, ud.row_lower, m);
+  stagePut(D.rowUpper, ud.row_upper, m);
+  int32_t bad = m;
+  PDLP_HIP(hipMemcpyAsync(updBad_.get(), &bad, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
+  launchUpdateValidate(D.rowLower, D.rowUpper, rowKindDev_.get(), m, updBad_.get(), stream_);
+  PDLP_HIP(hipMemcpyAsync(&bad, updBad_.get(), sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  if (bad < m) refuseKindChangeAt(F_.rowKind.data(), bad, ud.row_lower, ud.row_upper);
+}
+
+void Solver::stageColumns(const pdlp_update_t& ud, int32_t mask, const DataStage& D) {
+  if (mask & kUpdCost) stagePut(D.cost, ud.col_cost, F_.n0);
+  if (mask & kUpdColLower) stagePut(D.colLower, ud.col_lower, F_.n0);
+  if (mask & kUpdColUpper) stagePut(D.colUpper, ud.col_upper, F_.n0);
+}
+
+// The staged data into cost / lower / upper / rhs through the nPass passes (nullptr, 0: the unscaled copies)
+void Solver::replayData(int32_t mask, const DataStage& D, const double* csPass, const double* rsPass, int32_t nPass, double* cost,
+                        double* lower, double* upper, double* rhs) {
+  launchUpdateCols(mask, D.cost, D.colLower, D.colUpper, D.rowLower, D.rowUpper, slackRowDev_.get(), F_.sense, F_.n0, F_.n, csPass,
+                   nPass, cost, lower, upper, stream_);
   if (mask & kUpdRows)
-    launchUpdateRows(dRowLo, dRowUp, rowKindDev_.get(), rowNewIdxDev_.get(), m, rsPass_.get(), nPass_, rhs_.get(), stream_);
-  if (matrixUpdatable_) {  // the unscaled data follow every update: the same kernels with no pass to replay
-    launchUpdateCols(mask, dCost, dColLo, dColUp, dRowLo, dRowUp, slackRowDev_.get(), F_.sense, n0, n, nullptr, 0, mk_.cost0.get(),
-                     mk_.lower0.get(), mk_.upper0.get(), stream_);
-    if (mask & kUpdRows)
-      launchUpdateRows(dRowLo, dRowUp, rowKindDev_.get(), rowNewIdxDev_.get(), m, nullptr, 0, mk_.rhs0.get(), stream_);
-  }
+    launchUpdateRows(D.rowLower, D.rowUpper, rowKindDev_.get(), rowNewIdxDev_.get(), F_.m, rsPass, nPass, rhs, stream_);
+}
+
+// The left-to-right sums of the scaled c, b (PDHG_Init_Step_Sizes), by the host loops of the set-up
+void Solver::refreshScaledSums(bool cost, bool rhs) {
+  std::vector<double> hc(cost ? (size_t)F_.n : 0), hb(rhs ? (size_t)F_.m : 0);
+  cost_.download(hc.data(), hc.size(), stream_);
+  rhs_.download(hb.data(), hb.size(), stream_);
   PDLP_HIP(hipStreamSynchronize(stream_));
-  updSeconds_[1] = since(t1);
-  // the Hessian: assembled from the staging copy, taken through the kept passes (the matrix, so every factor, stays)
-  if (qValue) applyHessian(true, true);
+  if (cost) sumCost2_ = 0.0;
+  for (double v : hc) sumCost2_ += v * v;
+  if (rhs) sumRhs2_ = 0.0;
+  for (double v : hb) sumRhs2_ += v * v;
+}
 
-  // termination norms of the unscaled data and the left-to-right sums of the scaled c, b (PDHG_Init_Step_Sizes), by the
-  // host loops of the set-up
-  t1 = clock::now();
-  if (mask & kUpdCost) {
-    F_.normCost = unscaledNormCost(u.col_cost, n0, F_.sense);
-    std::vector<double> hc((size_t)n);
-    cost_.download(hc.data(), (size_t)n, stream_);
-    PDLP_HIP(hipStreamSynchronize(stream_));
-    sumCost2_ = 0.0;
-    for (double v : hc) sumCost2_ += v * v;
-  }
-  if (mask & kUpdRows) {
-    F_.normRhs = unscaledNormRhs(u.row_lower, u.row_upper, F_.rowKind.data(), m);
-    std::vector<double> hb((size_t)m);
-    rhs_.download(hb.data(), (size_t)m, stream_);
-    PDLP_HIP(hipStreamSynchronize(stream_));
-    sumRhs2_ = 0.0;
-    for (double v : hb) sumRhs2_ += v * v;
-  }
-  if (u.has_offset) F_.offset = u.offset;
-  updSeconds_[2] = since(t1);
+// The fused slab trial's per-block bounds; the captured batch bakes IterVecs::lowerUniform in (the vectors' addresses have
+// not changed), so only a flip of that flag needs a new graph
+bool Solver::refreshBoundsFlipsUniform() {
+  const int32_t before = vecs_.lowerUniform;
+  const int32_t after = refreshBlockBounds() ? 1 : 0;
+  return before != after;
+}
 
-  // the fused slab trial's per-block bounds; the captured batch bakes IterVecs::lowerUniform in (the vectors' addresses
-  // have not changed), so only a flip of that flag needs a new graph
-  t1 = clock::now();
-  bool recapture = false;
-  if (fused_ && (mask & (kUpdColLower | kUpdColUpper | kUpdRows))) {
-    const int32_t before = vecs_.lowerUniform;
-    const int32_t after = refreshBlockBounds() ? 1 : 0;
-    recapture = before != after;
-  }
-  updSeconds_[3] = since(t1);
-
-  // start of the next run
-  if (u.start_col_value) {
-    setHotStart(u.start_col_value, u.start_row_value, u.start_row_dual);
+// The tail: the start of the next run, reset, a new graph where `recapture` asks for one
+void Solver::finishUpdate(const pdlp_update_t& ud, bool recapture, double* resetSeconds, double* captureSeconds,
+                          std::chrono::steady_clock::time_point t0) {
+  if (ud.start_col_value) {
+    setHotStart(ud.start_col_value, ud.start_row_value, ud.start_row_dual);  // (with the scale vectors as they are now)
   } else {
     hasStart_ = false;
     startX_.clear();
     startY_.clear();
   }
-
-  t1 = clock::now();
+  auto t1 = clock::now();
   stPar_ = graphExec_ && !recapture ? graphPar_ : 0;  // the state slot a fresh solver starts from / the kept graph was captured with
   reset();
   stalledRounds_ = 0;
   stalledSince_ = 0;
-  updSeconds_[5] = since(t1);
+  *resetSeconds = since(t1);
   t1 = clock::now();
   if (recapture && graphExec_) {
     (void)hipGraphExecDestroy(graphExec_);
@@ -341,26 +324,71 @@ void Solver::updateImpl(const pdlp_update_t& u, const double* qValue) {
     captureGraph();
   }
   PDLP_HIP(hipStreamSynchronize(stream_));
-  updSeconds_[4] = since(t1);
+  *captureSeconds = since(t1);
   updRecaptured_ = recapture && graphExec_ ? 1 : 0;
   setupSeconds_ = since(t0);
+}
+
+// The held solver is brought to the state of a fresh create() on the modified problem.  Everything that can be refused
+// is refused before the first write to the solver's vectors.
+void Solver::update(const pdlp_update_t& u) { updateImpl(u, nullptr); }
+
+// qValue (or nullptr): new Hessian values as well (pdlp_mi355x_update_values without a_value; the count is checked there)
+void Solver::updateImpl(const pdlp_update_t& u, const double* qValue) {
+  const auto t0 = clock::now();
+  if (sharded_) refuseSharded(kEntryUpdate);
+  if (!updatable_) refuseNotUpdatable(kEntryUpdate);
+  checkUpdateShape(u);
+  const int32_t mask = updateMask(u);
+  PDLP_HIP(hipSetDevice(opt_.device));
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  ensureDataStaging();
+  const DataStage D = DataStage::over(updIn_.get(), F_.n0, F_.m);
+  stageRowsAndValidate(u, mask, D);
+  if (qValue) stageHessian(qValue);
+  // ---- nothing below is refused ----
+  stageColumns(u, mask, D);
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  updSeconds_[kUpdStage] = since(t0);
+
+  auto t1 = clock::now();
+  replayData(mask, D, csPass_.get(), rsPass_.get(), nPass_, cost_.get(), lower_.get(), upper_.get(), rhs_.get());
+  if (matrixUpdatable_)  // the unscaled data follow every update: the same kernels with no pass to replay
+    replayData(mask, D, nullptr, nullptr, 0, mk_.cost0.get(), mk_.lower0.get(), mk_.upper0.get(), mk_.rhs0.get());
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  updSeconds_[kUpdKernels] = since(t1);
+  // the Hessian: assembled from the staging copy, taken through the kept passes (the matrix, so every factor, stays)
+  if (qValue) applyHessian(true, true);
+
+  // termination norms of the unscaled data and the sums of the scaled c, b
+  t1 = clock::now();
+  if (mask & kUpdCost) {
+    F_.normCost = unscaledNormCost(u.col_cost, F_.n0, F_.sense);
+    refreshScaledSums(true, false);
+  }
+  if (mask & kUpdRows) {
+    F_.normRhs = unscaledNormRhs(u.row_lower, u.row_upper, F_.rowKind.data(), F_.m);
+    refreshScaledSums(false, true);
+  }
+  if (u.has_offset) F_.offset = u.offset;
+  updSeconds_[kUpdSums] = since(t1);
+
+  t1 = clock::now();
+  const bool recapture = fused_ && (mask & (kUpdColLower | kUpdColUpper | kUpdRows)) && refreshBoundsFlipsUniform();
+  updSeconds_[kUpdBounds] = since(t1);
+  finishUpdate(u, recapture, &updSeconds_[kUpdReset], &updSeconds_[kUpdCapture], t0);
 }
 
 // pdlp_mi355x_update_values: a_value, q_value and u, each optional, as ONE change.  The refusals that depend on how the
 // solver was created come first; the rest is the data update or the matrix update with the Hessian's part in it.
 void Solver::updateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t* u) {
-  if (sharded_)
-    throw std::runtime_error("pdlp_mi355x_update_values: sharded solvers (pdlp_mi355x_create_sharded) do not take updates");
-  if (!(opt_.updatable & PDLP_UPDATABLE_HESSIAN))
-    throw std::runtime_error("pdlp_mi355x_update_values: the solver was not created for Hessian updates (pdlp_params_t.updatable "
-                             "lacks PDLP_UPDATABLE_HESSIAN)");
+  if (sharded_) refuseSharded(kEntryUpdateValues);
+  if (!(opt_.updatable & PDLP_UPDATABLE_HESSIAN)) refuseNoHessianBit(kEntryUpdateValues);
   if (!aValue && numNz != 0)
     throw std::runtime_error("pdlp_mi355x_update_values: a_value is NULL but num_nz = " + std::to_string(numNz));
-  if (aValue && !(opt_.updatable & PDLP_UPDATABLE_MATRIX))
-    throw std::runtime_error("pdlp_mi355x_update_values: a_value given, but the solver was not created for matrix updates "
-                             "(pdlp_params_t.updatable lacks PDLP_UPDATABLE_MATRIX)");
+  if (aValue && !(opt_.updatable & PDLP_UPDATABLE_MATRIX)) refuseNoMatrixBit(kEntryUpdateValues);
   checkHessianUpdateShape(qValue, numQNz, hk_.nSlots > 0, hk_.nSlots);
-  updHessSeconds_[0] = updHessSeconds_[1] = updHessSeconds_[2] = updHessSeconds_[3] = 0.0;
+  for (double& s : updHessSeconds_) s = 0.0;
   if (aValue) {
     updateMatrixImpl(aValue, numNz, u, qValue);
   } else {
@@ -371,18 +399,16 @@ void Solver::updateValues(const double* aValue, int64_t numNz, const double* qVa
 
 // The caller's q_value into its staging buffer and the validation kernel on it: nothing of the solver is written.
 void Solver::stageHessian(const double* qValue) {
-  using clock = std::chrono::steady_clock;
   const auto t0 = clock::now();
   const int32_t n = F_.n;
   if (updQ_.size() == 0) updQ_.alloc((size_t)hk_.nSlots);
-  if (updBad_.size() == 0) updBad_.alloc(1);
-  if (!staged_) PDLP_HIP(hipMemcpyAsync(updQ_.get(), qValue, sizeof(double) * (size_t)hk_.nSlots, hipMemcpyHostToDevice, stream_));
-  int32_t bad = n;
+  stagePut(updQ_.get(), qValue, hk_.nSlots);
+  int32_t bad = n;  // (updBad_: ensureDataStaging, which every caller has been through)
   PDLP_HIP(hipMemcpyAsync(updBad_.get(), &bad, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
   launchHessianValidate(hk_.dstBeg.get(), hk_.srcSlot.get(), updQ_.get(), F_.sense, n, updBad_.get(), stream_);
   PDLP_HIP(hipMemcpyAsync(&bad, updBad_.get(), sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
   PDLP_HIP(hipStreamSynchronize(stream_));
-  updHessSeconds_[0] = std::chrono::duration<double>(clock::now() - t0).count();
+  updHessSeconds_[kHessStage] = since(t0);
   if (bad < n) throwNegativeDiagonal(bad);
 }
 
@@ -390,15 +416,13 @@ void Solver::stageHessian(const double* qValue) {
 // update leaves the diagonal to its scaling passes instead).  Always: the off-diagonal part through csPass_ as it stands,
 // and dQ_'s value arrays refilled from it.
 void Solver::applyHessian(bool assemble, bool replayDiag) {
-  using clock = std::chrono::steady_clock;
-  auto since = [](clock::time_point a) { return std::chrono::duration<double>(clock::now() - a).count(); };
   const int32_t n = F_.n, nOff = hk_.nOff;
   double* qdiag0 = qdiag0Dev();
   auto t1 = clock::now();
   if (assemble) {
     launchHessianAssemble(hk_.dstBeg.get(), hk_.srcSlot.get(), updQ_.get(), F_.sense, n, nOff, qdiag0, hk_.qoff0.get(), stream_);
     PDLP_HIP(hipStreamSynchronize(stream_));
-    updHessSeconds_[1] = since(t1);
+    updHessSeconds_[kHessAssemble] = since(t1);
   }
   t1 = clock::now();
   const double* diagSrc = replayDiag ? qdiag0 : nullptr;
@@ -411,11 +435,11 @@ void Solver::applyHessian(bool assemble, bool replayDiag) {
     if (offSrc) PDLP_HIP(hipMemcpyAsync(hk_.qoffScaled.get(), offSrc, sizeof(double) * (size_t)nOff, hipMemcpyDeviceToDevice, stream_));
   }
   PDLP_HIP(hipStreamSynchronize(stream_));
-  updHessSeconds_[2] = since(t1);
+  updHessSeconds_[kHessReplay] = since(t1);
   t1 = clock::now();
   if (nOff > 0) refillHessian();
   PDLP_HIP(hipStreamSynchronize(stream_));
-  updHessSeconds_[3] = since(t1);
+  updHessSeconds_[kHessRefill] = since(t1);
 }
 
 // pdlp_mi355x_update_matrix: new matrix values on the kept pattern, optionally with new data (u), as ONE change.  Of
@@ -430,17 +454,10 @@ void Solver::updateMatrix(const double* aValue, int64_t numNz, const pdlp_update
 }
 
 void Solver::updateMatrixImpl(const double* aValue, int64_t numNz, const pdlp_update_t* u, const double* qValue) {
-  using clock = std::chrono::steady_clock;
   const auto t0 = clock::now();
-  auto since = [](clock::time_point a) { return std::chrono::duration<double>(clock::now() - a).count(); };
-  if (sharded_)
-    throw std::runtime_error("pdlp_mi355x_update_matrix: sharded solvers (pdlp_mi355x_create_sharded) do not take updates");
-  if (!(opt_.updatable & PDLP_UPDATABLE_MATRIX))
-    throw std::runtime_error("pdlp_mi355x_update_matrix: the solver was not created for matrix updates (pdlp_params_t.updatable "
-                             "lacks PDLP_UPDATABLE_MATRIX)");
-  if (hasQoff_ && !hessianUpdatable_)
-    throw std::runtime_error("pdlp_mi355x_update_matrix: QPs whose Hessian has off-diagonal entries do not take matrix updates "
-                             "(the scaled copy of the Hessian follows the column factors; left for a later change)");
+  if (sharded_) refuseSharded(kEntryUpdateMatrix);
+  if (!(opt_.updatable & PDLP_UPDATABLE_MATRIX)) refuseNoMatrixBit(kEntryUpdateMatrix);
+  if (hasQoff_ && !hessianUpdatable_) refuseOffDiagonalHessian(kEntryUpdateMatrix);
   if (!matrixUpdatable_) throw std::runtime_error("pdlp_mi355x_update_matrix: the solver kept nothing for matrix updates");
   checkMatrixUpdateShape(aValue, numNz, nnzIn_);
   static const pdlp_update_t kNoData{};
@@ -451,38 +468,17 @@ void Solver::updateMatrixImpl(const double* aValue, int64_t numNz, const pdlp_up
   const int32_t mask = updateMask(ud);
   PDLP_HIP(hipSetDevice(opt_.device));
   PDLP_HIP(hipStreamSynchronize(stream_));
-  if (updIn_.size() == 0) {
-    updIn_.alloc((size_t)3 * n0 + (size_t)2 * m);
-    updBad_.alloc(1);
-  }
+  ensureDataStaging();
   if (updMat_.size() == 0) updMat_.alloc((size_t)nnz0);
-  double* dCost = updIn_.get();
-  double* dColLo = dCost + n0;
-  double* dColUp = dColLo + n0;
-  double* dRowLo = dColUp + n0;
-  double* dRowUp = dRowLo + m;
-  auto put = [&](double* dev, const double* host, int64_t count) {  // (a session has staged them already)
-    if (count > 0 && !staged_) PDLP_HIP(hipMemcpyAsync(dev, host, sizeof(double) * (size_t)count, hipMemcpyHostToDevice, stream_));
-  };
-  put(updMat_.get(), aValue, nnz0);
-  if (mask & kUpdRows) {
-    put(dRowLo, ud.row_lower, m);
-    put(dRowUp, ud.row_upper, m);
-    int32_t bad = m;
-    PDLP_HIP(hipMemcpyAsync(updBad_.get(), &bad, sizeof(int32_t), hipMemcpyHostToDevice, stream_));
-    launchUpdateValidate(dRowLo, dRowUp, rowKindDev_.get(), m, updBad_.get(), stream_);
-    PDLP_HIP(hipMemcpyAsync(&bad, updBad_.get(), sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-    PDLP_HIP(hipStreamSynchronize(stream_));
-    if (bad < m) throwKindChange(bad, F_.rowKind[bad], rowKindOf(ud.row_lower[bad], ud.row_upper[bad]));
-  }
+  const DataStage D = DataStage::over(updIn_.get(), n0, m);
+  stagePut(updMat_.get(), aValue, nnz0);
+  stageRowsAndValidate(ud, mask, D);
   if (gpuAbsMax(updMat_.get(), nnz0, stream_) == 0.0) throwAllZeroMatrix();  // (a NaN among the values is not zero, as for create)
   if (qValue) stageHessian(qValue);
   // ---- nothing below is refused ----
-  if (mask & kUpdCost) put(dCost, ud.col_cost, n0);
-  if (mask & kUpdColLower) put(dColLo, ud.col_lower, n0);
-  if (mask & kUpdColUpper) put(dColUp, ud.col_upper, n0);
+  stageColumns(ud, mask, D);
   PDLP_HIP(hipStreamSynchronize(stream_));
-  updMatSeconds_[0] = since(t0);
+  updMatSeconds_[kMatStage] = since(t0);
 
   // formulated values in reference order, their row-major copy through the kept permutation; the unscaled data overlaid
   // with what u gives (the replay kernels with no pass), copied into the solver's vectors
@@ -493,10 +489,7 @@ void Solver::updateMatrixImpl(const double* aValue, int64_t numNz, const pdlp_up
   gpuFormulateValues(K.aStart.get(), K.aIndex.get(), updMat_.get(), rowKindDev_.get(), rowNewIdxDev_.get(), n0, m, nnz0, nnz - nnz0,
                      K.cscVal.get(), stream_);
   launchRefill(K.permA.get(), K.cscVal.get(), nnz, nnz, K.aVal.get(), stream_);
-  launchUpdateCols(mask, dCost, dColLo, dColUp, dRowLo, dRowUp, slackRowDev_.get(), F_.sense, n0, n, nullptr, 0, K.cost0.get(),
-                   K.lower0.get(), K.upper0.get(), stream_);
-  if (mask & kUpdRows)
-    launchUpdateRows(dRowLo, dRowUp, rowKindDev_.get(), rowNewIdxDev_.get(), m, nullptr, 0, K.rhs0.get(), stream_);
+  replayData(mask, D, nullptr, nullptr, 0, K.cost0.get(), K.lower0.get(), K.upper0.get(), K.rhs0.get());
   auto copy = [&](double* dst, const double* src, int64_t count) {
     if (count > 0) PDLP_HIP(hipMemcpyAsync(dst, src, sizeof(double) * (size_t)count, hipMemcpyDeviceToDevice, stream_));
   };
@@ -508,7 +501,7 @@ void Solver::updateMatrixImpl(const double* aValue, int64_t numNz, const pdlp_up
   gpuFill(colScale_.get(), 1.0, n, stream_);
   gpuFill(rowScale_.get(), 1.0, m, stream_);
   PDLP_HIP(hipStreamSynchronize(stream_));
-  updMatSeconds_[1] = since(t1);
+  updMatSeconds_[kMatFormulate] = since(t1);
 
   t1 = clock::now();
   if (F_.scaled) {  // (PDLP_FEATURE_SCALING_OFF: nothing is scaled, no pass is kept)
@@ -522,7 +515,7 @@ void Solver::updateMatrixImpl(const double* aValue, int64_t numNz, const pdlp_up
     o.csPass = csPass_.get(); o.rsPass = rsPass_.get();  // a later pdlp_mi355x_update replays the NEW factors
     nPass_ = gpuScalePasses(o, stream_);
   }
-  updMatSeconds_[2] = since(t1);
+  updMatSeconds_[kMatPasses] = since(t1);
 
   // the off-diagonal part of the Hessian through the NEW factors (the diagonal rode along with the passes, as in create)
   if (hessianUpdatable_ && hk_.nOff > 0) applyHessian(false, false);
@@ -530,62 +523,24 @@ void Solver::updateMatrixImpl(const double* aValue, int64_t numNz, const pdlp_up
   t1 = clock::now();
   refillOperands();
   PDLP_HIP(hipStreamSynchronize(stream_));
-  updMatSeconds_[3] = since(t1);
+  updMatSeconds_[kMatRefills] = since(t1);
 
   // matNormInf, the host copies of the scale vectors, the left-to-right sums of the scaled c, b — as the set-up does;
   // the termination norms are those of the unscaled data and change with u only
   t1 = clock::now();
   F_.matNormInf = gpuAbsMax(K.cscVal.get(), nnz, stream_);
-  {
-    std::vector<double> hc((size_t)n), hb((size_t)m);
-    colScale_.download(F_.colScale.data(), (size_t)n, stream_);
-    rowScale_.download(F_.rowScale.data(), (size_t)m, stream_);
-    cost_.download(hc.data(), (size_t)n, stream_);
-    rhs_.download(hb.data(), (size_t)m, stream_);
-    PDLP_HIP(hipStreamSynchronize(stream_));
-    sumCost2_ = 0.0;
-    for (double v : hc) sumCost2_ += v * v;
-    sumRhs2_ = 0.0;
-    for (double v : hb) sumRhs2_ += v * v;
-  }
+  colScale_.download(F_.colScale.data(), (size_t)n, stream_);
+  rowScale_.download(F_.rowScale.data(), (size_t)m, stream_);
+  refreshScaledSums(true, true);  // (its synchronisation covers the two downloads above)
   if (mask & kUpdCost) F_.normCost = unscaledNormCost(ud.col_cost, n0, F_.sense);
   if (mask & kUpdRows) F_.normRhs = unscaledNormRhs(ud.row_lower, ud.row_upper, F_.rowKind.data(), m);
   if (ud.has_offset) F_.offset = ud.offset;
-  updMatSeconds_[4] = since(t1);
+  updMatSeconds_[kMatSums] = since(t1);
 
   t1 = clock::now();
-  bool recapture = false;
-  if (fused_) {  // every scaled bound has changed
-    const int32_t before = vecs_.lowerUniform;
-    const int32_t after = refreshBlockBounds() ? 1 : 0;
-    recapture = before != after;
-  }
-  updMatSeconds_[5] = since(t1);
-
-  if (ud.start_col_value) {
-    setHotStart(ud.start_col_value, ud.start_row_value, ud.start_row_dual);  // (with the new scale vectors)
-  } else {
-    hasStart_ = false;
-    startX_.clear();
-    startY_.clear();
-  }
-
-  t1 = clock::now();
-  stPar_ = graphExec_ && !recapture ? graphPar_ : 0;
-  reset();
-  stalledRounds_ = 0;
-  stalledSince_ = 0;
-  updMatSeconds_[7] = since(t1);
-  t1 = clock::now();
-  if (recapture && graphExec_) {
-    (void)hipGraphExecDestroy(graphExec_);
-    graphExec_ = nullptr;
-    captureGraph();
-  }
-  PDLP_HIP(hipStreamSynchronize(stream_));
-  updMatSeconds_[6] = since(t1);
-  updRecaptured_ = recapture && graphExec_ ? 1 : 0;
-  setupSeconds_ = since(t0);
+  const bool recapture = fused_ && refreshBoundsFlipsUniform();  // every scaled bound has changed
+  updMatSeconds_[kMatBounds] = since(t1);
+  finishUpdate(ud, recapture, &updMatSeconds_[kMatReset], &updMatSeconds_[kMatCapture], t0);
 }
 
 }  // namespace pdlp

@@ -26,10 +26,34 @@ inline int32_t updateMask(const pdlp_update_t& u) {
 
 // What can be checked without the problem: row bounds come in pairs, a start is whole or absent.  Throws.
 void checkUpdateShape(const pdlp_update_t& u);
-// The smallest row whose kind under the new bounds differs from rowKind, or m.
-int32_t firstKindChange(const int32_t* rowKind, int32_t m, const double* rowLower, const double* rowUpper);
-// The refusal for such a row: names the row and both kinds.
-[[noreturn]] void throwKindChange(int32_t row, int32_t was, int32_t now);
+// Throws for the smallest row whose kind under the new bounds differs from rowKind (names the row and both kinds); the
+// second form is for a row the device's validation kernel has found already.
+void refuseKindChange(const int32_t* rowKind, int32_t m, const double* rowLower, const double* rowUpper);
+[[noreturn]] void refuseKindChangeAt(const int32_t* rowKind, int32_t row, const double* rowLower, const double* rowUpper);
+
+// The refusals that depend on how the solver was created, each sentence in ONE place; `entry` is the C entry that refuses.
+constexpr const char* kEntryUpdate = "pdlp_mi355x_update";
+constexpr const char* kEntryUpdateMatrix = "pdlp_mi355x_update_matrix";
+constexpr const char* kEntryUpdateValues = "pdlp_mi355x_update_values";
+[[noreturn]] void refuseHipdlp(const char* entry);
+[[noreturn]] void refuseSharded(const char* entry);
+[[noreturn]] void refuseNotUpdatable(const char* entry);
+[[noreturn]] void refuseNoMatrixBit(const char* entry);  // (update_values: "a_value given, but ..." in front)
+[[noreturn]] void refuseNoHessianBit(const char* entry);
+[[noreturn]] void refuseOffDiagonalHessian(const char* entry);
+
+// The caller's five data arrays in one staging buffer (Solver::updIn_, sessIn_): cost | col_lower | col_upper | row_lower |
+// row_upper, count(n0, m) doubles.
+struct DataStage {
+  double *cost, *colLower, *colUpper, *rowLower, *rowUpper;
+  static size_t count(int32_t n0, int32_t m) { return (size_t)3 * n0 + (size_t)2 * m; }
+  static DataStage over(double* base, int32_t n0, int32_t m) {
+    DataStage d;
+    d.cost = base; d.colLower = d.cost + n0; d.colUpper = d.colLower + n0;
+    d.rowLower = d.colUpper + n0; d.rowUpper = d.rowLower + m;
+    return d;
+  }
+};
 
 // Host restatement of the device replay on a form that kept its passes (StandardForm::keepPasses): F.cost / lower / upper
 // / rhs, normCost / normRhs and offset become those of formulate + scale on the modified problem.  Validates first; throws

@@ -298,6 +298,25 @@ def test_release_and_reuse():
     S.close()
 
 
+# ---- what is held ----------------------------------------------------------------------------------------------------------
+def test_held_bytes_are_the_update_state_plus_the_sessions_own_buffers():
+    """held_bytes minus the session's six buffers (sizes as in DESIGN §2f) is what stage("update_state") reports in [0],
+    [4] and [6] for a split-ABI solver with the same bits whose staging exists (one update_matrix)."""
+    lp = L.HighsLp.from_npz(os.path.join(GOLD, "instances", "afiro.npz"))
+    n, m, nnz = lp.num_col, lp.num_row, len(lp.a_value)
+    S = solver.Session()
+    _, info = _solve(S, lp)
+    assert info.path == CREATE
+    own = 8 * (3 * n + 2 * m) + 8 * nnz + 4 * (n + 1 + nnz) + 8  # kept data, kept values, pattern staging, the record
+    ds = solver.DeviceSolver(lp, updatable=_bits(lp), **OPTIONS)
+    ds.update_matrix(np.array(lp.a_value, dtype=np.float64))
+    state = ds.stage("update_state")
+    assert state[0] > 0 and state[4] > 0
+    assert info.held_bytes - own == state[0] + state[4] + state[6], (info.held_bytes, own, state[:8])
+    ds.close()
+    S.close()
+
+
 # ---- the split ABI beside a live session -------------------------------------------------------------------------------------
 def test_session_does_not_disturb_the_split_abi():
     lp = _lp("random_lp")

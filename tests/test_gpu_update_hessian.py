@@ -248,6 +248,29 @@ def test_refusals_change_nothing():
     ds.close()
 
 
+def test_refusal_precedence_is_the_host_twins():
+    """Doubly wrong updates (HC.doubly_wrong): the device refuses with the words of pdlp_mi355x_host_prepare_qp, in its
+    order — row kind, all-zero matrix, Hessian diagonal — and writes nothing."""
+    lp = _lp("random_sparse_qp")
+    ds, untouched = _create(lp, updatable="matrix+hessian"), _create(lp, updatable="matrix+hessian")
+    want = _iterate_state(untouched)
+    untouched.close()
+    before = _vectors(ds, True)
+    for name, (u, words) in HC.doubly_wrong(lp).items():
+        data = {k: v for k, v in u.items() if k not in ("a_value", "q_value")}
+        with pytest.raises(RuntimeError) as host:
+            solver.host_prepare_qp(lp, a_value=u.get("a_value"), q_value=u.get("q_value"),
+                                   update=abi.UpdateHandle(**data) if data else None, updatable="matrix+hessian")
+        # (the Python layer puts "<entry> failed: " in front of the library's message, on either side)
+        msg, twin = _refused(ds, **u).split(" failed: ", 1)[1], str(host.value).split(" failed: ", 1)[1]
+        assert words in msg and msg == twin, (name, msg, twin)
+    after = _vectors(ds, True)
+    for k in before:
+        assert np.array_equal(before[k], after[k]), k
+    _assert_same_state(_iterate_state(ds), want)
+    ds.close()
+
+
 @pytest.mark.parametrize("why", ["missing_bit", "matrix_bit_only", "lp", "hipdlp", "sharded"])
 def test_refused_by_how_the_solver_was_created(why, monkeypatch):
     lp = _lp("random_sparse_qp")

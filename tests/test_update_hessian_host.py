@@ -240,6 +240,15 @@ def test_refusals():
     assert "no matrix nonzeros" in msg
 
 
+def test_refusal_precedence():
+    """Doubly wrong updates: row kind before all-zero matrix before Hessian diagonal (tests/update_hessian_cases.py
+    doubly_wrong names the expected words)."""
+    lp = _lp("random_sparse_qp")
+    for name, (u, words) in HC.doubly_wrong(lp).items():
+        msg = _message(lp, a_value=u.get("a_value"), q_value=u.get("q_value"), update=_handle(u), updatable="matrix+hessian")
+        assert words in msg, (name, msg)
+
+
 @pytest.mark.parametrize("with_matrix", [False, True])
 def test_a_negative_diagonal_names_the_smallest_column(with_matrix):
     lp = _lp("random_sparse_qp")

@@ -93,6 +93,24 @@ def modification(lp, what, seed, sparse_seed=None):
     return dict(q_value=new_values(lp, what, seed, sparse_seed))
 
 
+def doubly_wrong(lp):
+    """Three updates that are each wrong in two ways, name -> (keyword arguments of update_values, words of the refusal that
+    must win): a changed kind of row 0, an all-zero a_value and a negative Hessian diagonal are refused in this order."""
+    lo, up = np.array(lp.row_lower, dtype=np.float64), np.array(lp.row_upper, dtype=np.float64)
+    if MC.UC.row_kind(lo[:1], up[:1])[0] == 0:
+        up[0] = np.inf  # equality -> >=
+    else:
+        lo[0] = up[0] = 1.0  # anything else -> equality
+    rows, cols = _slots(lp)
+    q_bad = np.array(lp.hessian[2], dtype=np.float64)
+    q_bad[np.nonzero(rows == cols)[0][0]] = -lp.sense * 0.5
+    zeros = np.zeros(len(lp.a_value))
+    kind, zero = "row 0 would change its kind", "no matrix nonzeros"
+    return {"kind+zero": (dict(row_lower=lo, row_upper=up, a_value=zeros), kind),
+            "zero+diagonal": (dict(a_value=zeros, q_value=q_bad), zero),
+            "kind+diagonal": (dict(row_lower=lo, row_upper=up, q_value=q_bad), kind)}
+
+
 def apply(lp, u):
     """The modified problem P' (a copy; the pattern arrays are shared)."""
     rest = {k: v for k, v in u.items() if k != "q_value"}
