@@ -159,7 +159,7 @@ __device__ __forceinline__ int nextHalt(int it, const CheckCtl& c) {
   if (it + 1 < 10) next = it + 1;
   else next = ((long long)it / c.interval + 1) * c.interval;
   const long long last = (long long)c.optIterLimit - 1;
-  if (last > it && last < next) next = last;
+  if (c.terminate && last > it && last < next) next = last;  // (the fixed-work loop has no check there: it would stay halted)
   if (!c.terminate && next > c.iterLimit) next = c.iterLimit;
   if (next > 2147483647LL) next = 2147483647LL;
   return (int)next;

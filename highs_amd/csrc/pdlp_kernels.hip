@@ -693,7 +693,7 @@ __global__ __launch_bounds__(kSlabThreads, TWO ? 2 * kSlabThreads / 256 : kSlabT
       const int verdict = gridWait(a.bar, (int)blockIdx.x, nExp, (unsigned long long)a.st->nTrials + 1ull, lane, a.barLimit);
       if (lane == 0) *barVerdict = verdict;
     }
-    {  // the state record -> LDS, one word per thread (no register copy of the 50-word record)
+    {  // the state record -> LDS, one word per thread (no register copy of the 48-word record)
       const uint32_t* src = reinterpret_cast<const uint32_t*>(a.st);
       uint32_t* dstw = reinterpret_cast<uint32_t*>(sh);
       if (tid >= kVecThreads && tid - kVecThreads < (int)(sizeof(DevState) / 4)) dstw[tid - kVecThreads] = src[tid - kVecThreads];

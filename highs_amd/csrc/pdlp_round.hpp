@@ -35,7 +35,9 @@ struct RoundLoop {
   bool terminate;
   int32_t interval, iterLimit;
   int64_t haltAfter(int64_t it) const {
-    int64_t h = nextCheckIter((int32_t)it, interval, iterLimit);
+    // (the fixed-work loop checks nowhere but on the interval — roundEntry, checkDue — so it must not halt at the last
+    // iteration of iterLimit either: no check would run there and the device would stay halted in front of its target)
+    int64_t h = nextCheckIter((int32_t)it, interval, terminate ? iterLimit : INT_MAX);
     if (!terminate && h > iterLim) h = iterLim;
     return h;
   }

@@ -2312,6 +2312,14 @@ void Solver::setVector(const std::string& name, const double* host, int64_t len)
   if (l != len) throw std::runtime_error("length mismatch for vector " + name);
   PDLP_HIP(hipMemcpyAsync(p, host, sizeof(double) * len, hipMemcpyHostToDevice, stream_));
   PDLP_HIP(hipStreamSynchronize(stream_));
+  // the fused trial projects onto per-block scalars and its graph bakes the ULO instantiation in: both follow the bounds,
+  // as after an update (finishUpdate)
+  if (fused_ && (name == "lower" || name == "upper") && refreshBoundsFlipsUniform() && graphExec_) {
+    (void)hipGraphExecDestroy(graphExec_);
+    graphExec_ = nullptr;
+    captureGraph();
+    PDLP_HIP(hipStreamSynchronize(stream_));
+  }
 }
 
 void Solver::stage(const std::string& name, double* out, int32_t cap) {
@@ -2411,6 +2419,18 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     put(0, (double)smallLaunches_);
   } else if (name == "uniform_bound_columns") {  // columns whose lower / upper bound the fused launch takes from a scalar of their block
     put(0, (double)uniLowerCols_); put(1, (double)uniUpperCols_);
+  } else if (name == "fused_form") {  // the instantiation of k_spmv_slab<kAtyFused, TWO, CC, ULO> as launchSpmvAtyFusedPrimal picks it
+    const MatView at = dAt_.view();
+    const int32_t co = fused_ && at.lng.nTasks > 0 ? at.coTaskBlocks : 0;
+    put(0, fused_ ? 1.0 : 0.0);
+    put(1, co > 0 ? 1.0 : 0.0);
+    put(2, fused_ && vecs_.constCached ? 1.0 : 0.0);
+    put(3, fused_ && vecs_.lowerUniform ? 1.0 : 0.0);
+    put(4, (double)co);
+    put(5, fused_ && at.lng.nTasks > 0 && co == 0 ? 1.0 : 0.0);
+    put(6, fused_ && at.touchTail ? 1.0 : 0.0);
+    put(7, at.useSlab ? (double)at.slab.rowsPerBlock : 0.0);
+    put(8, (double)sizeof(DevState));  // (part of the launch's LDS request, which bounds rowsPerBlock for TWO)
   } else if (name == "exchange") {  // 0 = not sharded, 1 = RCCL all-reduce, 3 = direct xGMI mesh, two all-gathers (2 was the removed partials layout)
     put(0, !sharded_ ? 0.0 : !meshMode_ ? 1.0 : 3.0);
   } else if (name == "residuals") {

@@ -487,7 +487,8 @@ int pdlp_mi355x_iterate(pdlp_mi355x_solver_t* s, int32_t n_iters,
  * "x","y","ax","aty" (current iterate), "x_next","y_next","ax_next","aty_next",
  * "x_avg","y_avg","ax_avg","aty_avg","x_sum","y_sum","cost","rhs","lower",
  * "upper","col_scale","row_scale","slack_pos","slack_neg"; QP solvers also "qdiag" (the scaled diagonal of Q, length n).
- * len must equal the vector's length (n or m). */
+ * len must equal the vector's length (n or m).  Setting "lower" or "upper" also refreshes the per-block bound
+ * scalars of the fused trial (and captures its graph again where the one-lower-bound instantiation changes). */
 int pdlp_mi355x_get_vector(pdlp_mi355x_solver_t* s, const char* name,
                            double* host, int64_t len);
 int pdlp_mi355x_set_vector(pdlp_mi355x_solver_t* s, const char* name,
@@ -502,6 +503,12 @@ int pdlp_mi355x_set_vector(pdlp_mi355x_solver_t* s, const char* name,
  *              (eager launches, no hipGraph): the next pdlp_mi355x_iterate then reports the
  *              IN-LOOP average launch durations in spmv_ax_ms / spmv_aty_ms (reserved[0] = launches)
  *  "exchange"  scalars_out[0] = 0 not sharded, 1 RCCL all-reduce, 2 direct xGMI mesh
+ *  "fused_form" launches nothing: the instantiation of the fused A'y+ launch this solver runs —
+ *              [0] 1 = the 2-launch (fused) trial, [1] 1 = its 64-register variant with co-resident task
+ *              workgroups (TWO), [2] CC, [3] ULO (one lower bound for all columns), [4] task workgroups,
+ *              [5] 1 = the streaming blocks run the long columns' tasks themselves, [6] 1 = the tail columns
+ *              are touched before the barrier, [7] accumulator rows per block of A' in the slab layout,
+ *              [8] bytes of the state record in the launch's LDS request
  * HiPDLP solvers (algorithm = 1) instead know:
  *  "steps"     scalars_out[0] holds k on entry (1..40): run Halpern steps 1..k of a block, first and
  *              last one "major" (pdhg.cc:961-1018), from the current state and step sizes

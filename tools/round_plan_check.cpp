@@ -27,7 +27,9 @@ struct Case {
 bool refCheckAt(const Case& c, int64_t it) { return it < 10 || it % c.interval == 0 || (c.terminate && it == (int64_t)c.iterLimit - 1); }
 int64_t refNextHalt(const Case& c, int64_t it) {  // the next iteration the device halts at
   int64_t h = it + 1;
-  while (!(h < 10 || h % c.interval == 0 || h == (int64_t)c.iterLimit - 1)) ++h;
+  // (the fixed-work loop checks nowhere but on the interval, so it must not halt at iter_limit - 1 either: nothing would
+  // release it there)
+  while (!(h < 10 || h % c.interval == 0 || (c.terminate && h == (int64_t)c.iterLimit - 1))) ++h;
   if (!c.terminate && h > c.target) h = c.target;
   return h;
 }
@@ -142,9 +144,13 @@ void fixedWork() {
   for (int64_t start : {0, 3, 9, 10, 39, 40, 57})
     for (int64_t work : {1, 5, 40, 57, 200, 1000})
       for (int32_t interval : {40, 7, 1000})
-        for (int32_t ahead : {1, 2, 4, 16}) {
-          const Case c{start, INT_MAX, interval, ahead, false, start + work};
-          const RoundLoop L{c.target, false, interval, INT_MAX};
+        for (int32_t ahead : {1, 2, 4, 16})
+          // (a finite iteration limit at, one below and well below the target: the loop runs through iter_limit - 1
+          // without halting there, where it once stayed halted for good)
+          for (int64_t limit : {(int64_t)INT_MAX, start + work, start + work - 1, start + work / 2 + 1}) {
+          if (limit < 1) continue;
+          const Case c{start, (int32_t)limit, interval, ahead, false, start + work};
+          const RoundLoop L{c.target, false, interval, c.iterLimit};
           for (int64_t it = start; it < c.target; ++it) CHECK(L.haltAfter(it) <= c.target && L.haltAfter(it) == refNextHalt(c, it));
           for (unsigned seed : {0u, 7u}) {
             int64_t end = -1;
