@@ -274,6 +274,24 @@ class PdlpStreamPlan(C.Structure):
     ]
 
 
+class PdlpDeviceMatrix(C.Structure):
+    """pdlp_device_matrix_t (csrc/pdlp_api.cpp, a test hook outside the public header): what a solver holds of one
+    operand after its set-up, for the GPU tests of the device-side set-up."""
+    _fields_ = [
+        ("use_slab", C.c_int32), ("n_major", C.c_int32), ("n_minor", C.c_int32), ("chunk", C.c_int32),
+        ("n_blocks", C.c_int32), ("slab_blocks", C.c_int32), ("rows_per_block", C.c_int32), ("minor_bits", C.c_int32),
+        ("slab_width_log2", C.c_int32), ("n_long", C.c_int32), ("n_tasks", C.c_int32), ("task_group", C.c_int32),
+        ("long_group", C.c_int32), ("long_slots", C.c_int32), ("tile_log2", C.c_int32), ("n_tiles", C.c_int32),
+        ("n_mask_words", C.c_int32), ("n_csr_major", C.c_int32),
+        ("nnz", C.c_int64), ("nnz_short", C.c_int64), ("nnz_csr", C.c_int64),
+        ("beg", c_i32p), ("idx", c_i32p), ("block_beg", c_i32p), ("wave_beg", c_i32p), ("wave_ptr", c_i32p),
+        ("long_map", c_i32p), ("tasks", c_i32p), ("span_lo", c_i32p), ("span_hi", c_i32p), ("span_cnt", c_i32p),
+        ("ent", C.POINTER(C.c_uint32)), ("long_mask", C.POINTER(C.c_uint32)),
+        ("val", c_f64p), ("slab_val", c_f64p),
+        ("tile_owner", C.POINTER(C.c_int8)),
+    ]
+
+
 class PdlpMpsModel(C.Structure):
     """pdlp_mps_model_t (include/pdlp_mi355x.h): what pdlp_mi355x_read_mps fills."""
     _fields_ = [

@@ -10,6 +10,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "pdlp_batch.hpp"
@@ -628,6 +629,81 @@ int pdlp_mi355x_host_stream_plan(const pdlp_prepared_t* prep, int32_t which, int
 void pdlp_mi355x_free_stream_plan(pdlp_stream_plan_t* o) {
   if (!o) return;
   free(o->block_beg); free(o->long_majors); free(o->tasks);
+  memset(o, 0, sizeof(*o));
+}
+
+// TEST HOOK, not part of the public header (no product code calls it): what a solver holds of operand `which` (0: A by rows,
+// 1: A' by columns) after its set-up, on the host or on the device — downloaded as it lies in HBM, with no launch and no
+// change of state.  Stream layout (use_slab = 0): beg / idx / val are the operand's CSR, block_beg its work blocks
+// [4 * n_blocks].  Slab layout: beg / idx / val are the compact CSR of the long majors (long_map: compact index -> major),
+// wave_beg / wave_ptr [16 * slab_blocks + 1], ent / slab_val [nnz_short], long_mask [n_mask_words], and what the build
+// decided on the way: tile_owner [n_tiles], span_lo / span_hi / span_cnt [slab_blocks].  idx / val / ent / slab_val come
+// with their pad element (nnz_csr + 1, nnz_short + 1 entries).  tasks: [8 * n_tasks], records as in pdlp_task_plan_t.
+struct pdlp_device_matrix_t {
+  int32_t use_slab, n_major, n_minor, chunk, n_blocks, slab_blocks, rows_per_block, minor_bits;
+  int32_t slab_width_log2, n_long, n_tasks, task_group, long_group, long_slots, tile_log2, n_tiles;
+  int32_t n_mask_words, n_csr_major;
+  int64_t nnz, nnz_short, nnz_csr;
+  int32_t *beg, *idx, *block_beg, *wave_beg, *wave_ptr, *long_map, *tasks, *span_lo, *span_hi, *span_cnt;
+  uint32_t *ent, *long_mask;
+  double *val, *slab_val;
+  int8_t* tile_owner;
+};
+int pdlp_mi355x_device_matrix(pdlp_mi355x_solver_t* h, int32_t which, pdlp_device_matrix_t* out) {
+  return guarded([&] {
+    if (!h || !h->impl || !out) throw std::runtime_error("null argument");
+    if (which != 0 && which != 1) throw std::runtime_error("pdlp_mi355x_device_matrix: which is 0 (A) or 1 (A')");
+    memset(out, 0, sizeof(*out));
+    hipStream_t s = nullptr;
+    const pdlp::DeviceMatrix& M = *h->impl->deviceMatrix(which, &s);
+    out->use_slab = M.useSlab ? 1 : 0; out->n_major = M.nMajor; out->n_minor = M.nMinor; out->chunk = M.chunk;
+    out->n_blocks = M.nBlocks; out->n_long = M.nLong; out->n_tasks = M.nTasks; out->task_group = M.taskGroup;
+    out->long_group = M.longGroup; out->long_slots = M.longSlots; out->nnz = M.nnz;
+    out->n_csr_major = M.beg.size() ? (int32_t)M.beg.size() - 1 : 0;
+    auto pull = [&](const auto& dev, size_t count) {
+      using T = typename std::remove_pointer<decltype(dev.get())>::type;
+      if (count > dev.size()) throw std::runtime_error("pdlp_mi355x_device_matrix: an array is shorter than its layout says");
+      std::vector<T> v(count);
+      dev.download(v.data(), count, s);
+      PDLP_HIP(hipStreamSynchronize(s));
+      return v;
+    };
+    const std::vector<int32_t> beg = pull(M.beg, M.beg.size());
+    out->nnz_csr = beg.empty() ? 0 : beg.back();
+    out->beg = dupVec(beg);
+    out->idx = dupVec(pull(M.idx, (size_t)out->nnz_csr + 1));
+    out->val = dupVec(pull(M.val, (size_t)out->nnz_csr + 1));
+    out->block_beg = dupVec(pull(M.blockBeg, (size_t)4 * M.nBlocks));
+    static_assert(sizeof(pdlp::LongTask) == 8 * sizeof(int32_t), "task record layout");
+    {
+      const std::vector<pdlp::LongTask> t = pull(M.lTasks, (size_t)M.nTasks);
+      std::vector<int32_t> flat((size_t)8 * M.nTasks);
+      if (M.nTasks > 0) memcpy(flat.data(), t.data(), flat.size() * sizeof(int32_t));
+      out->tasks = dupVec(flat);
+    }
+    if (M.useSlab) {
+      const int32_t nB = M.slab.nBlocks;
+      out->slab_blocks = nB; out->rows_per_block = M.slab.rowsPerBlock; out->minor_bits = M.slab.minorBits;
+      out->slab_width_log2 = M.slabWidthLog2; out->tile_log2 = M.tileLog2; out->n_tiles = (int32_t)M.hostTileOwner.size();
+      out->n_mask_words = (int32_t)M.longMask.size();
+      const std::vector<int32_t> wavePtr = pull(M.wavePtr, (size_t)nB * pdlp::kSlabWavesPerBlock + 1);
+      out->nnz_short = wavePtr.back();
+      out->wave_ptr = dupVec(wavePtr);
+      out->wave_beg = dupVec(pull(M.waveBeg, (size_t)nB * pdlp::kSlabWavesPerBlock + 1));
+      out->ent = dupVec(pull(M.ent, (size_t)out->nnz_short + 1));
+      out->slab_val = dupVec(pull(M.slabVal, (size_t)out->nnz_short + 1));
+      out->long_mask = dupVec(pull(M.longMask, M.longMask.size()));
+      out->long_map = dupVec(M.hostLongMap);
+      out->tile_owner = dupVec(M.hostTileOwner);
+      out->span_lo = dupVec(M.hostSpanLo); out->span_hi = dupVec(M.hostSpanHi); out->span_cnt = dupVec(M.hostSpanCnt);
+    }
+  });
+}
+void pdlp_mi355x_free_device_matrix(pdlp_device_matrix_t* o) {
+  if (!o) return;
+  free(o->beg); free(o->idx); free(o->block_beg); free(o->wave_beg); free(o->wave_ptr); free(o->long_map); free(o->tasks);
+  free(o->span_lo); free(o->span_hi); free(o->span_cnt); free(o->ent); free(o->long_mask); free(o->val); free(o->slab_val);
+  free(o->tile_owner);
   memset(o, 0, sizeof(*o));
 }
 

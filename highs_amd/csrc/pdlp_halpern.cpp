@@ -85,6 +85,7 @@ void HalpernSolver::construct(const pdlp_problem_t& P, const void* id128) {
   bool gpuSetup = nnzIn >= 200000;
   if (sw.gpuSetup >= 0) gpuSetup = sw.gpuSetup != 0;
   if (sharded_) gpuSetup = false;  // the row-block shards are cut on the host
+  gpuSetup_ = gpuSetup;
   if (gpuSetup) {
     HipdlpSetup hs;
     hs.ruiz = opt_.scaling_mode & 1; hs.pc = opt_.scaling_mode & 4; hs.l2 = opt_.scaling_mode & 2;
@@ -765,6 +766,10 @@ void HalpernSolver::stage(const std::string& name, double* out, int32_t cap) {
     double us[3] = {0, 0, 0}, cnt[3] = {0, 0, 0};
     if (mesh_) mesh_->phaseStats(us, cnt, stream_);
     for (int k = 0; k < 3; ++k) { put(k, us[k]); put(3 + k, cnt[k]); }
+  } else if (name == "setup_scalars") {  // launches nothing: as Solver's stage of this name; what this form does not have is NaN
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    put(0, F_.normCost); put(1, F_.normRhs); put(2, nan); put(3, nan); put(4, nan);
+    put(5, (double)F_.nEqs); put(6, (double)F_.n0); put(7, F_.scaled ? 1.0 : 0.0); put(8, gpuSetup_ ? 1.0 : 0.0);
   } else if (name == "exchange") {
     put(0, sharded_ ? 2.0 : 0.0);
   } else if (name == "profile_on" || name == "profile_off") {

@@ -54,6 +54,7 @@ class HalpernSolver : public SolverBase {
   void setVector(const std::string& name, const double* host, int64_t len) override;
   void stage(const std::string& name, double* out, int32_t cap) override;
   double timeKernel(const std::string& name, int32_t reps) override;
+  const DeviceMatrix* deviceMatrix(int32_t which, hipStream_t* s) const override { *s = stream_; return which ? &dAt_ : &dA_; }
 
  private:
   void construct(const pdlp_problem_t& P, const void* id128);
@@ -94,6 +95,7 @@ class HalpernSolver : public SolverBase {
   // sharding (rows [r0_, r1_) and column slice [c0_, c1_) are owned; everything when world == 1)
   int32_t rank_ = 0, world_ = 1, r0_ = 0, r1_ = 0, mLoc_ = 0, c0_ = 0, c1_ = 0, nLoc_ = 0;
   bool sharded_ = false;
+  bool gpuSetup_ = false;  // formulated, scaled and laid out on the device (stage "setup_scalars")
   Mesh* mesh_ = nullptr;
   DeviceArray<double> commBuf_;  // partial A_g' y (n)
   hipStream_t stream_ = nullptr;

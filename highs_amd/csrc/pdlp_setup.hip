@@ -740,8 +740,10 @@ void gpuBuildSlabLayout(const DeviceCsrData& M, int32_t longLimit, int32_t W, in
     L.longCsr.nnz = 0;
     L.longCsr.beg.alloc(1);
     L.longCsr.beg.zero(s);
-    L.longCsr.idx.alloc(1);
+    L.longCsr.idx.alloc(1);  // (the pad element alone: zero, as the host build uploads it)
     L.longCsr.val.alloc(1);
+    L.longCsr.idx.zero(s);
+    L.longCsr.val.zero(s);
   }
 
   // short entries sorted by (wave, slab); the stable sort keeps (major, minor) order inside

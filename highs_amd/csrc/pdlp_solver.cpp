@@ -110,6 +110,7 @@ bool DeviceMatrix::touchesFewTiles(const std::vector<int32_t>& lo, const std::ve
 
 void DeviceMatrix::upload(const Compressed& cIn, int32_t nMajor_, int32_t nMinor_, const DevSwitches& sw, hipStream_t s) {
   nMajor = nMajor_;
+  nMinor = nMinor_;
   nnz = cIn.beg.empty() ? 0 : cIn.beg[nMajor_];
   useSlab = chooseSlab(sw.slab, nMajor_, nMinor_);
   const Compressed* c = &cIn;
@@ -125,8 +126,10 @@ void DeviceMatrix::upload(const Compressed& cIn, int32_t nMajor_, int32_t nMinor
     const int32_t nTiles = xcdTileCount(nMinor_, tileLog2);
     const std::vector<int32_t> hist = slabTileHistogram(cIn.beg.data(), cIn.idx.data(), part, kSlabLongLimit, tileLog2, nTiles, lo, hi, cnt);
     tileOwner = xcdTileOwners(hist, nTiles);
-    buildSlabLayout(cIn, nMajor_, nMinor_, kSlabLongLimit, slabWidthFor(sw, touchesFewTiles(lo, hi, cnt)), majorCost, L);
+    slabWidthLog2 = slabWidthFor(sw, touchesFewTiles(lo, hi, cnt));
+    buildSlabLayout(cIn, nMajor_, nMinor_, kSlabLongLimit, slabWidthLog2, majorCost, L);
     if (L.rowsPerBlock > kSlabMaxRows) throw std::runtime_error("slab layout: too many majors per block");
+    hostTileOwner = tileOwner; hostSpanLo = lo; hostSpanHi = hi; hostSpanCnt = cnt; hostLongMap = L.longMap;
     wavePtr.alloc(L.wavePtr.size());
     wavePtr.upload(L.wavePtr.data(), L.wavePtr.size(), s);
     waveBeg.alloc(L.waveBeg.size());
@@ -152,15 +155,17 @@ void DeviceMatrix::upload(const Compressed& cIn, int32_t nMajor_, int32_t nMinor
   beg.upload(c->beg.data(), c->beg.size(), s);
   idx.upload(c->idx.data(), (size_t)nnzCsr, s);
   val.upload(c->val.data(), (size_t)nnzCsr, s);
+  this->tileLog2 = tileLog2;
   uploadPlans(c->beg, nCsrMajor, useSlab ? L.longMap.data() : nullptr, s, c->idx.data(), useSlab ? &tileOwner : nullptr, tileLog2);
   PDLP_HIP(hipStreamSynchronize(s));  // host vectors may go out of scope
 }
 
 void DeviceMatrix::buildFromDevice(DeviceCsrData& M, const DevSwitches& sw, hipStream_t s) {
   nMajor = M.nMajor;
+  nMinor = M.nMinor;
   nnz = M.nnz;
   useSlab = chooseSlab(sw.slab, M.nMajor, M.nMinor);
-  std::vector<int32_t> hostBeg, hostLongMap, hostLongIdx;
+  std::vector<int32_t> hostBeg, hostLongIdx;
   std::vector<int8_t> tileOwner;
   int32_t tileLog2 = 0;
   int32_t nCsrMajor = nMajor;
@@ -185,6 +190,7 @@ void DeviceMatrix::buildFromDevice(DeviceCsrData& M, const DevSwitches& sw, hipS
       PDLP_HIP(hipStreamSynchronize(s));
       localM = touchesFewTiles(lo, hi, cnt);
       tileOwner = xcdTileOwners(hist, nTiles);
+      hostTileOwner = tileOwner; hostSpanLo = lo; hostSpanHi = hi; hostSpanCnt = cnt;
       // how long the runs of equal majors are at the rule's widest slabs (2^17): entries per short major of a block, over
       // the number of slabs the block's span crosses — 1 on a random operand (every entry of a row in another slab), the
       // major's whole length where a block is local.  Below 2 no narrower slab can help (buildSlabTuned skips its candidates).
@@ -228,6 +234,7 @@ void DeviceMatrix::buildFromDevice(DeviceCsrData& M, const DevSwitches& sw, hipS
     beg.download(hostBeg.data(), hostBeg.size(), s);
     PDLP_HIP(hipStreamSynchronize(s));
   }
+  this->tileLog2 = tileLog2;
   uploadPlans(hostBeg, nCsrMajor, useSlab ? hostLongMap.data() : nullptr, s, useSlab ? hostLongIdx.data() : nullptr,
               useSlab ? &tileOwner : nullptr, tileLog2);
 }
@@ -2394,6 +2401,10 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     // scaling passes, refills, norms + sums, per-block bounds, graph capture, reset; [8] = the whole update
     for (int k = 0; k < kMatSlots; ++k) put(k, updMatSeconds_[k]);
     put(kMatSlots, setupSeconds_);
+  } else if (name == "setup_scalars") {  // launches nothing: what the set-up left on the host — {normCost, normRhs, matNormInf, sumCost2,
+    // sumRhs2, nEqs, n0, scaled}, then [8] 1 = formulated, scaled and laid out on the device (pdlp_setup.hip), 0 = on the host
+    put(0, F_.normCost); put(1, F_.normRhs); put(2, F_.matNormInf); put(3, sumCost2_); put(4, sumRhs2_);
+    put(5, (double)F_.nEqs); put(6, (double)F_.n0); put(7, F_.scaled ? 1.0 : 0.0); put(8, gpuSetup_ ? 1.0 : 0.0);
   } else if (name == "trial_launches") {  // kernels per trial step of the hot loop (2 = fused decision + primal step)
     // mesh: 9 with single-block wait kernels, 7 with consumers that wait themselves, 5 with an exchange per launch
     // (fusedWait 0 / 1 / 2)

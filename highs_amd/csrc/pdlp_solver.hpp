@@ -62,11 +62,17 @@ struct DeviceMatrix {
   int64_t nnz = 0;
   bool useSlab = false;
   int32_t noPace = 0;  // slab kernel without the per-group block barrier (SlabMat::noPace), see tuneXcdMap
-  int32_t slabWidthLog2 = 0;  // log2 of the slab width the layout was built with (device build; see buildSlabTuned)
+  int32_t slabWidthLog2 = 0;  // log2 of the slab width the layout was built with (either build; see buildSlabTuned)
   double estRunLen = 1.0;     // estimated run length of equal majors at the widest slabs (device build)
   bool mapTuned = false;      // XCD map / pacing already chosen by timing (with the slab width)
   int32_t xcdMap = 1;  // block -> XCD assignment of the SpMV kernels (pdlp_kernels.hip xcdContiguousBlock), see tuneXcdMap
   SlabMat slab{};
+  // Host copies of what a build decides and then forgets (slab layout; a few KB): the minors, the XCD that owns every tile
+  // of the gathered vector, the per-block span and entry count of the short majors, the long majors.  Read by the test hook
+  // pdlp_mi355x_device_matrix alone.
+  int32_t nMinor = 0, tileLog2 = 0;
+  std::vector<int8_t> hostTileOwner;
+  std::vector<int32_t> hostSpanLo, hostSpanHi, hostSpanCnt, hostLongMap;
   // sw.slab: 0 = CSR stream only, 1 = slab layout, -1 = auto by nMinor
   void upload(const Compressed& c, int32_t nMajor_, int32_t nMinor_, const DevSwitches& sw, hipStream_t s);
   // same, from a matrix that is already in HBM (GPU-side setup); takes M's arrays
@@ -115,6 +121,8 @@ class SolverBase {
   virtual void setVector(const std::string& name, const double* host, int64_t len) = 0;
   virtual void stage(const std::string& name, double* out, int32_t cap) = 0;
   virtual double timeKernel(const std::string& name, int32_t reps) = 0;
+  // test hook pdlp_mi355x_device_matrix: operand 0 = A by rows, 1 = A' by columns, and the stream its arrays are read on
+  virtual const DeviceMatrix* deviceMatrix(int32_t which, hipStream_t* s) const = 0;
   // pdlp_mi355x_update; validates before it changes anything.  Only the cuPDLP-C path takes updates.
   virtual void update(const pdlp_update_t& u);
   // pdlp_mi355x_update_matrix; likewise
@@ -140,6 +148,7 @@ class Solver : public SolverBase {
   void setVector(const std::string& name, const double* host, int64_t len) override;
   void stage(const std::string& name, double* out, int32_t cap) override;
   double timeKernel(const std::string& name, int32_t reps) override;
+  const DeviceMatrix* deviceMatrix(int32_t which, hipStream_t* s) const override { *s = stream_; return which ? &dAt_ : &dA_; }
   void update(const pdlp_update_t& u) override;  // pdlp_update.cpp
   void updateMatrix(const double* aValue, int64_t numNz, const pdlp_update_t* u) override;  // pdlp_update.cpp
   void updateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz,

@@ -156,6 +156,12 @@ def lib():
         L.pdlp_mi355x_host_stream_plan.argtypes = [pPrep, C.c_int32, C.c_int32, C.c_int32, pPlan]
         L.pdlp_mi355x_free_stream_plan.argtypes = [pPlan]
         L.pdlp_mi355x_free_stream_plan.restype = None
+        # (a test hook outside the public header: what a solver holds of an operand after its set-up)
+        if hasattr(L, "pdlp_mi355x_device_matrix"):  # (an older build given through PDLP_MI355X_LIB has none)
+            pDevM = C.POINTER(abi.PdlpDeviceMatrix)
+            L.pdlp_mi355x_device_matrix.argtypes = [H, C.c_int32, pDevM]
+            L.pdlp_mi355x_free_device_matrix.argtypes = [pDevM]
+            L.pdlp_mi355x_free_device_matrix.restype = None
         pMps = C.POINTER(abi.PdlpMpsModel)
         L.pdlp_mi355x_read_mps.argtypes = [C.c_char_p, C.c_int32, pMps]
         L.pdlp_mi355x_read_mps_timed.argtypes = [C.c_char_p, C.c_int32, C.c_double, pMps]
@@ -557,6 +563,36 @@ class DeviceSolver:
         if init is not None:  # a few stages read their argument from the scalar array
             out[:len(init)] = init
         _check(lib().pdlp_mi355x_stage(self.h, name.encode(), out.ctypes.data_as(abi.c_f64p), n_out), "stage " + name)
+        return out
+
+    SETUP_SCALARS = ("norm_cost", "norm_rhs", "mat_norm_inf", "sum_cost2", "sum_rhs2", "n_eqs", "n0", "scaled", "gpu_setup")
+
+    def setup_scalars(self):
+        """Stage "setup_scalars" as a dict: what the set-up left on the host (NaN: this form has no such number) and
+        gpu_setup, 1.0 where the device formulated, scaled and laid the problem out."""
+        return dict(zip(self.SETUP_SCALARS, self.stage("setup_scalars", len(self.SETUP_SCALARS)).tolist()))
+
+    def device_matrix(self, which):
+        """pdlp_mi355x_device_matrix: what the solver holds of operand `which` (0: A by rows, 1: A' by columns), downloaded
+        as it lies in HBM (no launch, no change of state).  A dict of numbers and numpy copies: beg / idx / val are the
+        operand's CSR (stream layout) or the compact CSR of its long majors (slab layout); idx, val, ent and slab_val
+        come with their pad element; blocks [n_blocks, 4], tasks [n_tasks, 8] (pdlp_task_plan_t's records)."""
+        D = abi.PdlpDeviceMatrix()
+        _check(lib().pdlp_mi355x_device_matrix(self.h, which, C.byref(D)), "device_matrix")
+        g = lambda p, k, dt: np.ctypeslib.as_array(p, shape=(max(k, 1),))[:k].astype(dt).copy() if p else np.zeros(0, dtype=dt)
+        nw = 16 * D.slab_blocks + 1 if D.use_slab else 0
+        out = {k: getattr(D, k) for k in ("use_slab", "n_major", "n_minor", "nnz", "chunk", "n_blocks", "slab_blocks", "rows_per_block",
+                                          "minor_bits", "slab_width_log2", "n_long", "n_tasks", "task_group", "long_group",
+                                          "long_slots", "nnz_short", "tile_log2", "n_tiles")}
+        out.update(
+            beg=g(D.beg, D.n_csr_major + 1, np.int64), idx=g(D.idx, D.nnz_csr + 1, np.int64), val=g(D.val, D.nnz_csr + 1, np.float64),
+            block_beg=g(D.block_beg, 4 * D.n_blocks, np.int64).reshape(-1, 4), tasks=g(D.tasks, 8 * D.n_tasks, np.int64).reshape(-1, 8),
+            wave_beg=g(D.wave_beg, nw, np.int64), wave_ptr=g(D.wave_ptr, nw, np.int64),
+            ent=g(D.ent, D.nnz_short + 1 if D.use_slab else 0, np.uint32), slab_val=g(D.slab_val, D.nnz_short + 1 if D.use_slab else 0, np.float64),
+            long_mask=g(D.long_mask, D.n_mask_words, np.uint32), long_map=g(D.long_map, D.n_long if D.use_slab else 0, np.int64),
+            tile_owner=g(D.tile_owner, D.n_tiles, np.int64), span_lo=g(D.span_lo, D.slab_blocks, np.int64),
+            span_hi=g(D.span_hi, D.slab_blocks, np.int64), span_cnt=g(D.span_cnt, D.slab_blocks, np.int64))
+        lib().pdlp_mi355x_free_device_matrix(C.byref(D))
         return out
 
     def time_kernel(self, name, reps=20):
