@@ -9,6 +9,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <limits>
 
@@ -174,6 +175,16 @@ __global__ void k_apply_rows(const double* __restrict__ rs, int m, double* rhs, 
 __global__ void k_scale_vals(const int32_t* __restrict__ rowOf, const int32_t* __restrict__ colOf,
                              const double* __restrict__ rs, const double* __restrict__ cs, int64_t nnz, double* val) {
   GSTRIDE(p, nnz) val[p] = (val[p] / rs[rowOf[p]]) / cs[colOf[p]];
+}
+// the off-diagonal part N of a QP's Hessian, one thread per slot: v = (v / cs[row]) / cs[col], the two divisions of
+// applyScaling (pdlp_host.cpp) in its order; both factors are loaded before the first division
+__global__ void k_scale_qoff(const int32_t* __restrict__ rowOf, const int32_t* __restrict__ colOf,
+                             const double* __restrict__ cs, int64_t count, double* val) {
+  GSTRIDE(p, count) {
+    const double v = val[p];
+    const double fr = cs[rowOf[p]], fc = cs[colOf[p]];
+    val[p] = (v / fr) / fc;
+  }
 }
 // HiPDLP (scaling.cc): MODE 0 sqrt(max|a|) (Ruiz), 1 sqrt(sum|a|) (Pock-Chambolle, alpha 1), 2 sqrt(sqrt(sum a^2)) (L2);
 // zero or empty majors -> 1
@@ -412,6 +423,8 @@ int32_t gpuScalePasses(const ScaleOperands& o, hipStream_t s) {
       hipLaunchKernelGGL(k_major_reduce<false>, dim3(gridFor(m)), dim3(kT), 0, s, o.aBeg, o.aVal, m, rs.get());
     }
     hipLaunchKernelGGL(k_apply_cols, dim3(gridFor(n)), dim3(kT), 0, s, cs.get(), n, o.cost, o.lower, o.upper, o.colScale, o.qdiag);
+    if (o.qoffVal && o.qoffCount > 0)  // N follows the columns like qdiag; the factors come from the matrix alone
+      hipLaunchKernelGGL(k_scale_qoff, dim3(gridFor(o.qoffCount)), dim3(kT), 0, s, o.qoffRow, o.qoffCol, cs.get(), o.qoffCount, o.qoffVal);
     hipLaunchKernelGGL(k_apply_rows, dim3(gridFor(m)), dim3(kT), 0, s, rs.get(), m, o.rhs, o.rowScale);
     hipLaunchKernelGGL(k_scale_vals, dim3(gridFor(nnz)), dim3(kT), 0, s, o.cscIdx, o.cscCol, rs.get(), cs.get(), nnz, o.cscVal);
     hipLaunchKernelGGL(k_scale_vals, dim3(gridFor(nnz)), dim3(kT), 0, s, o.aMajor, o.aIdx, rs.get(), cs.get(), nnz, o.aVal);
@@ -569,22 +582,45 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
     PDLP_HIP(hipStreamSynchronize(s));
     return;
   }
-  // QP (cuPDLP-C form): the diagonal of Q, with the objective sense, rides along with the column scaling
+  // QP (cuPDLP-C form): the diagonal of Q, with the objective sense, rides along with the column scaling, and so does
+  // the off-diagonal part N.  The extraction stays on the host (integer work in the number of slots, and the one
+  // definition of N's entry order and of every refusal); its result is uploaded with a row index per slot.
   {
     std::vector<double> q;
-    if (D.keepHessianPattern) {
-      Compressed off;
-      extractHessianKept(P, D.sense, n, q, off, D.hmap);
-      if (!off.beg.empty())
-        throw std::runtime_error("pdlp_mi355x: this set-up path takes diagonal Hessians only (off-diagonal entries present)");
-    } else {
-      extractDiagonalHessian(P, D.sense, n, q);
-    }
+    Compressed off;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (D.keepHessianPattern) extractHessianKept(P, D.sense, n, q, off, D.hmap);
+    else extractHessian(P, D.sense, n, q, off);
+    const auto t1 = std::chrono::steady_clock::now();
+    D.secExtract = std::chrono::duration<double>(t1 - t0).count();
     if (!q.empty()) {
       D.qdiag.alloc((size_t)n);
       D.qdiag.upload(q.data(), (size_t)n, s);
-      PDLP_HIP(hipStreamSynchronize(s));  // q goes out of scope
-      if (D.keepHessianPattern) D.hQdiag0 = std::move(q);
+    }
+    std::vector<int32_t> offRow;
+    if (!off.beg.empty()) {
+      const size_t nOff = off.idx.size();
+      offRow.resize(nOff);
+      for (int32_t r = 0; r < n; ++r)
+        for (int32_t p = off.beg[r]; p < off.beg[r + 1]; ++p) offRow[p] = r;
+      D.N.nMajor = D.N.nMinor = n;
+      D.N.nnz = (int64_t)nOff;
+      D.N.beg.alloc((size_t)n + 1);
+      D.N.idx.alloc(nOff + 1);  // one pad element: the kernels clamp, never predicate, their loads
+      D.N.val.alloc(nOff + 1);
+      D.N.major.alloc(std::max<size_t>(nOff, 1));
+      D.N.idx.zero(s);
+      D.N.val.zero(s);
+      D.N.beg.upload(off.beg.data(), (size_t)n + 1, s);
+      D.N.idx.upload(off.idx.data(), nOff, s);
+      D.N.val.upload(off.val.data(), nOff, s);
+      D.N.major.upload(offRow.data(), nOff, s);
+    }
+    PDLP_HIP(hipStreamSynchronize(s));  // q, off and offRow go out of scope
+    D.secUploadHessian = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    if (D.keepHessianPattern && !q.empty()) {
+      D.hQdiag0 = std::move(q);
+      D.hQoff0 = std::move(off.val);
     }
   }
   if (keepM) {  // the unscaled formulated data: new matrix values change every factor, and un-scaling does not give these bits
@@ -602,8 +638,11 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
     o.cost = D.cost.get(); o.lower = D.lower.get(); o.upper = D.upper.get(); o.rhs = D.rhs.get();
     o.colScale = D.colScale.get(); o.rowScale = D.rowScale.get();
     o.qdiag = D.qdiag.size() ? D.qdiag.get() : nullptr;
+    if (D.N.nnz > 0) { o.qoffRow = D.N.major.get(); o.qoffCol = D.N.idx.get(); o.qoffVal = D.N.val.get(); o.qoffCount = D.N.nnz; }
     if (D.keepPasses) { o.csPass = D.csPass.get(); o.rsPass = D.rsPass.get(); }
+    const auto tp = std::chrono::steady_clock::now();
     const int32_t done = gpuScalePasses(o, s);
+    D.secPasses = std::chrono::duration<double>(std::chrono::steady_clock::now() - tp).count();
     if (D.keepPasses) D.nPass = done;
     D.scaled = true;
   }

@@ -60,6 +60,10 @@ struct DeviceProblem {
   DeviceCsrData At;  // columns, ascending row
   DeviceArray<double> cost, rhs, lower, upper, colScale, rowScale;
   DeviceArray<double> qdiag;      // QP only (cuPDLP-C form): diagonal of Q with the sense, scaled with the columns
+  // QP whose Hessian has an off-diagonal part (cuPDLP-C form): N = both triangles by rows with ascending column, in the
+  // order the host extraction defines (pdlp_host.hpp extractHessian / extractHessianKept), values scaled with the
+  // columns; nnz = 0: none.  idx / val end in the one pad element the layout builds expect.
+  DeviceCsrData N;
   DeviceArray<double> rowUpper;   // HiPDLP form only (rhs then holds the row lower bounds)
   DeviceArray<uint8_t> rowIsEq;   // HiPDLP form only, per permuted row
   // host copies of what the host side of the solver needs
@@ -77,11 +81,14 @@ struct DeviceProblem {
   bool keepMatrix = false;
   MatrixKeep keep;
   // PDLP_UPDATABLE_HESSIAN (set keepHessianPattern before gpuPrepare; cuPDLP-C form only): the Hessian is extracted with
-  // every slot kept (pdlp_host.hpp extractHessianKept); its assembly map and the unscaled diagonal stay on the host for
-  // the solver to take
+  // every slot kept (pdlp_host.hpp extractHessianKept); its assembly map, the unscaled diagonal and the unscaled values
+  // of N stay on the host for the solver to take
   bool keepHessianPattern = false;
   HessianMap hmap;
-  std::vector<double> hQdiag0;
+  std::vector<double> hQdiag0, hQoff0;
+  // wall seconds of three parts of gpuPrepare (cuPDLP-C form; stage "setup_seconds"): the Hessian's extraction on the
+  // host, the upload of its diagonal and of N, the scaling passes
+  double secExtract = 0, secUploadHessian = 0, secPasses = 0;
 };
 
 // Options of the HiPDLP form (pdlp_host.hpp formulateHipdlp / scaleHipdlp); nullptr = cuPDLP-C form.
@@ -110,6 +117,11 @@ struct ScaleOperands {
   double* aVal = nullptr;
   double *cost = nullptr, *lower = nullptr, *upper = nullptr, *rhs = nullptr, *colScale = nullptr, *rowScale = nullptr;
   double* qdiag = nullptr;                        // QP only, else nullptr
+  // the off-diagonal part N of a QP's Hessian: row, column and value of every slot; every pass gives each slot the two
+  // divisions (v / cs[row]) / cs[col] of applyScaling.  qoffVal == nullptr: no such part, nothing is launched for it
+  const int32_t *qoffRow = nullptr, *qoffCol = nullptr;
+  double* qoffVal = nullptr;
+  int64_t qoffCount = 0;
   double *csPass = nullptr, *rsPass = nullptr;    // updatable solvers: [11 n], [11 m], pass-major; else nullptr
 };
 int32_t gpuScalePasses(const ScaleOperands& o, hipStream_t s);  // returns the number of passes (11); synchronises

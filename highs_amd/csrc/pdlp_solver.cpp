@@ -485,10 +485,13 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   // PDLP_UPDATABLE_HESSIAN: every slot of the Hessian the caller passes is kept, so the structure follows the pattern
   const bool keepQPattern = (opt_.updatable & PDLP_UPDATABLE_HESSIAN) != 0;
   hasQoff_ = keepQPattern ? hessianHasOffDiagonalSlot(P) : hessianHasOffDiagonal(P);
-  if (hasQoff_) gpuSetup_ = false;  // the off-diagonal part of Q is scaled with the columns on the host (pdlp_host.cpp applyScaling)
+  // (one GPU: the off-diagonal part N of Q is scaled with the columns inside the device-side passes too and its layouts
+  // are built from the device arrays, pdlp_setup.hip k_scale_qoff; only its extraction is host work)
   // sharded: every rank still prepares the WHOLE problem (Ruiz scaling couples all rows and columns) but does it on
-  // its device and copies the result back once; only the row-block cut and the upload of its shard stay on the host
-  const bool shardedGpuSetup = sharded_ && gpuSetup_;
+  // its device and copies the result back once; only the row-block cut and the upload of its shard stay on the host.
+  // Not with an off-diagonal Hessian: neither downloadForm nor the shard cut on the device knows about N, so such a
+  // sharded QP is prepared on the host (pdlp_host.cpp applyScaling)
+  const bool shardedGpuSetup = sharded_ && gpuSetup_ && !hasQoff_;
   if (sharded_) gpuSetup_ = false;
   const bool doScale = !(opt_.features_off & PDLP_FEATURE_SCALING_OFF);
   updatable_ = opt_.updatable != 0 && !sharded_;  // (a sharded solver refuses updates: nothing to keep)
@@ -516,11 +519,13 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
     F_.rowScale = std::move(devProb.hRowScale);
     sumCost2_ = devProb.sumCost2;
     sumRhs2_ = devProb.sumRhs2;
+    setupParts_[0] = devProb.secExtract; setupParts_[1] = devProb.secUploadHessian; setupParts_[2] = devProb.secPasses;
     if (updatable_) keepForUpdates(&devProb);
     if (matrixUpdatable_) mk_ = std::move(devProb.keep);
     if (hessianUpdatable_) {
       F_.hmap = std::move(devProb.hmap);
-      keepHessian(devProb.hQdiag0, std::vector<double>());
+      keepHessian(devProb.hQdiag0, devProb.hQoff0);
+      devProb.hQdiag0 = devProb.hQoff0 = std::vector<double>();
     }
   } else if (shardedGpuSetup) {
     gpuPrepare(P, doScale, stream_, devProb);
@@ -811,7 +816,10 @@ void Solver::keepHessian(const std::vector<double>& qdiag0, const std::vector<do
 
 // dQ_ has just been built from tagged values (value of qoff slot k = k + 1): its value arrays become their source
 // indices, counted as finishMatrixKeep counts those of A and A', and are filled for the first time.
-void Solver::finishHessianKeep(const std::vector<double>& qoffScaled) {
+void Solver::finishHessianKeep(const std::vector<double>& qoffScaled) { finishHessianKeep(qoffScaled.data(), hipMemcpyHostToDevice); }
+// ... the scaled values in HBM already (device-side set-up)
+void Solver::finishHessianKeep(const DeviceArray<double>& qoffScaled) { finishHessianKeep(qoffScaled.get(), hipMemcpyDeviceToDevice); }
+void Solver::finishHessianKeep(const double* qoffScaled, hipMemcpyKind from) {
   const int64_t nOff = hk_.nOff;
   DeviceArray<unsigned long long> tagged;
   tagged.alloc(1);
@@ -825,7 +833,7 @@ void Solver::finishHessianKeep(const std::vector<double>& qoffScaled) {
   if (dQ_.useSlab) extract(dQ_.slabVal, srcQSlab_);
   unsigned long long found = 0;
   tagged.download(&found, 1, stream_);
-  hk_.qoffScaled.upload(qoffScaled.data(), (size_t)nOff, stream_);
+  if (nOff > 0) PDLP_HIP(hipMemcpyAsync(hk_.qoffScaled.get(), qoffScaled, sizeof(double) * (size_t)nOff, from, stream_));
   PDLP_HIP(hipStreamSynchronize(stream_));
   if ((int64_t)found != nOff)
     throw std::runtime_error("pdlp_mi355x: the layouts of a Hessian-updatable solver hold " + std::to_string(found) +
@@ -1070,7 +1078,28 @@ void Solver::uploadProblemFromDevice(DeviceProblem& D) {
   colScale_ = std::move(D.colScale); rowScale_ = std::move(D.rowScale);
   if (D.qdiag.size()) {
     qdiag_ = std::move(D.qdiag);
-    log(1, "Quadratic objective (diagonal Hessian): proximal primal step\n");
+    if (D.N.nnz == 0) log(1, "Quadratic objective (diagonal Hessian): proximal primal step\n");
+  }
+  if (D.N.nnz > 0) {
+    // N's layouts from its device arrays, at the width the rule gives: no timed width search (the width changes no sum, and
+    // N's launch is not the dominant one)
+    const int64_t nOff = D.N.nnz;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (hessianUpdatable_) {  // values that name their slot, as for A and A'; the scaled ones go to hk_.qoffScaled
+      DeviceArray<double> scaled;
+      scaled.alloc((size_t)nOff);
+      PDLP_HIP(hipMemcpyAsync(scaled.get(), D.N.val.get(), sizeof(double) * (size_t)nOff, hipMemcpyDeviceToDevice, stream_));
+      launchTagValues(D.N.val.get(), nOff, stream_);
+      dQ_.buildFromDevice(D.N, sw_, stream_);
+      finishHessianKeep(scaled);
+    } else {
+      dQ_.buildFromDevice(D.N, sw_, stream_);
+    }
+    D.N = DeviceCsrData();
+    PDLP_HIP(hipStreamSynchronize(stream_));
+    setupParts_[3] = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    log(1, "Quadratic objective (%lld off-diagonal Hessian entries): proximal step on the diagonal, explicit Q x term for the rest\n",
+        (long long)nOff);
   }
   allocIterates();
 }
@@ -2405,6 +2434,11 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     // sumRhs2, nEqs, n0, scaled}, then [8] 1 = formulated, scaled and laid out on the device (pdlp_setup.hip), 0 = on the host
     put(0, F_.normCost); put(1, F_.normRhs); put(2, F_.matNormInf); put(3, sumCost2_); put(4, sumRhs2_);
     put(5, (double)F_.nEqs); put(6, (double)F_.n0); put(7, F_.scaled ? 1.0 : 0.0); put(8, gpuSetup_ ? 1.0 : 0.0);
+  } else if (name == "setup_seconds") {  // launches nothing: wall seconds of parts of a device-side set-up — the Hessian's extraction on
+    // the host, the upload of its diagonal and of N, the scaling passes, N's layout build (zeros after a host set-up) — and
+    // [4] the whole create
+    for (int k = 0; k < 4; ++k) put(k, setupParts_[k]);
+    put(4, setupSeconds_);
   } else if (name == "trial_launches") {  // kernels per trial step of the hot loop (2 = fused decision + primal step)
     // mesh: 9 with single-block wait kernels, 7 with consumers that wait themselves, 5 with an exchange per launch
     // (fusedWait 0 / 1 / 2)

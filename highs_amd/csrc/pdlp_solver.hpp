@@ -219,7 +219,9 @@ class Solver : public SolverBase {
   // Hessian-updatable solvers (pdlp_update.hpp): the assembly map and the unscaled Hessian into hk_; dQ_'s source indices
   // out of its tagged build and the first refill; the parts of an update
   void keepHessian(const std::vector<double>& qdiag0, const std::vector<double>& qoff0);
-  void finishHessianKeep(const std::vector<double>& qoffScaled);
+  void finishHessianKeep(const std::vector<double>& qoffScaled);  // host set-up: the scaled values of N from the form
+  void finishHessianKeep(const DeviceArray<double>& qoffScaled);  // device-side set-up: device to device
+  void finishHessianKeep(const double* qoffScaled, hipMemcpyKind from);
   void refillHessian();
   void stageHessian(const double* qValue);
   void applyHessian(bool assemble, bool replayDiag);
@@ -295,6 +297,9 @@ class Solver : public SolverBase {
   int32_t rank_ = 0, world_ = 1, r0_ = 0, r1_ = 0, mLoc_ = 0;
   Comm* comm_ = nullptr;
   bool gpuSetup_ = true;   // formulate/scale/transpose/slab layout on the device (pdlp_setup.hip)
+  // device-side set-up: wall seconds of the Hessian's host extraction, its upload, the scaling passes and N's layout build
+  // (stage "setup_seconds"; zeros after a host set-up)
+  double setupParts_[4] = {};
   double sumCost2_ = 0, sumRhs2_ = 0;  // left-to-right sums of the scaled c, b
   bool sharded_ = false;  // row-block sharded kernel sequence (world > 1, or forced for testing)
   bool shardOnDevice_ = false;  // sharded + device-side set-up: the rank's shard is cut on the device (uploadShardFromDevice)
