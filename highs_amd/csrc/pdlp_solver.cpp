@@ -1441,6 +1441,8 @@ void Solver::reset() {
   pFeasLR_ = dFeasLR_ = gapLR_ = pFeasLC_ = dFeasLC_ = gapLC_ = 0.0;
   nRestarts_ = 0;
   nChecks_ = 0;
+  lastRestartKind_ = 0;
+  lastCheckIter_ = -1;
   termCode_ = PDLP_TERM_TIMELIMIT_OR_ITERLIMIT;
   termIterate_ = 0;
 }
@@ -1750,15 +1752,15 @@ bool Solver::checkInfeasibility() {  // cupdlp_solver.c:710-795
 
 // PDHG_Restart_Iterate_GPU (cupdlp_proj.c:88-148) with PDHG_Check_Restart_GPU
 // (cupdlp_restart.c:3-124) and PDHG_Compute_Step_Size_Ratio (cupdlp_step.c:147-176).
-void Solver::restartIterate() {
-  if (!restartOn_) return;
+int Solver::restartIterate() {
+  if (!restartOn_) return 0;
   DevState& s = *hostState_;
   auto score = [](double beta, double p, double d, double g) { return std::sqrt(beta * p * p + d * d / beta + g * g); };
   const int32_t it = s.nIter;
   if (it == iLastRestartIter_) {
     pFeasLR_ = cur_.pFeas; dFeasLR_ = cur_.dFeas; gapLR_ = cur_.gap;
     pFeasLC_ = cur_.pFeas; dFeasLC_ = cur_.dFeas; gapLC_ = cur_.gap;
-    return;
+    return 0;
   }
   const double muCur = score(s.beta, cur_.pFeas, cur_.dFeas, cur_.gap);
   const double muAvg = score(s.beta, avg_.pFeas, avg_.dFeas, avg_.gap);
@@ -1778,7 +1780,7 @@ void Solver::restartIterate() {
   }
   const Residuals& cand = toCurrent ? cur_ : avg_;
   pFeasLC_ = cand.pFeas; dFeasLC_ = cand.dFeas; gapLC_ = cand.gap;
-  if (!restart) return;
+  if (!restart) return 0;
 
   const int c = s.cur;
   const int32_t n = F_.n;
@@ -1825,6 +1827,7 @@ void Solver::restartIterate() {
   log(2, "Restart at iter %d to %s: beta = %g\n", it, toCurrent ? "current" : "average", s.beta);
   // The reference recomputes the residuals here (cupdlp_proj.c:145); the values
   // are overwritten by the next check before anything reads them, so we don't.
+  return toCurrent ? 1 : 2;
 }
 
 // One line of the iteration log (the reference prints every 100th check, the last iteration and at the time limit).
@@ -1881,6 +1884,7 @@ void Solver::downloadCtl() {
   pFeasLR_ = c.pFeasLR; dFeasLR_ = c.dFeasLR; gapLR_ = c.gapLR;
   pFeasLC_ = c.pFeasLC; dFeasLC_ = c.dFeasLC; gapLC_ = c.gapLC;
   iLastRestartIter_ = c.iLastRestartIter; nRestarts_ = c.nRestarts; nChecks_ = c.nChecks;
+  lastRestartKind_ = c.restartKind; lastCheckIter_ = c.lastCheckIter;
   if (c.terminated) { termCode_ = c.termCode; termIterate_ = c.termIterate; }
 }
 
@@ -2149,7 +2153,8 @@ void Solver::doSolve(bool terminate, int32_t target) {
       if (timeUp) { termCode_ = PDLP_TERM_TIMELIMIT_OR_ITERLIMIT; break; }
       if (it >= iterLim - 1) { termCode_ = PDLP_TERM_TIMELIMIT_OR_ITERLIMIT; break; }
     }
-    restartIterate();
+    lastRestartKind_ = restartIterate();
+    lastCheckIter_ = it;
     int64_t halt = nextCheckIter(it);
     if (!terminate && halt > iterLim) halt = iterLim;
     s.haltIter = (int32_t)halt;
@@ -2302,6 +2307,8 @@ std::pair<double*, int64_t> Solver::lookup(const std::string& name) {
   if (name == "aty_avg") return {atyAvg_.get(), n};
   if (name == "x_sum") return {xSum_.get(), n};
   if (name == "y_sum") return {ySum_.get(), m};
+  if (name == "x_last") return {xLast_.get(), n};  // the iterate of the last restart (xLastRestart, yLastRestart)
+  if (name == "y_last") return {yLast_.get(), m};
   if (name == "cost") return {cost_.get(), n};
   if (name == "rhs") return {rhs_.get(), m};
   if (name == "lower") return {lower_.get(), n};
@@ -2341,6 +2348,21 @@ void Solver::setVector(const std::string& name, const double* host, int64_t len)
     s.tau = host[0]; s.sigma = host[1]; s.beta = host[2];
     s.eta = std::sqrt(s.tau * s.sigma);
     s.primalStep = s.tau; s.dualStep = s.sigma;
+    pushState();
+    return;
+  }
+  if (name == "restart_memory") {  // {iLastRestartIter, pFeasLR, dFeasLR, gapLR, pFeasLC, dFeasLC, gapLC}: the host's mirrors, which
+    // every upload of the control record (the head of a device-driven loop, check_device) and restartIterate start from
+    if (len != 7) throw std::runtime_error("restart_memory needs iLastRestartIter and the six numbers of the last restart and candidate");
+    iLastRestartIter_ = (int32_t)host[0];
+    pFeasLR_ = host[1]; dFeasLR_ = host[2]; gapLR_ = host[3];
+    pFeasLC_ = host[4]; dFeasLC_ = host[5]; gapLC_ = host[6];
+    return;
+  }
+  if (name == "step_sums") {  // {sumPrimalStep, sumDualStep, avgW, avgWx}: the weights of the running sums
+    if (len != 4) throw std::runtime_error("step_sums needs sumPrimalStep, sumDualStep, avgW, avgWx");
+    DevState& s = *hostState_;
+    s.sumPrimalStep = host[0]; s.sumDualStep = host[1]; s.avgW = host[2]; s.avgWx = host[3];
     pushState();
     return;
   }
@@ -2502,6 +2524,8 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     // uses (enqueueCheckDevice): the fixed-work loop's control record with target nIter + 1 and restarts off, so that no
     // vector is rewritten but by the flush of the pending averages; [0] = the record's `ran`.  Never forced: an iteration
     // that is not on the schedule is refused.  A reset() restores everything this touches.
+    // out[0] == 1 on entry: restarts stay as the solver has them (the check may rewrite the iterate, as in a solve).
+    const bool allowRestart = out && cap >= 1 && out[0] == 1.0;
     if (!devCheck_ || sharded_) throw std::runtime_error("check_device: the checks of this solver are not driven by one device");
     DevState& s = *hostState_;
     const int32_t it = s.nIter;
@@ -2511,7 +2535,7 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     {
       BarrierRound round{*this, beginBarrierRound()};
       const bool restartWas = restartOn_;
-      restartOn_ = false;
+      if (!allowRestart) restartOn_ = false;
       uploadCtl(false, (int64_t)it + 1);
       restartOn_ = restartWas;
       s.haltIter = it;
@@ -2525,6 +2549,29 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     downloadCtl();
     checkSeen_ = checkSeq_;
     put(0, (double)rec->ran);
+  } else if (name == "check_host") {  // the host-driven twin of check_device with restarts allowed: one check of the present state as
+    // the fixed-work loop of doSolve with target nIter + 1 runs it (computeAverage, computeResiduals, restartIterate, the next
+    // halt, the state pushed).  Never forced either.
+    if (sharded_) throw std::runtime_error("check_host: not on a sharded solver");
+    DevState& s = *hostState_;
+    const int32_t it = s.nIter;
+    if (!(it < 10 || it % checkInterval() == 0))
+      throw std::runtime_error("check_host: iteration " + std::to_string(it) + " is not a check iteration");
+    computeAverage();
+    computeResiduals();
+    ++nChecks_;
+    lastRestartKind_ = restartIterate();
+    lastCheckIter_ = it;
+    s.haltIter = (int32_t)std::min<int64_t>(nextCheckIter(it), (int64_t)it + 1);
+    s.halted = 0;
+    pushState(false);
+    put(0, 1.0);
+  } else if (name == "restart_state") {  // launches nothing: the restart bookkeeping as the last check left it, from the host's mirrors
+    const DevState& s = *hostState_;
+    const double v[16] = {(double)lastRestartKind_, (double)nRestarts_, (double)iLastRestartIter_, pFeasLR_, dFeasLR_, gapLR_, pFeasLC_,
+                          dFeasLC_, gapLC_, s.sumPrimalStep, s.sumDualStep, s.avgW, s.avgWx, (double)s.haltIter, (double)nChecks_,
+                          (double)lastCheckIter_};
+    for (int k = 0; k < 16; ++k) put(k, v[k]);
   } else {
     throw std::runtime_error("unknown stage: " + name);
   }

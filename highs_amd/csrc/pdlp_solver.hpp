@@ -256,7 +256,7 @@ class Solver : public SolverBase {
   void computeResiduals();
   bool checkTermination(const Residuals& r) const;
   bool checkInfeasibility();
-  void restartIterate();
+  int restartIterate();  // 0: no restart, 1: to the current iterate, 2: to the average
   int32_t checkInterval() const { return opt_.check_interval > 0 ? opt_.check_interval : kReleaseInterval; }
   int32_t nextCheckIter(int32_t it) const;
   void checkStepSearch(int32_t iterBefore, int32_t trialsBefore);  // throws once 50 stops in a row have accepted no trial
@@ -448,6 +448,7 @@ class Solver : public SolverBase {
   Residuals cur_, avg_;
   double pFeasLR_ = 0, dFeasLR_ = 0, gapLR_ = 0, pFeasLC_ = 0, dFeasLC_ = 0, gapLC_ = 0;
   int32_t iLastRestartIter_ = 0, nRestarts_ = 0, nChecks_ = 0;
+  int32_t lastRestartKind_ = 0, lastCheckIter_ = -1;  // of the last check, host- or device-driven (stage "restart_state")
   int32_t termCode_ = PDLP_TERM_TIMELIMIT_OR_ITERLIMIT, termIterate_ = 0;
   bool adaptive_ = true, restartOn_ = true;
   double feasTol_ = 1e-8;

@@ -271,16 +271,29 @@ def test_derived_numbers_at_the_fallbacks(state, form, monkeypatch):
 # ---- the test stage itself: nothing outlives a reset ------------------------------------------------------------------------
 @pytest.mark.parametrize("form", ["one", "seq"])
 def test_a_reset_behind_check_device_restores_everything(form, monkeypatch):
-    """check_device on a planted state, reset(), 80 iterations: the iterates, step sizes and counters of a solver that never
-    ran the stage."""
+    """check_device on a planted state — then, with a planted memory of the last restart, planted weights of the running sums
+    and planted x_last / y_last, the check with restarts allowed (it restarts: iteration 0 is not iLastRestartIter = -5) and
+    its host-driven twin check_host — reset(), 80 iterations: the iterates, step sizes, counters and restart bookkeeping of a
+    solver that never ran a stage."""
     lp = _lp("255x257", "real")
     a, b = _create(lp, form, True, monkeypatch), _create(lp, form, True, monkeypatch)
-    K.plant(a, "real", np.random.default_rng(14))
+    rng = np.random.default_rng(14)
+    K.plant(a, "real", rng)
     assert a.stage("check_device", 1)[0] == 1.0
+    a.set("x_last", rng.standard_normal(a.n)); a.set("y_last", rng.standard_normal(a.m))
+    a.set("step_sums", [2.0, 3.0, 0.5, 0.25])
+    a.set("restart_memory", [-5, 1.0, 2.0, 3.0, 4.0, 5.0, 6.0])
+    assert a.stage("check_device", 1, init=[1])[0] == 1.0
+    rs = a.stage("restart_state", 16)
+    assert rs[0] in (1.0, 2.0) and rs[1] == 1.0 and rs[2] == 0.0 and rs[9] == rs[10] == 0.0 and not np.any(a.get("x_sum", a.n))
+    a.set("restart_memory", [-5, 1.0, 2.0, 3.0, 4.0, 5.0, 6.0])
+    assert a.stage("check_host", 1)[0] == 1.0 and a.stage("restart_state", 16)[1] == 2.0
     a.reset()
+    assert np.array_equal(a.stage("restart_state", 16), b.stage("restart_state", 16))
     sa, sb = a.iterate(80), b.iterate(80)
     assert (sa.iters, sa.trials, sa.checks, sa.restarts) == (sb.iters, sb.trials, sb.checks, sb.restarts) and sa.iters == 80
-    for k in ("x", "y", "ax", "aty", "x_sum", "y_sum", "steps"):
-        length = 8 if k == "steps" else a.m if k in ("y", "ax", "y_sum") else a.n
+    for k in ("x", "y", "ax", "aty", "x_sum", "y_sum", "x_last", "y_last", "steps"):
+        length = 8 if k == "steps" else a.m if k in ("y", "ax", "y_sum", "y_last") else a.n
         assert np.array_equal(a.get(k, length), b.get(k, length)), k
+    assert np.array_equal(a.stage("restart_state", 16), b.stage("restart_state", 16))
     a.close(); b.close()
