@@ -632,6 +632,24 @@ void pdlp_mi355x_free_stream_plan(pdlp_stream_plan_t* o) {
   memset(o, 0, sizeof(*o));
 }
 
+// TEST HOOK, not part of the public header: the rule that decides whether a HiPDLP solver runs the steps 2..40 of a block as
+// one persistent launch (pdlp_halpern_small.hpp halpernSmallReason — the function HalpernSolver calls), on shapes given by
+// hand.  shape[11]: blocks of A, blocks of A', chunk of A, chunk of A', use_slab, long-major tasks, long-major contribution
+// groups, sharded, profile mode, switch on, resident workgroups.  *reason: 0 persistent, else why not; *grid: the launch's
+// working workgroups; *mode: 1 XCD-local, 0 agent scope (meaningful where *reason is 0).
+int pdlp_mi355x_host_hipdlp_small_rule(const int32_t* shape, int32_t xcd_local_allowed, int32_t* reason, int32_t* grid, int32_t* mode) {
+  return guarded([&] {
+    if (!shape || !reason || !grid || !mode) throw std::runtime_error("null argument");
+    pdlp::HalpernSmallShape s{};
+    s.blocksA = shape[0]; s.blocksAt = shape[1]; s.chunkA = shape[2]; s.chunkAt = shape[3]; s.useSlab = shape[4];
+    s.longTasks = shape[5]; s.longContrib = shape[6]; s.sharded = shape[7]; s.profile = shape[8]; s.switchOn = shape[9];
+    s.resident = shape[10];
+    *reason = pdlp::halpernSmallReason(s);
+    *grid = pdlp::halpernSmallGrid(s);
+    *mode = pdlp::halpernSmallMode(*grid, xcd_local_allowed != 0);
+  });
+}
+
 // TEST HOOK, not part of the public header (no product code calls it): what a solver holds of operand `which` (0: A by rows,
 // 1: A' by columns) after its set-up, on the host or on the device — downloaded as it lies in HBM, with no launch and no
 // change of state.  Stream layout (use_slab = 0): beg / idx / val are the operand's CSR, block_beg its work blocks

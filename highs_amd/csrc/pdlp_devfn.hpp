@@ -421,6 +421,73 @@ __device__ __forceinline__ void hierBarrier(const HierBar& h, unsigned long long
   }
 }
 
+// ---- what the persistent launches share (pdlp_small.hip: the trial loop; pdlp_halpern_small.hip: HiPDLP's step loop) ----
+// (inside a launch that has passed its roll call a wait can only fail on a defect: the timeout raises the flag word,
+// which the decision phase turns into commError = 1)
+template <bool LOCAL>
+__device__ __forceinline__ void arrive(unsigned long long* bar, int lb, int nBlocks, unsigned long long epoch, unsigned long long limit) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its stores (write-through, or into the shared L2) ...
+  __syncthreads();                                    // ... before the block's arrival word is written
+  if (threadIdx.x < kWave) (void)gridBarrier<LOCAL>(bar, lb, nBlocks, epoch, (int)threadIdx.x, limit);
+  __syncthreads();
+}
+// the same through the XCD-hierarchical barrier (k-th barrier of the launch)
+__device__ __forceinline__ __attribute__((unused)) void arriveHier(const HierBar& h, unsigned long long k) {
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x < kWave) hierBarrier(h, k, (int)threadIdx.x);
+  __syncthreads();
+}
+// accesses to the vectors that change during the launch: agent scope on all XCDs, or L2-coherent on one XCD
+template <bool LOCAL>
+__device__ __forceinline__ double ldM(const double* p) { return LOCAL ? ldStream(p) : ldAgent(p); }
+template <bool LOCAL>
+__device__ __forceinline__ void stM(double* p, double v) { if (LOCAL) *p = v; else stAgent(p, v); }
+
+// The work block a workgroup owns in one operand, loaded ONCE per launch: a persistent workgroup runs the same
+// block of A and of A' in every trial, and the matrix never changes — entries, values and the bookkeeping of the
+// lane's first major stay in registers; a trial then only gathers, adds and stores.
+template <int CHUNK>
+struct OwnBlock {
+  static constexpr int kPer = CHUNK / kSpmvThreads;
+  int r0 = 0, r1 = 0, p0 = 0, cnt = 0, qb = 0, qe = 0, slot_ = 0;
+  int32_t ci[kPer];
+  double va[kPer];
+  // primal step inside phase A (small blocks, two entries per lane): cost, bounds (and the diagonal of Q) of every entry's column
+  static constexpr bool kKeepPrimal = kPer <= 2;
+  double pc[kKeepPrimal ? kPer : 1], pl[kKeepPrimal ? kPer : 1], pu[kKeepPrimal ? kPer : 1], pq[kKeepPrimal ? kPer : 1];
+  double fixed = 0.0;  // rhs of the lane's first row (phase A)
+  bool have = false;
+  __device__ __forceinline__ void loadPrimal(const IterVecs& v) {
+    if (kKeepPrimal) {
+#pragma unroll
+      for (int k = 0; k < kPer; ++k) {
+        pc[k] = v.cost[ci[k]]; pl[k] = v.lower[ci[k]]; pu[k] = v.upper[ci[k]]; pq[k] = v.qdiag ? v.qdiag[ci[k]] : 0.0;
+      }
+    }
+  }
+  __device__ __forceinline__ void load(const SpmvMat& M, int blk, bool dual, const double* rhs) {
+    have = true;
+    slot_ = M.partOffset + blk;
+    const int4 bb = *reinterpret_cast<const int4*>(M.blockBeg + 4 * blk);  // (first major, end major, first entry, end entry)
+    r0 = bb.x; r1 = bb.y; p0 = bb.z; cnt = bb.w - bb.z;
+    const int tid = threadIdx.x;
+    const int rFirst = r0 + tid;
+    const int rr = rFirst < r1 ? rFirst : r1 - 1;
+    qb = M.beg[rr] - p0;
+    qe = M.beg[rr + 1] - p0;
+    if (dual) fixed = rhs[rr];
+    const int last = cnt > 0 ? cnt - 1 : 0;  // idx/val carry one pad element
+#pragma unroll
+    for (int k = 0; k < kPer; ++k) {
+      const int q = tid + k * kSpmvThreads;
+      const int qq = q < last ? q : last;
+      ci[k] = M.idx[p0 + qq];
+      va[k] = M.val[p0 + qq];
+    }
+  }
+};
+
 // Epilogue operands that do not depend on the SpMV result.
 struct Pre { double a, b, c, d, e; };
 
@@ -512,7 +579,21 @@ __device__ __forceinline__ void trialSums(const double* __restrict__ partDY, int
   trialSumsT<0>(partDY, nDY, partDX, partInter, nDX, scratch, dY2, dX2, inter, partQ, nQ, qint);
 }
 
+// Where the HiPDLP step puts its results.  The arithmetic below exists ONCE; the two launch forms differ only here.
+// Plain launches (k_spmv / k_spmv_slab): the vectors touched once per kernel leave non-temporally, the two GATHERED ones
+// (reflected x, y_current) with ordinary stores.  Inside the persistent launch of pdlp_halpern_small.hip every vector
+// written by the launch goes through the loop's access policy stM (HalpernIoLoop).
+struct HalpernIoPlain {
+  static __device__ __forceinline__ void stream(double* p, double v) { stStream(p, v); }
+  static __device__ __forceinline__ void gathered(double* p, double v) { *p = v; }
+};
+template <bool LOCAL>
+struct HalpernIoLoop {
+  static __device__ __forceinline__ void stream(double* p, double v) { stM<LOCAL>(p, v); }
+  static __device__ __forceinline__ void gathered(double* p, double v) { stM<LOCAL>(p, v); }
+};
 // HiPDLP step, column side (pdhg.cc:975-990 and :1008-1011): s = (A'y)_j.
+template <class IO = HalpernIoPlain>
 __device__ __forceinline__ __attribute__((unused)) void halpernPrimal(const HalpernVecs& h, int j, double s, const Pre& p, double tau,
                                               double rho, double w) {
   const double xc = p.a, cost = p.b, xa = p.c, l = p.d, u = p.e;
@@ -520,15 +601,16 @@ __device__ __forceinline__ __attribute__((unused)) void halpernPrimal(const Halp
   const double t = (u < temp) ? u : temp;  // std::min(temp, u)
   const double proj = (l < t) ? t : l;     // std::max(l, .)   (linalg::projectBox)
   if (h.major) {
-    stStream(h.xn + j, proj);
-    stStream(h.slack + j, (proj - temp) / tau);
+    IO::stream(h.xn + j, proj);
+    IO::stream(h.slack + j, (proj - temp) / tau);
   }
   const double rx = 2.0 * proj - xc;
-  h.rx[j] = rx;  // gathered by the A x kernel: ordinary store
+  IO::gathered(h.rx + j, rx);  // gathered by the A x kernel: ordinary store
   const double blended = rho * rx + (1.0 - rho) * xc;
-  stStream(h.xc + j, w * blended + (1.0 - w) * xa);
+  IO::stream(h.xc + j, w * blended + (1.0 - w) * xa);
 }
 // HiPDLP step, row side (pdhg.cc:995-1006 and :1012-1015): s = (A reflected_x)_i.
+template <class IO = HalpernIoPlain>
 __device__ __forceinline__ __attribute__((unused)) void halpernDual(const HalpernVecs& h, int i, double s, const Pre& p, double sigma,
                                             double rho, double w) {
   const double yc = p.a, ya = p.b, rl = p.c, ru = p.d;
@@ -539,11 +621,11 @@ __device__ __forceinline__ __attribute__((unused)) void halpernDual(const Halper
   const double pd = (temp - proj) * sigma;
   const double ry = 2.0 * pd - yc;
   if (h.major) {
-    stStream(h.yn + i, pd);
-    stStream(h.ry + i, ry);
+    IO::stream(h.yn + i, pd);
+    IO::stream(h.ry + i, ry);
   }
   const double blended = rho * ry + (1.0 - rho) * yc;
-  h.yc[i] = w * blended + (1.0 - w) * ya;  // gathered by the A' y kernel: ordinary store
+  IO::gathered(h.yc + i, w * blended + (1.0 - w) * ya);  // gathered by the A' y kernel: ordinary store
 }
 
 

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <string>
 
 namespace pdlp {
 
@@ -163,22 +164,38 @@ void HalpernSolver::construct(const pdlp_problem_t& P, const void* id128) {
   // block -> XCD assignment of the two operands (scratch vectors: any input will do)
   tuneXcdMap(dA_, sw, tmpN_.get(), tmpM_.get(), stream_);
   tuneXcdMap(dAt_, sw, tmpM_.get(), tmpN_.get(), stream_);
+  // small LPs: the steps 2..40 of a block as ONE persistent launch (pdlp_halpern_small.hpp); PDLP_MI355X_PERSISTENT_HIPDLP=0
+  // keeps the two launches per step
+  smallSwitch_ = sw.persistentHipdlp != 0;
+  smallLocalAllowed_ = sw.xcdLocal != 0;
+  smallTimeoutMs_ = sw.barrierTimeoutMs;
+  if (!sharded_) {
+    smallResident_ = halpernSmallResident(opt_.device);
+    smallBar_.alloc(kHalpernSmallBarWords);
+    smallBar_.zero(stream_);
+  }
   reset();
   setupSeconds_ = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
-void HalpernSolver::release() noexcept {
+void HalpernSolver::dropGraphs() noexcept {
   if (graphExec_) (void)hipGraphExecDestroy(graphExec_);
   if (unitGraph_) (void)hipGraphExecDestroy(unitGraph_);
+  graphExec_ = nullptr; unitGraph_ = nullptr;
+  unitGraphPersistent_ = graphExecPersistent_ = false;
+}
+
+void HalpernSolver::release() noexcept {
+  dropGraphs();
   if (hostRing_) (void)hipHostFree(hostRing_);
-  unitGraph_ = nullptr; hostRing_ = nullptr;
+  hostRing_ = nullptr;
   for (hipEvent_t e : profEvents_) (void)hipEventDestroy(e);
   profEvents_.clear();
   if (hostState_) (void)hipHostFree(hostState_);
   if (hostStats_) (void)hipHostFree(hostStats_);
   delete mesh_;
   if (stream_) (void)hipStreamDestroy(stream_);
-  graphExec_ = nullptr; hostState_ = nullptr; hostStats_ = nullptr; stream_ = nullptr; mesh_ = nullptr;
+  hostState_ = nullptr; hostStats_ = nullptr; stream_ = nullptr; mesh_ = nullptr;
 }
 
 HalpernSolver::~HalpernSolver() { release(); }
@@ -368,10 +385,74 @@ void HalpernSolver::profCollect() {
   profQueued_ = 0;
 }
 
+// What the qualification rule of the persistent launch looks at (pdlp_halpern_small.hpp)
+HalpernSmallShape HalpernSolver::smallShape() const {
+  const MatView A = dA_.view(), At = dAt_.view();
+  HalpernSmallShape s{};
+  s.blocksA = A.csr.nBlocks; s.blocksAt = At.csr.nBlocks; s.chunkA = A.csr.chunk; s.chunkAt = At.csr.chunk;
+  s.useSlab = A.useSlab || At.useSlab ? 1 : 0;
+  s.longTasks = A.lng.nTasks + At.lng.nTasks;
+  s.longContrib = A.lng.contrib != nullptr || At.lng.contrib != nullptr ? 1 : 0;
+  s.sharded = sharded_ ? 1 : 0; s.profile = profile_ ? 1 : 0; s.switchOn = smallSwitch_ ? 1 : 0;
+  s.resident = smallResident_;
+  return s;
+}
+
+// The steps kFirst..kLast (the last one major) as ONE launch behind the memset of its barrier words.  Replayed from a graph
+// its arguments are frozen: what differs between launches comes from device memory (pdlp_halpern_small.hip).
+void HalpernSolver::enqueuePersistent(int32_t kFirst, int32_t kLast) {
+  HalpernSmallLaunch q;
+  q.A = dA_.view(); q.At = dAt_.view();
+  q.h = stepVecs(true, kLast);
+  q.st = dState_.get();
+  q.bar = smallBar_.get();
+  q.grid = halpernSmallGrid(smallShape());
+  q.kFirst = kFirst; q.kLast = kLast; q.timeoutMs = smallTimeoutMs_;
+  launchHalpernSmall(q, halpernSmallMode(q.grid, smallLocalAllowed_), stream_);
+  if (capturing_) capturedPersistent_ = true;
+  else ++persistentLaunches_;
+}
+
+void HalpernSolver::enqueueStepsFrom2(int32_t kLast) {
+  if (kLast < 2) return;
+  if (persistentReason() == kHsPersistent) { enqueuePersistent(2, kLast); return; }
+  for (int i = 2; i <= kLast - 1; ++i) enqueueStep(false, i);
+  enqueueStep(true, kLast);
+}
+
 // The steps 2..40 of a block (the hipGraph of the host-driven loop; part of the unit graph of the device-driven one)
-void HalpernSolver::enqueueMinorSteps() {
-  for (int i = 2; i <= kCheckInterval - 1; ++i) enqueueStep(false, i);
-  enqueueStep(true, kCheckInterval);
+void HalpernSolver::enqueueMinorSteps() { enqueueStepsFrom2(kCheckInterval); }
+
+// Host-queued blocks: has the persistent launch reported a stall?  (One 4-byte download; the device-driven loop reads the
+// word with the whole record.)
+bool HalpernSolver::pullStalled() {
+  PDLP_HIP(hipMemcpyAsync(&hostState_->stalled, &dState_.get()->stalled, sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+  PDLP_HIP(hipStreamSynchronize(stream_));
+  return hostState_->stalled != 0;
+}
+
+// The persistent launch could not run and has changed nothing (HalpernState::stalled, host copy).  2, its XCD placement
+// check or nt-load self-test failed: on in mode 0, agent-scope accesses on all XCDs.  3, its roll call failed (the device
+// is shared): plain launches for good.  1, a grid barrier failed behind a passed roll call: a defect, the solve ends in
+// an error.  The captured graphs hold the launch that stalled: dropped.  The caller pushes the state and queues the steps
+// again, which now take the other form.
+void HalpernSolver::recoverStall() {
+  HalpernState& H = *hostState_;
+  const int code = H.stalled;
+  if (code == 2 && smallLocalAllowed_) {
+    smallLocalAllowed_ = false;
+    log(1, "HiPDLP: the persistent launch's workgroups do not share one XCD; continuing with agent-scope accesses on all XCDs\n");
+  } else if (code == 3) {
+    smallResident_ = 0;
+    log(1, "HiPDLP: the persistent launch's workgroups were not resident within %d ms (is the device shared?); continuing with "
+           "two launches per step\n", smallTimeoutMs_);
+  } else {
+    throw std::runtime_error("pdlp_mi355x: a grid barrier of the persistent HiPDLP launch failed (stall code " + std::to_string(code) + ")");
+  }
+  ++barrierFallbacks_;
+  dropGraphs();
+  PDLP_HIP(hipMemsetAsync(smallBar_.get() + kHsForceWord, 0, sizeof(unsigned long long), stream_));  // (a test's request is served)
+  H.stalled = 0;
 }
 
 // One block of the main loop (pdhg.cc:578-641) in the HOST-driven loop: major step 1, [fixed-point error if a restart
@@ -386,12 +467,16 @@ void HalpernSolver::runBlock(bool fpeAfterFirst) {
     if (!graphExec_) {
       hipGraph_t graph = nullptr;
       PDLP_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
+      capturing_ = true; capturedPersistent_ = false;
       enqueueMinorSteps();
+      capturing_ = false;
       PDLP_HIP(hipStreamEndCapture(stream_, &graph));
       PDLP_HIP(hipGraphInstantiate(&graphExec_, graph, nullptr, nullptr, 0));
       (void)hipGraphDestroy(graph);
+      graphExecPersistent_ = capturedPersistent_;
     }
     PDLP_HIP(hipGraphLaunch(graphExec_, stream_));
+    if (graphExecPersistent_) ++persistentLaunches_;
   } else {
     enqueueMinorSteps();
   }
@@ -473,11 +558,15 @@ void HalpernSolver::noteRecord(const HalpernRecord& r) {
 // restart came before (gated), the check's statistics, the decision kernel and what it switches on (restart copies,
 // output copy).  Every kernel is a no-op once the loop has halted; the whole unit replays from ONE hipGraph.
 void HalpernSolver::enqueueUnit() {
+  enqueueStep(true, 1);
+  enqueueFpe(kSlotFpe0, &dState_.get()->runFpe0);
+  enqueueMinorSteps();
+  enqueueUnitTail();
+}
+// ... behind its 40 steps (also: behind the steps 2..40 queued again after a stalled persistent launch)
+void HalpernSolver::enqueueUnitTail() {
   HalpernState* ds = dState_.get();
   const int32_t n = F_.n, m = mLoc_;
-  enqueueStep(true, 1);
-  enqueueFpe(kSlotFpe0, &ds->runFpe0);
-  enqueueMinorSteps();
   enqueueFpe(kSlotFpe, &ds->run);
   enqueueCheck(xn_.get(), yn_.get(), true, &ds->run);
   enqueueDiff(&ds->run);
@@ -535,26 +624,44 @@ void HalpernSolver::doSolve(bool terminate, int64_t iterTarget) {
   if (device) {
     // ---- the device decides: whole units are queued ahead, the host reads the checks' lines ----
     pushState();
-    if (!unitGraph_ && useGraph_) {
-      hipGraph_t graph = nullptr;
-      PDLP_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
-      enqueueUnit();
-      PDLP_HIP(hipStreamEndCapture(stream_, &graph));
-      PDLP_HIP(hipGraphInstantiate(&unitGraph_, graph, nullptr, nullptr, 0));
-      (void)hipGraphDestroy(graph);
-    }
     int ahead = 1;
     for (;;) {
       if (terminate && timeUp()) { termStatus_ = 2; break; }
+      if (!unitGraph_ && useGraph_) {  // (again behind a stall: the unit then takes another form)
+        hipGraph_t graph = nullptr;
+        PDLP_HIP(hipStreamBeginCapture(stream_, hipStreamCaptureModeThreadLocal));
+        capturing_ = true; capturedPersistent_ = false;
+        enqueueUnit();
+        capturing_ = false;
+        PDLP_HIP(hipStreamEndCapture(stream_, &graph));
+        PDLP_HIP(hipGraphInstantiate(&unitGraph_, graph, nullptr, nullptr, 0));
+        (void)hipGraphDestroy(graph);
+        unitGraphPersistent_ = capturedPersistent_;
+      }
       const int32_t checksBefore = H.nChecks;
       const auto t0 = std::chrono::steady_clock::now();
       const int64_t unitsLeft = (limit - H.iters + kCheckInterval - 1) / kCheckInterval;
       const int units = (int)std::max<int64_t>(1, std::min<int64_t>(ahead, unitsLeft));
       for (int u = 0; u < units; ++u) {
-        if (unitGraph_) PDLP_HIP(hipGraphLaunch(unitGraph_, stream_));
-        else enqueueUnit();
+        if (unitGraph_) {
+          PDLP_HIP(hipGraphLaunch(unitGraph_, stream_));
+          if (unitGraphPersistent_) ++persistentLaunches_;
+        } else {
+          enqueueUnit();
+        }
       }
       pullState();
+      // A persistent launch stalled: it changed nothing, and neither did anything queued behind it — the unit's first step
+      // and the fixed-point error behind it are done, its steps 2..40 and its check are not.  Those are queued again, in
+      // the form the stall leaves (recoverStall), from the unchanged state.
+      while (H.stalled) {
+        recoverStall();
+        armState();
+        pushState();
+        enqueueMinorSteps();
+        enqueueUnitTail();
+        pullState();
+      }
       for (int32_t c = checksBefore; c < H.nChecks; ++c) noteRecord(hostRing_[c % kHalpernRing]);
       mirror();
       if (H.halted) {
@@ -581,6 +688,15 @@ void HalpernSolver::doSolve(bool terminate, int64_t iterTarget) {
     enqueueCheck(xn_.get(), yn_.get(), true, nullptr);
     enqueueDiff(nullptr);
     fetchStats(kStatOut);
+    while (persistentReason() == kHsPersistent && pullStalled()) {  // (as in the device-driven loop: the steps 2..40 and the check again)
+      recoverStall();
+      pushState();
+      enqueueMinorSteps();
+      enqueueFpe(kSlotFpe, nullptr);
+      enqueueCheck(xn_.get(), yn_.get(), true, nullptr);
+      enqueueDiff(nullptr);
+      fetchStats(kStatOut);
+    }
     if (mesh_) mesh_->verifyReplicated(rx_.get(), F_.n, stream_);  // the reflected x is the vector every rank holds in full
     const HalpernRecord r = halpernDecide(H, hostStats_);
     noteRecord(r);
@@ -754,6 +870,13 @@ void HalpernSolver::stage(const std::string& name, double* out, int32_t cap) {
     runBlock(false);
     enqueueFpe(kSlotFpe, nullptr);
     fetchStats(3);
+    while (persistentReason() == kHsPersistent && pullStalled()) {  // (the steps 2..40 again, in the form the stall leaves)
+      recoverStall();
+      pushState();
+      enqueueMinorSteps();
+      enqueueFpe(kSlotFpe, nullptr);
+      fetchStats(3);
+    }
     hostState_->fpe = halpernFpe(*hostState_, hostStats_ + kSlotFpe);
     put(0, hostState_->fpe);
   } else if (name == "steps") {  // out[0] = number of steps (1..40), the last one major: returns nothing
@@ -762,6 +885,46 @@ void HalpernSolver::stage(const std::string& name, double* out, int32_t cap) {
     armState();
     pushState();
     for (int i = 1; i <= k; ++i) enqueueStep(i == 1 || i == k, i);
+  } else if (name == "steps_persistent") {
+    // the contract of "steps": step 1 by the plain launches, the steps 2..k in ONE persistent launch, the last one major.
+    // A solver that does not (or no longer) qualify is an error here, never a quiet run through the plain launches.
+    const int k = out && cap > 0 ? (int)out[0] : kCheckInterval;
+    if (k < 1 || k > kCheckInterval) throw std::runtime_error("steps_persistent: 1..40");
+    if (persistentReason() != kHsPersistent)
+      throw std::runtime_error("steps_persistent: this solver keeps the plain launches (persistent_reason " + std::to_string(persistentReason()) + ")");
+    armState();
+    pushState();
+    enqueueStep(true, 1);
+    if (k >= 2) {
+      enqueuePersistent(2, k);
+      while (pullStalled()) {  // (a failed placement check: once more in mode 0; a failed roll call: the error above)
+        recoverStall();
+        if (persistentReason() != kHsPersistent) throw std::runtime_error("steps_persistent: the launch's workgroups were not resident at once");
+        pushState();
+        enqueuePersistent(2, k);
+      }
+    }
+  } else if (name == "stall_next_block") {
+    // TEST HOOK: the next persistent launch ends as one whose roll call (3) or XCD placement check (2) failed — it changes
+    // nothing and reports the code — so that the fall-back runs without any launch waiting for its timeout.
+    const int code = out && cap > 0 ? (int)out[0] : 0;
+    if (code != 2 && code != 3) throw std::runtime_error("stall_next_block: 2 (placement) or 3 (roll call)");
+    if (persistentReason() != kHsPersistent) throw std::runtime_error("stall_next_block: this solver keeps the plain launches");
+    if (code == 2 && halpernSmallMode(halpernSmallGrid(smallShape()), smallLocalAllowed_) != 1)
+      throw std::runtime_error("stall_next_block: no placement check outside the XCD-local mode");
+    const unsigned long long word = (unsigned long long)code;
+    PDLP_HIP(hipMemcpyAsync(smallBar_.get() + kHsForceWord, &word, sizeof(word), hipMemcpyHostToDevice, stream_));
+    PDLP_HIP(hipStreamSynchronize(stream_));
+  } else if (name == "persistent_launches") {
+    put(0, (double)persistentLaunches_);
+  } else if (name == "step_barriers") {  // grid barriers per Halpern step inside a block: 2 where its steps 2..40 are one launch
+    put(0, persistentReason() == kHsPersistent ? 2.0 : 0.0);
+  } else if (name == "barrier_fallbacks") {
+    put(0, (double)barrierFallbacks_);
+  } else if (name == "persistent_reason") {  // pdlp_halpern_small.hpp halpernSmallReason: 0 = persistent
+    put(0, (double)persistentReason());
+  } else if (name == "persistent_mode") {  // 1 XCD-local, 0 agent scope on all XCDs, -1 plain launches
+    put(0, persistentReason() == kHsPersistent ? (double)halpernSmallMode(halpernSmallGrid(smallShape()), smallLocalAllowed_) : -1.0);
   } else if (name == "mesh_phases") {  // {X, P, -} average wait in us, then the wait counts (since the last call)
     double us[3] = {0, 0, 0}, cnt[3] = {0, 0, 0};
     if (mesh_) mesh_->phaseStats(us, cnt, stream_);

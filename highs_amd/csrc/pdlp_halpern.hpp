@@ -3,7 +3,8 @@
 // step sizes from a power method, PID-controlled primal weight.  One Halpern step is TWO launches —
 // the A'y SpMV with the primal projection/reflection/blend as its epilogue, and the A x SpMV with
 // the dual ones — and a block of 40 steps replays from a hipGraph; the host only acts at the
-// reference's check iterations (every PDHG_CHECK_INTERVAL = 40 steps, pdhg.cc:32).
+// reference's check iterations (every PDHG_CHECK_INTERVAL = 40 steps, pdhg.cc:32).  On small LPs the
+// steps 2..40 of a block are ONE persistent launch instead of 78 (pdlp_halpern_small.hpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -11,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "pdlp_halpern_small.hpp"
 #include "pdlp_mesh.hpp"
 #include "pdlp_solver.hpp"
 
@@ -71,6 +73,14 @@ class HalpernSolver : public SolverBase {
   void armState();                             // host copy: the loop may run (gate words follow the state)
   void enqueueStep(bool major, int32_t kOff);
   void enqueueMinorSteps();                    // steps 2..40
+  void enqueueStepsFrom2(int32_t kLast);       // steps 2..kLast, the last one major: ONE persistent launch where the solver qualifies
+  void enqueuePersistent(int32_t kFirst, int32_t kLast);
+  void enqueueUnitTail();                      // a unit behind its steps: check + decision + gated copies
+  HalpernSmallShape smallShape() const;
+  int32_t persistentReason() const { return halpernSmallReason(smallShape()); }
+  bool pullStalled();                          // host-queued blocks: the device's `stalled` word -> host copy; true if set
+  void recoverStall();                         // stalled 2: on in mode 0; 3: plain launches for good; 1: throws
+  void dropGraphs() noexcept;
   void runBlock(bool fpeAfterFirst);           // steps 1..40 of one block (host-driven loop)
   void enqueueUnit();                          // block + check + decision + gated copies (device-driven loop)
   // gate (device word, nullptr = always): see pdlp_halpern.hpp launchHalpern*
@@ -122,6 +132,16 @@ class HalpernSolver : public SolverBase {
   Res res_;
   hipGraphExec_t graphExec_ = nullptr;
   bool useGraph_ = true;
+  // the persistent launch of the steps 2..40 (pdlp_halpern_small.hpp)
+  bool smallSwitch_ = true;        // PDLP_MI355X_PERSISTENT_HIPDLP
+  bool smallLocalAllowed_ = true;  // PDLP_MI355X_XCD_LOCAL (development), and no failed placement check so far
+  int32_t smallResident_ = 0;      // workgroups of the kernel the device holds at once (0 after a failed roll call: plain launches for good)
+  int32_t smallTimeoutMs_ = 1000;
+  DeviceArray<unsigned long long> smallBar_;
+  bool capturing_ = false, capturedPersistent_ = false;  // a stream capture is open / has taken a persistent launch
+  bool unitGraphPersistent_ = false, graphExecPersistent_ = false;
+  int64_t persistentLaunches_ = 0;  // persistent launches queued (replays of a captured one included)
+  int32_t barrierFallbacks_ = 0;
   // in-loop kernel timing (stage "profile_on"): HIP events around the two launches of every step
   bool profile_ = false;
   std::vector<hipEvent_t> profEvents_;

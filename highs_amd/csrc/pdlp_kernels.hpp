@@ -247,6 +247,12 @@ struct HalpernState {
   int32_t pid, terminate, nRestarts, nChecks;
   int32_t termStatus;
   int32_t fpe0Pending;  // the next block starts behind a restart (runFpe0 is this word while the loop runs, 0 once it has halted)
+  // The persistent launch of a block's steps 2..40 (pdlp_halpern_small.hpp) could not run or finish: 1 a grid barrier failed
+  // (an error), 2 its XCD placement check failed, 3 its roll call failed.  The launch that sets it also sets `halted` and
+  // clears the gate words run / runFpe0 / doRestart: everything still queued is a no-op, exactly as behind a halt, until
+  // the host has looked (HalpernSolver::recoverStall) and armed the state again.
+  int32_t stalled;
+  int32_t pad_;
 };
 // One line of the check, written by the device into pinned host memory (a ring): what the host logs and returns.
 struct HalpernRecord {

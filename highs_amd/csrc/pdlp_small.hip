@@ -89,71 +89,8 @@ struct SmallArgsQ : SmallArgs {
   int32_t xcdN;
 };
 
-// (inside a launch that has passed its roll call a wait can only fail on a defect: the timeout raises the flag word,
-// which the decision phase turns into commError = 1)
-template <bool LOCAL>
-__device__ __forceinline__ void arrive(unsigned long long* bar, int lb, int nBlocks, unsigned long long epoch, unsigned long long limit) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // every storing wave drains its stores (write-through, or into the shared L2) ...
-  __syncthreads();                                    // ... before the block's arrival word is written
-  if (threadIdx.x < kWave) (void)gridBarrier<LOCAL>(bar, lb, nBlocks, epoch, (int)threadIdx.x, limit);
-  __syncthreads();
-}
-// the same through the XCD-hierarchical barrier (k-th barrier of the launch)
-__device__ __forceinline__ void arriveHier(const HierBar& h, unsigned long long k) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x < kWave) hierBarrier(h, k, (int)threadIdx.x);
-  __syncthreads();
-}
-// accesses to the vectors that change during the launch: agent scope on all XCDs, or L2-coherent on one XCD
-template <bool LOCAL>
-__device__ __forceinline__ double ldM(const double* p) { return LOCAL ? ldStream(p) : ldAgent(p); }
-template <bool LOCAL>
-__device__ __forceinline__ void stM(double* p, double v) { if (LOCAL) *p = v; else stAgent(p, v); }
-
-// The work block a workgroup owns in one operand, loaded ONCE per launch: a persistent workgroup runs the same
-// block of A and of A' in every trial, and the matrix never changes — entries, values and the bookkeeping of the
-// lane's first major stay in registers; a trial then only gathers, adds and stores.
-template <int CHUNK>
-struct OwnBlock {
-  static constexpr int kPer = CHUNK / kSpmvThreads;
-  int r0 = 0, r1 = 0, p0 = 0, cnt = 0, qb = 0, qe = 0, slot_ = 0;
-  int32_t ci[kPer];
-  double va[kPer];
-  // primal step inside phase A (small blocks, two entries per lane): cost, bounds (and the diagonal of Q) of every entry's column
-  static constexpr bool kKeepPrimal = kPer <= 2;
-  double pc[kKeepPrimal ? kPer : 1], pl[kKeepPrimal ? kPer : 1], pu[kKeepPrimal ? kPer : 1], pq[kKeepPrimal ? kPer : 1];
-  double fixed = 0.0;  // rhs of the lane's first row (phase A)
-  bool have = false;
-  __device__ __forceinline__ void loadPrimal(const IterVecs& v) {
-    if (kKeepPrimal) {
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) {
-        pc[k] = v.cost[ci[k]]; pl[k] = v.lower[ci[k]]; pu[k] = v.upper[ci[k]]; pq[k] = v.qdiag ? v.qdiag[ci[k]] : 0.0;
-      }
-    }
-  }
-  __device__ __forceinline__ void load(const SpmvMat& M, int blk, bool dual, const double* rhs) {
-    have = true;
-    slot_ = M.partOffset + blk;
-    const int4 bb = *reinterpret_cast<const int4*>(M.blockBeg + 4 * blk);  // (first major, end major, first entry, end entry)
-    r0 = bb.x; r1 = bb.y; p0 = bb.z; cnt = bb.w - bb.z;
-    const int tid = threadIdx.x;
-    const int rFirst = r0 + tid;
-    const int rr = rFirst < r1 ? rFirst : r1 - 1;
-    qb = M.beg[rr] - p0;
-    qe = M.beg[rr + 1] - p0;
-    if (dual) fixed = rhs[rr];
-    const int last = cnt > 0 ? cnt - 1 : 0;  // idx/val carry one pad element
-#pragma unroll
-    for (int k = 0; k < kPer; ++k) {
-      const int q = tid + k * kSpmvThreads;
-      const int qq = q < last ? q : last;
-      ci[k] = M.idx[p0 + qq];
-      va[k] = M.val[p0 + qq];
-    }
-  }
-};
+// (arrive / arriveHier, the access policies ldM / stM and OwnBlock: pdlp_devfn.hpp — the HiPDLP loop of pdlp_halpern_small.hip
+// meets, reads, writes and holds its work blocks the same way)
 
 // One trial's pass over the owned block (same plan, lanes and sums as k_spmv's stream path) with the epilogue of
 // phase A (DUAL) or T.  Per-thread reduction partials are added to acc0 / acc1.

@@ -348,6 +348,7 @@ DevSwitches DevSwitches::fromEnv() {
   w.fused = num("PDLP_MI355X_FUSED", -1);
   w.persistent = num("PDLP_MI355X_PERSISTENT", -1);
   w.persistentQp = num("PDLP_MI355X_PERSISTENT_QP", -1);
+  w.persistentHipdlp = num("PDLP_MI355X_PERSISTENT_HIPDLP", -1);
   w.barrierTimeoutMs = num("PDLP_MI355X_BARRIER_TIMEOUT_MS", 1000);
   {
     const char* e = getenv("PDLP_MI355X_EXCHANGE");

@@ -32,6 +32,7 @@ struct DevSwitches {
   int constCached = -1;   // PDLP_MI355X_CONST_CACHED=0|1 (development): c, l, u of the primal step non-temporal / ordinary loads (default: by size)
   int fused = -1, persistent = -1, xcdLocal = -1, hierBarrier = -1, deviceCheck = -1, checkSmall = -1;
   int persistentQp = -1;  // PDLP_MI355X_PERSISTENT_QP=0: small QPs with off-diagonal Hessian entries keep their launches per trial (LPs, diagonal QPs: not read)
+  int persistentHipdlp = -1;  // PDLP_MI355X_PERSISTENT_HIPDLP=0: the HiPDLP path keeps its two launches per Halpern step on small LPs too
   int primalInA = -1;     // PDLP_MI355X_PRIMAL_IN_A: the persistent loop without its P phase (pdlp_small.hip PINA); -1 = where measured faster
   int barrierTimeoutMs = 1000;  // PDLP_MI355X_BARRIER_TIMEOUT_MS: how long a grid barrier / roll call waits for missing workgroups
   int fault = 0;          // PDLP_MI355X_FAULT (tests): 1 = the first persistent launch expects one workgroup too many,
