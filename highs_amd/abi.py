@@ -127,6 +127,18 @@ class PdlpUpdate(C.Structure):
     ]
 
 
+class PdlpVariant(C.Structure):
+    """pdlp_variant_t (include/pdlp_mi355x.h): one variant of pdlp_mi355x_batch_run_values; its size is checked against
+    pdlp_mi355x_variant_size()."""
+    _fields_ = [
+        ("a_value", c_f64p),
+        ("num_nz", C.c_int64),
+        ("q_value", c_f64p),
+        ("num_q_nz", C.c_int64),
+        ("u", PdlpUpdate),
+    ]
+
+
 # pdlp_session_info_t.path / .changed (include/pdlp_mi355x.h)
 SESSION_NONE, SESSION_CREATE, SESSION_UPDATE, SESSION_UPDATE_MATRIX, SESSION_UPDATE_VALUES, SESSION_ONE_SHOT = range(6)
 SESSION_PATH_NAME = {0: "none", 1: "create", 2: "update", 3: "update matrix", 4: "update values", 5: "one-shot"}
@@ -468,3 +480,22 @@ class UpdateHandle:
             put("start_row_value", start.get("row_value"))
             put("start_row_dual", start.get("row_dual"))
         self.struct = U
+
+
+class VariantHandle:
+    """Owns the numpy buffers a pdlp_variant_t points to: a_value / q_value (None = the values of the batch's problem) and
+    the arguments of UpdateHandle."""
+
+    def __init__(self, a_value=None, q_value=None, **update):
+        self.update = UpdateHandle(**update)
+        self.a_value = None if a_value is None else _f64(a_value)
+        self.q_value = None if q_value is None else _f64(q_value)
+        V = PdlpVariant()
+        if self.a_value is not None:
+            V.a_value = _ptr(self.a_value, c_f64p)
+            V.num_nz = self.a_value.size
+        if self.q_value is not None:
+            V.q_value = _ptr(self.q_value, c_f64p)
+            V.num_q_nz = self.q_value.size
+        V.u = self.update.struct
+        self.struct = V

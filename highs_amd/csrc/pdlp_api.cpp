@@ -798,6 +798,29 @@ int pdlp_mi355x_batch_run(pdlp_mi355x_batch_t* B, int32_t K, const pdlp_update_t
   });
 }
 
+int pdlp_mi355x_batch_run_values(pdlp_mi355x_batch_t* B, int32_t K, const pdlp_variant_t* v, pdlp_result_t* R) {
+  return guarded([&] {
+    if (!B || !B->impl) throw std::runtime_error("pdlp_mi355x_batch_run_values: null batch");
+    B->impl->runValues(K, v, R);
+  });
+}
+
+int64_t pdlp_mi355x_variant_size(void) { return sizeof(pdlp_variant_t); }
+
+// Test hook, not part of the public header: what pdlp_mi355x_batch_run_values refuses, for a batch created on P with opt,
+// before it looks at a matrix or Hessian value — no device call is made.
+int pdlp_mi355x_host_batch_variants_refusal(const pdlp_problem_t* P, const pdlp_params_t* opt, int32_t K, const pdlp_variant_t* v,
+                                            const pdlp_result_t* R) {
+  return guarded([&] {
+    if (!P || !opt) throw std::runtime_error("null argument");
+    pdlp::refuseBatchArguments(pdlp::kEntryBatchRunValues, K, v, R);
+    for (int32_t k = 0; k < K; ++k) {
+      const std::string why = pdlp::batchVariantRefusal(*P, *opt, v[k]);
+      if (!why.empty()) throw std::runtime_error("variant " + std::to_string(k) + ": " + why);
+    }
+  });
+}
+
 int pdlp_mi355x_batch_info(const pdlp_mi355x_batch_t* B, pdlp_batch_info_t* out) {
   return guarded([&] {
     if (!B || !B->impl || !out) throw std::runtime_error("pdlp_mi355x_batch_info: null argument");

@@ -20,9 +20,48 @@ BatchDriver::BatchDriver(std::vector<BatchLane*> lanes, BatchBackend* backend) :
 // pdlp_update_t.reserved: the variant's own iteration limit
 static int32_t iterLimitOf(const pdlp_update_t& u) { return u.reserved > 0 ? u.reserved : 0; }
 
-void BatchDriver::run(int32_t K, const pdlp_update_t* u, pdlp_result_t* R) {
-  if (K < 1) throw std::runtime_error("pdlp_mi355x_batch_run: K = " + std::to_string(K) + " variants (at least 1)");
-  if (!u || !R) throw std::runtime_error("pdlp_mi355x_batch_run: null argument");
+BaseData::BaseData(const pdlp_problem_t& P)
+    : cost(P.col_cost, P.col_cost + P.num_col), colLower(P.col_lower, P.col_lower + P.num_col),
+      colUpper(P.col_upper, P.col_upper + P.num_col), rowLower(P.row_lower, P.row_lower + P.num_row),
+      rowUpper(P.row_upper, P.row_upper + P.num_row), offset(P.offset) {
+  const int64_t nnz = P.num_col > 0 && P.a_start ? (int64_t)P.a_start[P.num_col] : 0;
+  if (nnz > 0 && P.a_value) aValue.assign(P.a_value, P.a_value + nnz);
+  const int64_t slots = P.q_dim > 0 && P.q_start && P.q_index && P.q_value ? (int64_t)P.q_start[P.q_dim] : 0;
+  if (slots > 0) qValue.assign(P.q_value, P.q_value + slots);
+}
+
+LaneUpdatePlan planLaneUpdate(const Variant& v, int differs, const BaseData& base) {
+  LaneUpdatePlan plan;
+  plan.v = v;
+  pdlp_update_t& u = plan.v.u;
+  int now = 0;
+  auto take = [&](const double*& field, const std::vector<double>& kept, int bit) {
+    if (field) now |= bit;
+    else if (differs & bit) field = kept.data();
+  };
+  take(u.col_cost, base.cost, kLaneCost);
+  take(u.col_lower, base.colLower, kLaneColLower);
+  take(u.col_upper, base.colUpper, kLaneColUpper);
+  if (u.row_lower) now |= kLaneRows;  // (given together: validated)
+  else if (differs & kLaneRows) { u.row_lower = base.rowLower.data(); u.row_upper = base.rowUpper.data(); }
+  if (u.has_offset) now |= kLaneOffset;
+  else if (differs & kLaneOffset) { u.has_offset = 1; u.offset = base.offset; }
+  take(plan.v.a_value, base.aValue, kLaneMatrix);
+  if (!(now & kLaneMatrix) && plan.v.a_value) plan.v.num_nz = (int64_t)base.aValue.size();
+  take(plan.v.q_value, base.qValue, kLaneHessian);
+  if (!(now & kLaneHessian) && plan.v.q_value) plan.v.num_q_nz = (int64_t)base.qValue.size();
+  plan.now = now;
+  plan.call = plan.v.q_value ? kCallUpdateValues : plan.v.a_value ? kCallUpdateMatrix : kCallUpdate;
+  return plan;
+}
+
+void refuseBatchArguments(const char* entry, int32_t K, const void* variants, const void* results) {
+  if (K < 1) throw std::runtime_error(std::string(entry) + ": K = " + std::to_string(K) + " variants (at least 1)");
+  if (!variants || !results) throw std::runtime_error(std::string(entry) + ": null argument");
+}
+
+void BatchDriver::run(int32_t K, const Variant* u, pdlp_result_t* R, const char* entry) {
+  refuseBatchArguments(entry, K, u, R);
   // all-or-nothing: every variant is validated before the first one changes a lane
   for (int32_t k = 0; k < K; ++k) {
     try {
@@ -51,15 +90,15 @@ void BatchDriver::run(int32_t K, const pdlp_update_t* u, pdlp_result_t* R) {
   info_.wall_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
-void BatchDriver::runSequential(int32_t first, int32_t K, const pdlp_update_t* u, pdlp_result_t* R) {
+void BatchDriver::runSequential(int32_t first, int32_t K, const Variant* u, pdlp_result_t* R) {
   for (int32_t k = first; k < K; ++k) {
-    lanes_[0]->setVariant(k, iterLimitOf(u[k]));
+    lanes_[0]->setVariant(k, iterLimitOf(u[k].u));
     lanes_[0]->update(u[k]);
     lanes_[0]->runAlone(&R[k]);
   }
 }
 
-void BatchDriver::runConcurrent(int32_t K, const pdlp_update_t* u, pdlp_result_t* R) {
+void BatchDriver::runConcurrent(int32_t K, const Variant* u, pdlp_result_t* R) {
   const int32_t nLanes = (int32_t)lanes_.size();
   std::vector<int32_t> variantOf((size_t)nLanes, -1);  // the variant a lane is solving, -1: none
   std::vector<char> out((size_t)nLanes, 0);            // the lane has left the concurrent set (the failure rule)
@@ -73,8 +112,15 @@ void BatchDriver::runConcurrent(int32_t K, const pdlp_update_t* u, pdlp_result_t
     for (int32_t l = 0; l < nLanes; ++l) {
       while (variantOf[l] < 0 && !out[l] && next < K) {
         const int32_t k = next++;
-        lanes_[l]->setVariant(k, iterLimitOf(u[k]));
+        lanes_[l]->setVariant(k, iterLimitOf(u[k].u));
         lanes_[l]->update(u[k]);
+        // A value update keeps every pattern, so the lane still qualifies; were it ever not to, its variant goes the way
+        // of the failure rule below: solved alone afterwards (the lane holds the variant), no shared launch for the lane.
+        if (hasValues(u[k]) && !lanes_[l]->sequentialReason().empty()) {
+          alone.emplace_back(l, k);
+          out[l] = 1;
+          break;
+        }
         lanes_[l]->begin();
         if (lanes_[l]->idle()) lanes_[l]->finish(&R[k]);  // (the iteration limit is reached before the first round)
         else { variantOf[l] = k; ran[l] = 1; }
@@ -124,7 +170,7 @@ void BatchDriver::runConcurrent(int32_t K, const pdlp_update_t* u, pdlp_result_t
   // every lane has failed with variants left: those run one after the other on a lane's own solver
   if (next < K) {
     for (int32_t k = next; k < K; ++k) {
-      lanes_[0]->setVariant(k, iterLimitOf(u[k]));
+      lanes_[0]->setVariant(k, iterLimitOf(u[k].u));
       lanes_[0]->update(u[k]);
       lanes_[0]->runAlone(&R[k]);
       ++info_.fallback_variants;

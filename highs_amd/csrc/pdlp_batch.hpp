@@ -7,6 +7,11 @@
 // halt are each lane's own, so the bits of every result are those of a solo update + run.  A lane whose variant has ended
 // takes the next one while the others carry on.  Everywhere else batch_run is a loop of update + run on lane 0.
 //
+// A variant (pdlp_variant_t) is new data and, through pdlp_mi355x_batch_run_values, new matrix and Hessian VALUES on P's
+// patterns; pdlp_mi355x_batch_run wraps each of its updates into a variant without values.  Value updates keep row order,
+// task plans, chunk sizes, the XCD map and the persistent loop, so whether the launches are shared depends on the pattern
+// and the options alone.
+//
 // The driver (BatchDriver) sees its lanes and the device only through the two interfaces below, so that it also runs
 // against canned lanes on a machine without a device.
 #pragma once
@@ -33,15 +38,41 @@ struct LaneUnit {
 
 enum LaneVerdict : int { kLaneGoOn = 0, kLaneOver = 1, kLaneFailed = 2 };
 
+using Variant = pdlp_variant_t;
+// new values, or a count that claims some (refused as pdlp_mi355x_update_values refuses it): not a plain pdlp_mi355x_update
+inline bool hasValues(const Variant& v) { return v.a_value || v.q_value || v.num_nz != 0 || v.num_q_nz != 0; }
+constexpr const char* kEntryBatchRun = "pdlp_mi355x_batch_run";
+constexpr const char* kEntryBatchRunValues = "pdlp_mi355x_batch_run_values";
+
+// What of P an update can change, kept on the host: variant k is P with v[k] applied, whatever variant the lane solved
+// before — so what an earlier variant changed on a lane and this one leaves alone goes back to P's values.
+struct BaseData {
+  std::vector<double> cost, colLower, colUpper, rowLower, rowUpper, aValue, qValue;
+  double offset = 0.0;
+  explicit BaseData(const pdlp_problem_t& P);
+};
+
+// The ONE update call that takes a lane's solver, which differs from P in the arrays `differs` names, to variant v: what v
+// gives, P's array for what it leaves alone but the solver differs in, nothing (NULL: unchanged) for the rest.
+enum : int { kLaneCost = 1, kLaneColLower = 2, kLaneColUpper = 4, kLaneRows = 8, kLaneOffset = 16, kLaneMatrix = 32, kLaneHessian = 64 };
+enum LaneCall : int { kCallUpdate = 0, kCallUpdateMatrix = 1, kCallUpdateValues = 2 };
+struct LaneUpdatePlan {
+  Variant v;      // the arguments of the call
+  int now = 0;    // the arrays in which the solver differs from P afterwards
+  LaneCall call = kCallUpdate;  // no value array: the plain update; a_value alone: update_matrix (which is update_values on a
+                                // Hessian-updatable solver); else update_values
+};
+LaneUpdatePlan planLaneUpdate(const Variant& v, int differs, const BaseData& base);
+
 // What the driver asks of a resident solver (SolverLane: Solver's lane steps, pdlp_solver.hpp).
 class BatchLane {
  public:
   virtual ~BatchLane() = default;
   virtual std::string sequentialReason() = 0;  // empty: the launches can be shared
   virtual int32_t workBlocks() = 0;
-  virtual void validate(const pdlp_update_t& u) = 0;  // throws with update's words; changes nothing
+  virtual void validate(const Variant& v) = 0;  // throws with the words of the update entry v maps to; changes nothing
   virtual void setVariant(int32_t k, int32_t iterLimit) = 0;  // log prefix and iteration limit (0: the batch's) of what follows
-  virtual void update(const pdlp_update_t& u) = 0;
+  virtual void update(const Variant& v) = 0;
   virtual void runAlone(pdlp_result_t* R) = 0;  // the ordinary run, with its own fall-backs
   virtual void begin() = 0;
   virtual bool idle() = 0;
@@ -62,12 +93,12 @@ class BatchBackend {
 class BatchDriver {
  public:
   BatchDriver(std::vector<BatchLane*> lanes, BatchBackend* backend);
-  void run(int32_t K, const pdlp_update_t* u, pdlp_result_t* R);
+  void run(int32_t K, const Variant* v, pdlp_result_t* R, const char* entry = kEntryBatchRun);  // entry: named in the refusals
   const pdlp_batch_info_t& info() const { return info_; }
 
  private:
-  void runSequential(int32_t first, int32_t K, const pdlp_update_t* u, pdlp_result_t* R);
-  void runConcurrent(int32_t K, const pdlp_update_t* u, pdlp_result_t* R);
+  void runSequential(int32_t first, int32_t K, const Variant* v, pdlp_result_t* R);
+  void runConcurrent(int32_t K, const Variant* v, pdlp_result_t* R);
   std::vector<BatchLane*> lanes_;
   BatchBackend* backend_;
   pdlp_batch_info_t info_{};
@@ -75,6 +106,11 @@ class BatchDriver {
 
 // Refusals of pdlp_mi355x_batch_create that need no device: nullptr, or the message.
 std::string batchCreateRefusal(const pdlp_params_t& opt, int32_t lanes);
+// K < 1 and null arrays, as both run entries refuse them.  Throws.
+void refuseBatchArguments(const char* entry, int32_t K, const void* variants, const void* results);
+// Refusals of one variant of pdlp_mi355x_batch_run_values that look at no matrix or Hessian VALUE, for a batch created on P
+// with opt (the batch's own DATA bit is added here): empty, or the words of the update entry the variant maps to.
+std::string batchVariantRefusal(const pdlp_problem_t& P, const pdlp_params_t& opt, const Variant& v);
 
 // The batch behind the C ABI: the solvers, their lanes, the device backend and the driver.
 class Batch {
@@ -82,6 +118,7 @@ class Batch {
   Batch(const pdlp_problem_t& P, const pdlp_params_t& opt, int32_t lanes);
   ~Batch();
   void run(int32_t K, const pdlp_update_t* u, pdlp_result_t* R);
+  void runValues(int32_t K, const Variant* v, pdlp_result_t* R);
   const pdlp_batch_info_t& info() const { return driver_->info(); }
 
  private:

@@ -41,6 +41,34 @@ void Solver::validateUpdate(const pdlp_update_t& u) const {
   if (u.row_lower) refuseKindChange(F_.rowKind.data(), F_.m, u.row_lower, u.row_upper);
 }
 
+// The refusals of updateValues / updateMatrix for these arguments, in their order and words.  Those that look at no value
+// first (refuseValueUpdate); then the all-zero matrix by the host's rule on the caller's array, and the negative diagonal
+// by the update's own head (the assembly map lives on the device only): stageHessian writes the staging copy of q_value
+// and the validation kernel's word, which nothing but an update's head reads — nothing of the solver's problem.
+void Solver::validateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t& u) const {
+  ValueUpdateFacts f;
+  f.sharded = sharded_;
+  f.updatable = opt_.updatable;
+  f.nnz = nnzIn_;
+  f.qSlots = hk_.nSlots;
+  f.hasQoff = hasQoff_;
+  f.rowKind = F_.rowKind.data();
+  f.m = F_.m;
+  refuseValueUpdate(f, aValue, numNz, qValue, numQNz, u);
+  if (aValue) {
+    bool anyNonzero = false;  // (a NaN among the values is not zero, as for create and for the device's absolute maximum)
+    for (int64_t p = 0; p < nnzIn_ && !anyNonzero; ++p) anyNonzero = aValue[p] != 0.0;
+    if (!anyNonzero) throwAllZeroMatrix();
+  }
+  if (qValue) {
+    Solver* self = const_cast<Solver*>(this);  // (staging only, see above)
+    PDLP_HIP(hipSetDevice(opt_.device));
+    PDLP_HIP(hipStreamSynchronize(stream_));
+    self->ensureDataStaging();
+    self->stageHessian(qValue);
+  }
+}
+
 // run() up to the first round of its device-driven loop
 void Solver::laneBegin() {
   reset();
@@ -101,17 +129,6 @@ void Solver::laneFinish(pdlp_result_t* R) {
 
 namespace {
 
-// The data of P that an update can change, kept on the host: variant k is P with u[k] applied, whatever variant the lane
-// solved before — so what an earlier variant changed on a lane and this one leaves alone goes back to P's values.
-struct BaseData {
-  std::vector<double> cost, colLower, colUpper, rowLower, rowUpper;
-  double offset = 0.0;
-  explicit BaseData(const pdlp_problem_t& P)
-      : cost(P.col_cost, P.col_cost + P.num_col), colLower(P.col_lower, P.col_lower + P.num_col),
-        colUpper(P.col_upper, P.col_upper + P.num_col), rowLower(P.row_lower, P.row_lower + P.num_row),
-        rowUpper(P.row_upper, P.row_upper + P.num_row), offset(P.offset) {}
-};
-
 class SolverLane : public BatchLane {
  public:
   SolverLane(Solver* s, const pdlp_params_t& opt, const BaseData* base) : s_(s), opt_(opt), base_(base) {
@@ -120,7 +137,10 @@ class SolverLane : public BatchLane {
   }
   std::string sequentialReason() override { return s_->laneSequentialReason(); }
   int32_t workBlocks() override { return s_->laneWorkBlocks(); }
-  void validate(const pdlp_update_t& u) override { s_->validateUpdate(u); }
+  void validate(const Variant& v) override {
+    if (!hasValues(v)) s_->validateUpdate(v.u);
+    else s_->validateValues(v.a_value, v.num_nz, v.q_value, v.num_q_nz, v.u);
+  }
   void setVariant(int32_t k, int32_t iterLimit) override {
     pdlp_params_t o = opt_;
     if (iterLimit > 0) o.iter_limit = iterLimit;
@@ -132,24 +152,14 @@ class SolverLane : public BatchLane {
     }
     s_->setRuntimeOptions(o);
   }
-  void update(const pdlp_update_t& u) override {
-    enum { kCost = 1, kColLower = 2, kColUpper = 4, kRows = 8, kOffset = 16 };
-    pdlp_update_t v = u;
-    int now = 0;
-    auto take = [&](const double*& field, const std::vector<double>& base, int bit) {
-      if (field) now |= bit;
-      else if (differs_ & bit) field = base.data();
-    };
-    take(v.col_cost, base_->cost, kCost);
-    take(v.col_lower, base_->colLower, kColLower);
-    take(v.col_upper, base_->colUpper, kColUpper);
-    if (v.row_lower) now |= kRows;  // (given together: validated)
-    else if (differs_ & kRows) { v.row_lower = base_->rowLower.data(); v.row_upper = base_->rowUpper.data(); }
-    if (v.has_offset) now |= kOffset;
-    else if (differs_ & kOffset) { v.has_offset = 1; v.offset = base_->offset; }
-    differs_ |= now;  // (also when the update throws half-way: a needless restore costs time only)
-    s_->update(v);
-    differs_ = now;
+  void update(const Variant& v) override {
+    const LaneUpdatePlan plan = planLaneUpdate(v, differs_, *base_);
+    const Variant& w = plan.v;
+    differs_ |= plan.now;  // (also when the update throws half-way: a needless restore costs time only)
+    if (plan.call == kCallUpdate) s_->update(w.u);
+    else if (plan.call == kCallUpdateMatrix) s_->updateMatrix(w.a_value, w.num_nz, &w.u);
+    else s_->updateValues(w.a_value, w.num_nz, w.q_value, w.num_q_nz, &w.u);
+    differs_ = plan.now;
   }
   void runAlone(pdlp_result_t* R) override { s_->run(R); }
   void begin() override { s_->laneBegin(); }
@@ -193,6 +203,30 @@ std::string batchCreateRefusal(const pdlp_params_t& opt, int32_t lanes) {
   return std::string();
 }
 
+std::string batchVariantRefusal(const pdlp_problem_t& P, const pdlp_params_t& opt, const Variant& v) {
+  try {
+    std::vector<int32_t> kind((size_t)std::max(P.num_row, 0));
+    for (int32_t i = 0; i < P.num_row; ++i) kind[(size_t)i] = rowKindOf(P.row_lower[i], P.row_upper[i]);
+    if (!hasValues(v)) {  // Solver::validateUpdate, on a solver the batch has made updatable
+      checkUpdateShape(v.u);
+      if (v.u.row_lower) refuseKindChange(kind.data(), P.num_row, v.u.row_lower, v.u.row_upper);
+      return std::string();
+    }
+    const SessionShape shape = sessionShapeOf(P);
+    ValueUpdateFacts f;
+    f.updatable = opt.updatable | PDLP_UPDATABLE_DATA;
+    f.nnz = shape.nnz;
+    f.qSlots = (opt.updatable & PDLP_UPDATABLE_HESSIAN) ? shape.qSlots : 0;
+    f.hasQoff = (opt.updatable & PDLP_UPDATABLE_HESSIAN) ? hessianHasOffDiagonalSlot(P) : hessianHasOffDiagonal(P);
+    f.rowKind = kind.data();
+    f.m = P.num_row;
+    refuseValueUpdate(f, v.a_value, v.num_nz, v.q_value, v.num_q_nz, v.u);
+  } catch (const std::exception& e) {
+    return e.what();
+  }
+  return std::string();
+}
+
 struct Batch::Impl {
   std::vector<std::unique_ptr<Solver>> solvers;
   std::vector<std::unique_ptr<SolverLane>> lanes;
@@ -225,7 +259,20 @@ Batch::~Batch() = default;
 
 void Batch::run(int32_t K, const pdlp_update_t* u, pdlp_result_t* R) {
   PDLP_HIP(hipSetDevice(impl_->device));
-  driver_->run(K, u, R);
+  std::vector<Variant> v;  // each update as a variant without values
+  if (K >= 1 && u) {
+    v.resize((size_t)K);
+    for (int32_t k = 0; k < K; ++k) {
+      memset(&v[(size_t)k], 0, sizeof(Variant));
+      v[(size_t)k].u = u[k];
+    }
+  }
+  driver_->run(K, u ? v.data() : nullptr, R, kEntryBatchRun);
+}
+
+void Batch::runValues(int32_t K, const Variant* v, pdlp_result_t* R) {
+  PDLP_HIP(hipSetDevice(impl_->device));
+  driver_->run(K, v, R, kEntryBatchRunValues);
 }
 
 }  // namespace pdlp

@@ -184,6 +184,10 @@ class Solver : public SolverBase {
   int32_t laneWorkBlocks() const { return smallGrid_; }
   // the refusals of update(u) that do not depend on the device, with update's words; nothing is changed
   void validateUpdate(const pdlp_update_t& u) const;
+  // likewise every refusal of updateValues(aValue, numNz, qValue, numQNz, &u) — of updateMatrix where a_value comes alone to
+  // a solver without PDLP_UPDATABLE_HESSIAN —, the all-zero matrix and the negative diagonal included; nothing of the
+  // solver's problem is changed (the Hessian's values go through the update's own staging buffer and validation kernel)
+  void validateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t& u) const;
   void laneBegin();
   bool laneIdle() const { return loop_.noLoop; }  // the iteration limit is reached before the first round: laneFinish may follow at once
   void laneQueue(int32_t ahead, std::vector<LaneUnit>& units);

@@ -160,6 +160,32 @@ void throwNegativeDiagonal(int32_t col) {
                            "diagonal entry of column " + std::to_string(col) + " is negative)");
 }
 
+// Solver::updateValues' refusals, then those of the Impl it hands over to (updateMatrixImpl with a_value, else updateImpl),
+// up to the point where either looks at a value
+void refuseValueUpdate(const ValueUpdateFacts& f, const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz,
+                       const pdlp_update_t& u) {
+  const bool matrixBit = (f.updatable & PDLP_UPDATABLE_MATRIX) != 0, hessianBit = (f.updatable & PDLP_UPDATABLE_HESSIAN) != 0;
+  const bool asMatrix = aValue && !qValue && numQNz == 0 && !hessianBit;  // pdlp_mi355x_update_matrix (Solver::updateMatrix)
+  if (!asMatrix) {
+    if (f.sharded) refuseSharded(kEntryUpdateValues);
+    if (!hessianBit) refuseNoHessianBit(kEntryUpdateValues);
+    if (!aValue && numNz != 0)
+      throw std::runtime_error("pdlp_mi355x_update_values: a_value is NULL but num_nz = " + std::to_string(numNz));
+    if (aValue && !matrixBit) refuseNoMatrixBit(kEntryUpdateValues);
+    checkHessianUpdateShape(qValue, numQNz, f.qSlots > 0, f.qSlots);
+  }
+  if (aValue) {
+    if (f.sharded) refuseSharded(kEntryUpdateMatrix);
+    if (!matrixBit) refuseNoMatrixBit(kEntryUpdateMatrix);
+    if (f.hasQoff && !hessianBit) refuseOffDiagonalHessian(kEntryUpdateMatrix);
+    checkMatrixUpdateShape(aValue, numNz, f.nnz);
+  } else if (!f.updatable) {
+    refuseNotUpdatable(kEntryUpdate);
+  }
+  checkUpdateShape(u);
+  if (u.row_lower) refuseKindChange(f.rowKind, f.m, u.row_lower, u.row_upper);
+}
+
 void hostAssembleHessianUpdate(const double* qValue, StandardForm& F, bool validateOnly) {
   if (!F.hmap.kept() || F.qdiag0.size() != (size_t)F.n || F.qoff0.size() != (size_t)F.hmap.nOff)
     throw std::runtime_error("pdlp_mi355x_update_values: the form did not keep its Hessian");

@@ -128,6 +128,24 @@ void hostReplayHessianUpdate(const double* qValue, StandardForm& F);
 // the same validation and assembly into F.qdiag0 / F.qoff0 only (the matrix update's scale() does the rest)
 void hostAssembleHessianUpdate(const double* qValue, StandardForm& F, bool validateOnly);
 
+// ---- a value update validated ahead of time (a batch validates every variant before it changes a lane) ------------------
+// What the refusals that look at no VALUE depend on: a held solver fills it from itself (Solver::validateValues), the host
+// tests from the problem and the options (batchVariantRefusal, pdlp_batch.hpp).
+struct ValueUpdateFacts {
+  bool sharded = false;
+  int32_t updatable = 0;        // pdlp_params_t.updatable as the solver was created with
+  int64_t nnz = 0, qSlots = 0;  // the caller's nonzeros and Hessian slots at create (qSlots: 0 without a Hessian)
+  bool hasQoff = false;         // the Hessian has an off-diagonal part
+  const int32_t* rowKind = nullptr;
+  int32_t m = 0;
+};
+// Throws what pdlp_mi355x_update_values(aValue, numNz, qValue, numQNz, &u) — or pdlp_mi355x_update_matrix(aValue, numNz,
+// &u) where that is the entry (a_value alone on a solver without PDLP_UPDATABLE_HESSIAN) — refuses before it looks at a
+// value, in that entry's order and words: sharded, the updatable bits, the counts, the off-diagonal Hessian, u's shape
+// and the kind change.
+void refuseValueUpdate(const ValueUpdateFacts& f, const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz,
+                       const pdlp_update_t& u);
+
 // bad[0] = min(bad[0], smallest column whose assembled diagonal is negative); the caller sets bad[0] = n first
 void launchHessianValidate(const int32_t* dstBeg, const int32_t* srcSlot, const double* qValue, double sense, int32_t n,
                            int32_t* bad, hipStream_t s);

@@ -49,7 +49,7 @@ EXPORTS = [
     "pdlp_mi355x_session_create", "pdlp_mi355x_session_solve", "pdlp_mi355x_session_info", "pdlp_mi355x_session_release",
     "pdlp_mi355x_session_destroy", "pdlp_mi355x_session_info_size", "pdlp_mi355x_host_classify",
     "pdlp_mi355x_batch_create", "pdlp_mi355x_batch_run", "pdlp_mi355x_batch_info", "pdlp_mi355x_batch_destroy",
-    "pdlp_mi355x_batch_info_size",
+    "pdlp_mi355x_batch_info_size", "pdlp_mi355x_batch_run_values", "pdlp_mi355x_variant_size",
     "pdlp_mi355x_solve_many", "pdlp_mi355x_pool_info_size",
 ]
 
@@ -128,6 +128,16 @@ def lib():
             pB = C.POINTER(abi.PdlpBatchInfo)
             L.pdlp_mi355x_batch_create.argtypes = [pP, pO, C.c_int32, C.POINTER(H)]
             L.pdlp_mi355x_batch_run.argtypes = [H, C.c_int32, pU, pR]
+            # (a build from before the value variants has neither: tools/batch_values_bench.py's sequential side)
+            if hasattr(L, "pdlp_mi355x_batch_run_values"):
+                pV = C.POINTER(abi.PdlpVariant)
+                L.pdlp_mi355x_batch_run_values.argtypes = [H, C.c_int32, pV, pR]
+                L.pdlp_mi355x_variant_size.restype = C.c_int64
+                # (a test hook outside the public header: batch_run_values' refusals that need no device)
+                L.pdlp_mi355x_host_batch_variants_refusal.argtypes = [pP, pO, C.c_int32, pV, pR]
+                if L.pdlp_mi355x_variant_size() != C.sizeof(abi.PdlpVariant):
+                    raise RuntimeError("pdlp_variant_t: the library's size %d differs from abi.PdlpVariant's %d" %
+                                       (L.pdlp_mi355x_variant_size(), C.sizeof(abi.PdlpVariant)))
             L.pdlp_mi355x_batch_info.argtypes = [H, pB]
             L.pdlp_mi355x_batch_destroy.argtypes = [H]
             L.pdlp_mi355x_batch_destroy.restype = None
@@ -606,7 +616,14 @@ class DeviceBatch:
     of DeviceSolver.update's arguments (col_cost, col_lower, col_upper, row_lower, row_upper, offset, start; {} = the LP as
     it is) plus, optionally, iter_limit for that variant alone — and returns one PdlpOutcome per variant, bit for bit what
     `DeviceSolver(lp, updatable=True, **options)` gives for update(**variant) + solve().  Where the LP's trial loop runs
-    XCD-local the variants run at once, one per XCD (include/pdlp_mi355x.h; info().text says how the last run went)."""
+    XCD-local the variants run at once, one per XCD (include/pdlp_mi355x.h; info().text says how the last run went).
+
+    A variant's dict may also carry a_value= (new matrix values, for a batch created with updatable="matrix") and q_value=
+    (new Hessian values, updatable="hessian" or "matrix+hessian"), each on the LP's own pattern; an array a variant leaves
+    out is the LP's own, whatever variant its lane solved before.  If any variant has one, the call goes through
+    pdlp_mi355x_batch_run_values, and the reference is `DeviceSolver(lp, updatable=…, **options)` (the batch's own
+    `updatable`) + update_values(a_value, q_value, **data) — update_matrix(a_value, **data) for a_value alone on a batch
+    without "hessian", update(**data) without either array — + solve()."""
 
     def __init__(self, lp, lanes=8, params=None, **options):
         self.params = params or abi.default_params(**options)
@@ -621,16 +638,18 @@ class DeviceBatch:
     def run(self, variants):
         import copy
         K = len(variants)
+        with_values = any(v.get("a_value") is not None or v.get("q_value") is not None for v in variants)
         handles, lps, limits = [], [], []
-        U = (abi.PdlpUpdate * max(K, 1))()
+        U = ((abi.PdlpVariant if with_values else abi.PdlpUpdate) * max(K, 1))()
         Rs = (abi.PdlpResult * max(K, 1))()
         results = []
         for k, v in enumerate(variants):
             v = dict(v)
             limit = v.pop("iter_limit", None)
-            hnd = abi.UpdateHandle(**v)
+            a_value, q_value = v.pop("a_value", None), v.pop("q_value", None)
+            hnd = abi.VariantHandle(a_value, q_value, **v) if with_values else abi.UpdateHandle(**v)
             if limit is not None:
-                hnd.struct.reserved = int(limit)
+                (hnd.struct.u if with_values else hnd.struct).reserved = int(limit)
             handles.append(hnd)
             U[k] = hnd.struct
             limits.append(self.params.iter_limit if limit is None else int(limit))
@@ -640,11 +659,18 @@ class DeviceBatch:
                     setattr(lp, name, np.array(v[name], dtype=np.float64))
             if v.get("offset") is not None:
                 lp.offset = float(v["offset"])
+            if a_value is not None:
+                lp.a_value = np.array(a_value, dtype=np.float64)
+            if q_value is not None:
+                lp.hessian = (lp.hessian[0], lp.hessian[1], np.array(q_value, dtype=np.float64))
             lps.append(lp)
             R = abi.ResultHandle(self.lp.num_col, self.lp.num_row)
             results.append(R)
             Rs[k] = R.struct
-        _check(lib().pdlp_mi355x_batch_run(self.h, K, U, Rs), "pdlp_mi355x_batch_run")
+        if with_values:
+            _check(lib().pdlp_mi355x_batch_run_values(self.h, K, U, Rs), "pdlp_mi355x_batch_run_values")
+        else:
+            _check(lib().pdlp_mi355x_batch_run(self.h, K, U, Rs), "pdlp_mi355x_batch_run")
         out = []
         for k in range(K):
             results[k].struct = Rs[k]

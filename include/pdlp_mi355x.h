@@ -365,6 +365,23 @@ int64_t pdlp_mi355x_session_info_size(void); /* sizeof(pdlp_session_info_t); pdl
  *     barrier leaves the shared launches for good; its variant is re-solved alone through the ordinary run
  *     (fallback_variants counts them).
  *   * With log_level >= 1 every log line carries a "[variant k] " prefix.
+ *
+ * VALUE VARIANTS (pdlp_mi355x_batch_run_values): a variant may also carry new MATRIX values and new HESSIAN values on P's
+ * patterns — a risk-aversion sweep or re-estimated covariances on one portfolio model, scenario LPs whose coefficients
+ * differ on one pattern, SQP subproblems.  The lanes' updatable bits are the caller's: the batch adds none besides DATA,
+ * so a_value needs PDLP_UPDATABLE_MATRIX in opt and q_value needs PDLP_UPDATABLE_HESSIAN — and lanes created with
+ * PDLP_UPDATABLE_HESSIAN follow THE PATTERN CONTRACT above (every slot the caller passes is kept, explicit zeros included).
+ * It is batch_run's contract with one change: R[k] is, bit for bit, what the ONE held solver s gives for the update below
+ * followed by pdlp_mi355x_run, where A_k is v[k].a_value where given and P's a_value otherwise, Q_k likewise:
+ *     neither array ....................................... pdlp_mi355x_update(s, &v[k].u)
+ *     a_value only, opt without PDLP_UPDATABLE_HESSIAN ..... pdlp_mi355x_update_matrix(s, A_k, num_nz, &v[k].u)
+ *     otherwise ........................................... pdlp_mi355x_update_values(s, A_k, nnz, Q_k, qnz, &v[k].u)
+ * "Unchanged" in a batch always means P's values, whatever variant the lane solved before: an array that a lane's earlier
+ * variant changed and this one leaves alone goes back to P's in the same update.  (A count given with a NULL array sends
+ * the variant to update_values, which refuses it.)  All v[k] are validated before anything is changed — the all-zero
+ * matrix and the negative diagonal included —; a refusal reads "variant k: " + the words of the entry the variant maps to
+ * and leaves the batch as it was.  pdlp_batch_info_t describes a batch_run_values as it does a batch_run; value updates
+ * change no pattern, so whether the lanes share launches is the same for both entries.
  * THREADING: one thread uses a batch at a time. */
 typedef struct pdlp_batch_info { /* about the last pdlp_mi355x_batch_run */
   int32_t lanes;             /* solvers held */
@@ -382,6 +399,13 @@ typedef struct pdlp_batch_info { /* about the last pdlp_mi355x_batch_run */
 typedef struct pdlp_mi355x_batch pdlp_mi355x_batch_t; /* opaque */
 int pdlp_mi355x_batch_create(const pdlp_problem_t* P, const pdlp_params_t* opt, int32_t lanes, pdlp_mi355x_batch_t** out);
 int pdlp_mi355x_batch_run(pdlp_mi355x_batch_t* B, int32_t K, const pdlp_update_t* u, pdlp_result_t* R);
+typedef struct pdlp_variant {
+  const double* a_value; int64_t num_nz;    /* NULL / 0: the matrix values of the batch's problem P */
+  const double* q_value; int64_t num_q_nz;  /* NULL / 0: P's Hessian values */
+  pdlp_update_t u;                          /* data, start, u.reserved = iteration limit; all zero: P's data, cold start */
+} pdlp_variant_t;
+int pdlp_mi355x_batch_run_values(pdlp_mi355x_batch_t* B, int32_t K, const pdlp_variant_t* v, pdlp_result_t* R);
+int64_t pdlp_mi355x_variant_size(void);     /* sizeof(pdlp_variant_t); pdlp_mi355x_sizeof keeps its indices */
 int pdlp_mi355x_batch_info(const pdlp_mi355x_batch_t* B, pdlp_batch_info_t* out);
 void pdlp_mi355x_batch_destroy(pdlp_mi355x_batch_t* B);
 int64_t pdlp_mi355x_batch_info_size(void); /* sizeof(pdlp_batch_info_t); pdlp_mi355x_sizeof keeps its indices */

@@ -1,7 +1,10 @@
 // tools/batch_driver_check.cpp — the batch driver (highs_amd/csrc/pdlp_batch.cpp) behind canned lanes, as a stand-alone
 // host program for sanitizer runs (tools/batch_driver_check.sh): no device call is made.  A canned lane "solves" variant k
 // in rounds[k] rounds, writes k into R[k].num_iter, and fails where the script says so; the checks are on who solved what,
-// the launch counts, the refills and the failure rule.
+// the launch counts, the refills and the failure rule.  A canned lane also plays the held solver of a value variant
+// (pdlp_mi355x_batch_run_values): it follows which array its "solver" holds through the one update call the lane plans
+// (planLaneUpdate), and checks after every update that it holds variant k = P with v[k] applied — whatever it solved
+// before, and also after an update that threw half-way.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -19,19 +22,70 @@ struct Script {
   int failVariant = -1;      // this variant's lane reports a failure in its first round
   std::string sequential;    // lanes' reason for running alone
   int badVariant = -1;       // validate() refuses this variant
+  std::string kinds;         // per variant: n nothing, A a_value, Q q_value, B both, D data (cost and rows); empty: all n
+  int throwVariant = -1;     // update() of this variant throws half-way, once
+  int disqualifyVariant = -1;  // after this variant's update the lane says it cannot share launches
 };
+// P of the canned batches, and one set of arrays per variant (their addresses are what the lanes follow)
+struct Arrays { std::vector<double> cost{1, 2}, lower{0, 0}, upper{1, 1}, rowLo{0, 0}, rowUp{1, 1}, a{1, 2, 3}, q{4, 5}; };
+const int32_t kStart[] = {0, 2, 3}, kIndex[] = {0, 1, 1}, kQStart[] = {0, 1, 2}, kQIndex[] = {0, 1};
+pdlp_problem_t problemOf(const Arrays& d) {
+  pdlp_problem_t P;
+  memset(&P, 0, sizeof(P));
+  P.num_col = 2; P.num_row = 2; P.num_nz = 3;
+  P.a_start = kStart; P.a_index = kIndex; P.a_value = d.a.data();
+  P.col_cost = d.cost.data(); P.col_lower = d.lower.data(); P.col_upper = d.upper.data();
+  P.row_lower = d.rowLo.data(); P.row_upper = d.rowUp.data();
+  P.q_dim = 2; P.q_start = kQStart; P.q_index = kQIndex; P.q_value = d.q.data();
+  return P;
+}
+const double kTorn = 0.0;  // what an array holds after an update that threw: neither P's nor a variant's
+struct Held { const double *cost, *rows, *a, *q; };
 struct CannedLane : BatchLane {
   const Script& sc;
-  int id, variant = -1, left = 0, updates = 0, alone = 0, shared = 0;
+  const BaseData& base;
+  int id, variant = -1, left = 0, updates = 0, alone = 0, shared = 0, differs = 0, plain = 0, matrix = 0, values = 0;
+  bool threw = false, disqualified = false;
+  Held held;
   std::vector<int> solved;
-  CannedLane(const Script& s, int i) : sc(s), id(i) {}
-  std::string sequentialReason() override { return sc.sequential; }
+  CannedLane(const Script& s, const BaseData& b, int i)
+      : sc(s), base(b), id(i), held{b.cost.data(), b.rowLower.data(), b.aValue.data(), b.qValue.data()} {}
+  std::string sequentialReason() override { return disqualified ? "canned: no longer shareable" : sc.sequential; }
   int32_t workBlocks() override { return 21; }
-  void validate(const pdlp_update_t& u) override {
-    if (u.reserved == -7) throw std::runtime_error("pdlp_mi355x_update: row 5 would change its kind");
+  void validate(const Variant& v) override {
+    if (v.u.reserved == -7) throw std::runtime_error("pdlp_mi355x_update: row 5 would change its kind");
+    if (v.u.reserved == -8) throw std::runtime_error("pdlp_mi355x_update_values: the Hessian is not positive semidefinite");
   }
   void setVariant(int32_t k, int32_t) override { variant = k; }
-  void update(const pdlp_update_t&) override { ++updates; }
+  // SolverLane::update, with a solver that only remembers whose array it holds
+  void update(const Variant& v) override {
+    ++updates;
+    const LaneUpdatePlan plan = planLaneUpdate(v, differs, base);
+    const Variant& w = plan.v;
+    differs |= plan.now;
+    CHECK(plan.call == (w.q_value ? kCallUpdateValues : w.a_value ? kCallUpdateMatrix : kCallUpdate));
+    CHECK((w.a_value == nullptr) == (w.num_nz == 0) && (w.q_value == nullptr) == (w.num_q_nz == 0));
+    if (variant == sc.throwVariant && !threw) {  // half-way: everything it was asked to change is torn
+      threw = true;
+      if (w.u.col_cost) held.cost = &kTorn;
+      if (w.u.row_lower) held.rows = &kTorn;
+      if (w.a_value) held.a = &kTorn;
+      if (w.q_value) held.q = &kTorn;
+      throw std::runtime_error("canned: the update of variant " + std::to_string(variant) + " failed");
+    }
+    if (w.u.col_cost) held.cost = w.u.col_cost;
+    if (w.u.row_lower) { CHECK(w.u.row_upper); held.rows = w.u.row_lower; }
+    if (w.a_value) held.a = w.a_value;
+    if (w.q_value) held.q = w.q_value;
+    differs = plan.now;
+    (plan.call == kCallUpdate ? plain : plan.call == kCallUpdateMatrix ? matrix : values)++;
+    // variant k = P with v[k] applied
+    CHECK(held.cost == (v.u.col_cost ? v.u.col_cost : base.cost.data()));
+    CHECK(held.rows == (v.u.row_lower ? v.u.row_lower : base.rowLower.data()));
+    CHECK(held.a == (v.a_value ? v.a_value : base.aValue.data()));
+    CHECK(held.q == (v.q_value ? v.q_value : base.qValue.data()));
+    if (variant == sc.disqualifyVariant) disqualified = true;
+  }
   void runAlone(pdlp_result_t* R) override { R->num_iter = variant; R->num_trials = -1 - id; ++alone; solved.push_back(variant); }
   void begin() override { left = sc.rounds[(size_t)variant]; }
   bool idle() override { return left == 0; }
@@ -59,54 +113,103 @@ struct CountingBackend : BatchBackend {
   }
 };
 
-void scenario(int nLanes, const Script& sc, int K) {
+void scenario(int nLanes, const Script& sc, int K, bool oldEntry = true) {
+  const Arrays p;
+  const pdlp_problem_t P = problemOf(p);
+  const BaseData base(P);
+  CHECK(base.aValue.size() == 3 && base.qValue.size() == 2 && base.aValue.data() != p.a.data());  // (a copy: P's arrays may go)
   std::vector<std::unique_ptr<CannedLane>> own;
   std::vector<BatchLane*> lanes;
-  for (int l = 0; l < nLanes; ++l) { own.emplace_back(new CannedLane(sc, l)); lanes.push_back(own.back().get()); }
+  for (int l = 0; l < nLanes; ++l) { own.emplace_back(new CannedLane(sc, base, l)); lanes.push_back(own.back().get()); }
   CountingBackend be;
   BatchDriver d(lanes, &be);
-  std::vector<pdlp_update_t> u((size_t)K);
+  std::vector<Arrays> mine((size_t)K);
+  std::vector<Variant> u((size_t)K);
   std::vector<pdlp_result_t> R((size_t)K);
-  memset(u.data(), 0, sizeof(pdlp_update_t) * (size_t)K);
+  memset(u.data(), 0, sizeof(Variant) * (size_t)K);
   memset(R.data(), 0, sizeof(pdlp_result_t) * (size_t)K);
+  int nValue = 0;
+  for (int k = 0; k < K; ++k) {
+    const char kind = sc.kinds.empty() ? 'n' : sc.kinds[(size_t)k % sc.kinds.size()];
+    Arrays& m = mine[(size_t)k];
+    Variant& v = u[(size_t)k];
+    if (kind == 'A' || kind == 'B') { v.a_value = m.a.data(); v.num_nz = 3; }
+    if (kind == 'Q' || kind == 'B') { v.q_value = m.q.data(); v.num_q_nz = 2; }
+    if (kind == 'D') { v.u.col_cost = m.cost.data(); v.u.row_lower = m.rowLo.data(); v.u.row_upper = m.rowUp.data(); }
+    nValue += hasValues(v) ? 1 : 0;
+  }
+  const char* entry = oldEntry ? kEntryBatchRun : kEntryBatchRunValues;
   for (auto& r : R) r.num_iter = -1;
   if (sc.badVariant >= 0) {
-    u[(size_t)sc.badVariant].reserved = -7;
+    u[(size_t)sc.badVariant].u.reserved = oldEntry ? -7 : -8;
     bool threw = false;
-    try { d.run(K, u.data(), R.data()); } catch (const std::exception& e) {
+    try { d.run(K, u.data(), R.data(), entry); } catch (const std::exception& e) {
       threw = true;
-      CHECK(std::string(e.what()).find("variant " + std::to_string(sc.badVariant) + ": pdlp_mi355x_update: row 5") == 0);
+      const char* words = oldEntry ? ": pdlp_mi355x_update: row 5" : ": pdlp_mi355x_update_values: the Hessian is not";
+      CHECK(std::string(e.what()).find("variant " + std::to_string(sc.badVariant) + words) == 0);
     }
     CHECK(threw);
     for (auto& l : own) CHECK(l->updates == 0);  // nothing was changed
     for (auto& r : R) CHECK(r.num_iter == -1);
-    u[(size_t)sc.badVariant].reserved = 0;
+    u[(size_t)sc.badVariant].u.reserved = 0;
   }
-  d.run(K, u.data(), R.data());
+  {  // K < 1 and null arrays, by the entry's name
+    bool threw = false;
+    try { d.run(0, u.data(), R.data(), entry); } catch (const std::exception& e) {
+      threw = std::string(e.what()) == std::string(entry) + ": K = 0 variants (at least 1)";
+    }
+    CHECK(threw);
+    threw = false;
+    try { d.run(K, nullptr, R.data(), entry); } catch (const std::exception& e) {
+      threw = std::string(e.what()) == std::string(entry) + ": null argument";
+    }
+    CHECK(threw);
+  }
+  if (sc.throwVariant >= 0) {
+    // an update that throws in the middle of a run ends the call; the lanes then differ from P in whatever they were
+    // asked to change, so the next call (below) still gives every variant its own arrays
+    bool threw = false;
+    try { d.run(K, u.data(), R.data(), entry); } catch (const std::exception& e) {
+      threw = std::string(e.what()).find("canned: the update of variant") == 0;
+    }
+    CHECK(threw);
+    for (auto& l : own) { l->solved.clear(); l->alone = l->shared = 0; }
+    for (auto& r : R) r.num_iter = -1;
+  }
+  d.run(K, u.data(), R.data(), entry);
   const pdlp_batch_info_t& I = d.info();
   for (int k = 0; k < K; ++k) CHECK(R[(size_t)k].num_iter == k);  // every variant solved, each into its own result
-  int solved = 0;
-  for (auto& l : own) solved += (int)l->solved.size();
+  int solved = 0, plain = 0, valued = 0;
+  for (auto& l : own) { solved += (int)l->solved.size(); plain += l->plain; valued += l->matrix + l->values; }
   CHECK(solved == K);  // ... exactly once
+  if (nValue == 0) CHECK(valued == 0);  // without value variants every update is the plain one, as before them
+  CHECK(valued >= nValue);              // (more: the restores)
   CHECK(I.variants == K && I.lanes == nLanes);
   const bool concurrent = sc.sequential.empty() && nLanes > 1 && K > 1;
+  const int fellBack = (sc.failVariant >= 0 && sc.failVariant < K ? 1 : 0) + (sc.disqualifyVariant >= 0 && sc.disqualifyVariant < K ? 1 : 0);
   if (!concurrent) {
     CHECK(I.lanes_concurrent == 1 && I.trial_launches == 0 && be.rounds == 0);
     CHECK(strncmp(I.reason, "sequential: ", 12) == 0);
     CHECK((int)own[0]->solved.size() == K);
   } else {
     CHECK(strncmp(I.reason, "concurrent: ", 12) == 0);
-    CHECK(I.lanes_concurrent == std::min(nLanes, K));
-    CHECK(I.fallback_variants == (sc.failVariant >= 0 && sc.failVariant < K ? 1 : 0));
+    if (sc.disqualifyVariant < 0) CHECK(I.lanes_concurrent == std::min(nLanes, K));
+    CHECK(I.fallback_variants == fellBack);
     if (sc.failVariant >= 0 && sc.failVariant < K) {
       // the failed lane solved its variant alone, after the others, and took part in ONE round only
       const int l = -1 - R[(size_t)sc.failVariant].num_trials;
       CHECK(l >= 0 && l < nLanes && own[(size_t)l]->alone == 1 && own[(size_t)l]->shared == 1);
       CHECK(I.xcc_of_lane[l] == -1);
     }
+    if (sc.disqualifyVariant >= 0 && sc.disqualifyVariant < K) {
+      // the lane that no longer qualifies after its value update solved that variant alone, and nothing after it
+      const int l = -1 - R[(size_t)sc.disqualifyVariant].num_trials;
+      CHECK(l >= 0 && l < nLanes && own[(size_t)l]->alone == 1 && own[(size_t)l]->solved.back() == sc.disqualifyVariant);
+    }
     CHECK(I.trial_launches == I.check_launches && I.trial_launches > 0);
   }
-  printf("ok: %d lanes, K = %d: %s; %d shared launches, %d alone\n", nLanes, K, I.reason, I.trial_launches, I.fallback_variants);
+  printf("ok: %d lanes, K = %d%s: %s; %d shared launches, %d alone; %d plain and %d value updates\n", nLanes, K,
+         sc.kinds.empty() ? "" : (" [" + sc.kinds + "]").c_str(), I.reason, I.trial_launches, I.fallback_variants, plain, valued);
 }
 }  // namespace
 
@@ -128,6 +231,26 @@ int main() {
   scenario(4, b, 4);
   Script allFail = a; allFail.failVariant = 0;
   scenario(2, allFail, 2);
+  // value variants: every restore transition on one lane and on two, refills, the sequential classes
+  Script v = a; v.kinds = "AnQnBDQn";
+  scenario(1, v, 8, false);
+  scenario(2, v, 8, false);
+  scenario(8, v, 8, false);
+  scenario(3, v, 12, false);
+  Script vs = v; vs.sequential = "48 work blocks need more than one XCD";
+  scenario(8, vs, 8, false);
+  Script vb = v; vb.badVariant = 3;
+  scenario(4, vb, 8, false);
+  // a value variant whose update throws in the middle of a run (a refill on 2 lanes; the first update on 8)
+  Script vt = v; vt.throwVariant = 4;
+  scenario(2, vt, 8, false);
+  scenario(8, vt, 8, false);
+  scenario(1, vt, 8, false);
+  // a lane that says it no longer qualifies after a value update: the failure rule
+  Script vd = v; vd.disqualifyVariant = 2;
+  scenario(3, vd, 8, false);
+  Script vf = v; vf.failVariant = 1;
+  scenario(3, vf, 8, false);
   printf("batch driver: all scenarios passed\n");
   return 0;
 }
