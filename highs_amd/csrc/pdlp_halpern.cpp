@@ -292,6 +292,7 @@ void HalpernSolver::initStepSizes() {
 void HalpernSolver::pushState() {
   PDLP_HIP(hipMemcpyAsync(dState_.get(), hostState_, sizeof(HalpernState), hipMemcpyHostToDevice, stream_));
   PDLP_HIP(hipStreamSynchronize(stream_));
+  hostAhead_ = false;
 }
 void HalpernSolver::pullState() {
   PDLP_HIP(hipMemcpyAsync(hostState_, dState_.get(), sizeof(HalpernState), hipMemcpyDeviceToHost, stream_));
@@ -548,6 +549,7 @@ void HalpernSolver::restartCopies() {
 }
 
 void HalpernSolver::noteRecord(const HalpernRecord& r) {
+  lastRecord_ = r;
   res_.pObj = r.pObj; res_.dObj = r.dObj; res_.gap = r.gap; res_.relGap = r.relGap; res_.pFeas = r.pFeas; res_.dFeas = r.dFeas;
   if (opt_.log_level > 1 && rank_ == 0)
     logLine(opt_, 2, "%9lld  %+15.8e  %+15.8e  %8.2e  %10.2e  %8.2e  fpe %8.2e  w %8.2e\n", (long long)r.iters, r.pObj, r.dObj,
@@ -567,24 +569,54 @@ void HalpernSolver::enqueueUnit() {
 void HalpernSolver::enqueueUnitTail() {
   HalpernState* ds = dState_.get();
   const int32_t n = F_.n, m = mLoc_;
-  enqueueFpe(kSlotFpe, &ds->run);
-  enqueueCheck(xn_.get(), yn_.get(), true, &ds->run);
-  enqueueDiff(&ds->run);
+  enqueueCheckSums(&ds->run);
   launchHalpernDecide(ds, statOut_.get(), hostRing_, stream_);
   launchHalpernRestartCopy(ds, xa_.get(), xc_.get(), xn_.get(), n, ya_.get(), yc_.get(), yn_.get(), m, stream_);
   launchHalpernKeepOutput(ds, outX_.get(), xn_.get(), n, outY_.get(), yn_.get(), m, stream_);
 }
 
+// The statistics of the check behind a block, in the order both loops queue them (gate: the device-driven loop's `run`)
+void HalpernSolver::enqueueCheckSums(const int32_t* gate) {
+  enqueueFpe(kSlotFpe, gate);
+  enqueueCheck(xn_.get(), yn_.get(), true, gate);
+  enqueueDiff(gate);
+}
+
+// a converged check keeps its iterate (pdhg.cc:866-877): the host-driven loop
+void HalpernSolver::keepOutput(const double* x, const double* y) {
+  PDLP_HIP(hipMemcpyAsync(outX_.get(), x, sizeof(double) * F_.n, hipMemcpyDeviceToDevice, stream_));
+  PDLP_HIP(hipMemcpyAsync(outY_.get(), y, sizeof(double) * mLoc_, hipMemcpyDeviceToDevice, stream_));
+  haveOutput_ = true;
+}
+
+// The initial convergence check, pdhg.cc:563-570: the slack is derived by bound kind (no major step has cached one)
+bool HalpernSolver::initialCheck(HalpernRecord& r) {
+  enqueueCheck(xc_.get(), yc_.get(), false, nullptr);
+  fetchStats(kSlotFpe0);
+  if (mesh_) mesh_->verifyReplicated(rx_.get(), F_.n, stream_);
+  return halpernResiduals(*hostState_, hostStats_, r);
+}
+
+// The host-driven loop behind fetchStats(kStatOut): the decision on the host's copy of the state, then what it asks for
+void HalpernSolver::hostCheckEnd() {
+  HalpernState& H = *hostState_;
+  const HalpernRecord r = halpernDecide(H, hostStats_);
+  hostAhead_ = true;
+  ++hostChecks_;
+  noteRecord(r);
+  iters_ = H.iters; nRestarts_ = H.nRestarts; nChecks_ = H.nChecks;
+  if (H.converged) {
+    keepOutput(xn_.get(), yn_.get());
+    termStatus_ = 0;
+    return;
+  }
+  if (H.doRestart) restartCopies();
+}
+
 // PDLPSolver::solve, pdhg.cc:494-707.  terminate = false: fixed-work loop for timing (same
 // kernels, checks and restarts; convergence is ignored).
 void HalpernSolver::doSolve(bool terminate, int64_t iterTarget) {
-  const int32_t n = F_.n, m = mLoc_;
   HalpernState& H = *hostState_;
-  auto keepOutput = [&](const double* x, const double* y) {
-    PDLP_HIP(hipMemcpyAsync(outX_.get(), x, sizeof(double) * n, hipMemcpyDeviceToDevice, stream_));
-    PDLP_HIP(hipMemcpyAsync(outY_.get(), y, sizeof(double) * m, hipMemcpyDeviceToDevice, stream_));
-    haveOutput_ = true;
-  };
   auto mirror = [&]() { iters_ = H.iters; nRestarts_ = H.nRestarts; nChecks_ = H.nChecks; };
   auto timeUp = [&]() {  // every rank must take the same branch: the ranks' clocks are OR-ed
     bool up = elapsed() > opt_.time_limit;
@@ -605,11 +637,8 @@ void HalpernSolver::doSolve(bool terminate, int64_t iterTarget) {
   armState();
   if (H.iters == 0 && terminate) {  // initial convergence check, pdhg.cc:563-570
     pushState();
-    enqueueCheck(xc_.get(), yc_.get(), false, nullptr);
-    fetchStats(kSlotFpe0);
-    if (mesh_) mesh_->verifyReplicated(rx_.get(), F_.n, stream_);
     HalpernRecord r{};
-    const bool conv = halpernResiduals(H, hostStats_, r);
+    const bool conv = initialCheck(r);
     H.nChecks += 1;
     res_.pObj = r.pObj; res_.dObj = r.dObj; res_.gap = r.gap; res_.relGap = r.relGap; res_.pFeas = r.pFeas; res_.dFeas = r.dFeas;
     mirror();
@@ -662,7 +691,7 @@ void HalpernSolver::doSolve(bool terminate, int64_t iterTarget) {
         enqueueUnitTail();
         pullState();
       }
-      for (int32_t c = checksBefore; c < H.nChecks; ++c) noteRecord(hostRing_[c % kHalpernRing]);
+      for (int32_t c = checksBefore; c < H.nChecks; ++c) { noteRecord(hostRing_[c % kHalpernRing]); ++deviceChecks_; }
       mirror();
       if (H.halted) {
         if (H.converged) { haveOutput_ = true; termStatus_ = 0; }
@@ -684,29 +713,18 @@ void HalpernSolver::doSolve(bool terminate, int64_t iterTarget) {
     const bool fpeAfterFirst = H.fpe0Pending != 0;
     pushState();
     runBlock(fpeAfterFirst);
-    enqueueFpe(kSlotFpe, nullptr);
-    enqueueCheck(xn_.get(), yn_.get(), true, nullptr);
-    enqueueDiff(nullptr);
+    enqueueCheckSums(nullptr);
     fetchStats(kStatOut);
     while (persistentReason() == kHsPersistent && pullStalled()) {  // (as in the device-driven loop: the steps 2..40 and the check again)
       recoverStall();
       pushState();
       enqueueMinorSteps();
-      enqueueFpe(kSlotFpe, nullptr);
-      enqueueCheck(xn_.get(), yn_.get(), true, nullptr);
-      enqueueDiff(nullptr);
+      enqueueCheckSums(nullptr);
       fetchStats(kStatOut);
     }
     if (mesh_) mesh_->verifyReplicated(rx_.get(), F_.n, stream_);  // the reflected x is the vector every rank holds in full
-    const HalpernRecord r = halpernDecide(H, hostStats_);
-    noteRecord(r);
-    mirror();
-    if (H.converged) {
-      keepOutput(xn_.get(), yn_.get());
-      termStatus_ = 0;
-      return;
-    }
-    if (H.doRestart) restartCopies();
+    hostCheckEnd();
+    if (H.converged) return;
   }
   if (terminate) termStatus_ = 1;
 }
@@ -814,8 +832,109 @@ void HalpernSolver::postsolve(pdlp_result_t* R) {
   R->solve_seconds = solveSeconds_;
 }
 
-std::pair<double*, int64_t> HalpernSolver::lookup(const std::string& name) {
+void HalpernSolver::requireUnsharded(const std::string& what) const {
+  if (sharded_) throw std::runtime_error(what + ": not on a sharded solver");
+}
+
+// ---- TEST HOOKS of the check iteration -------------------------------------------------------------------------------
+namespace {
+// "halpern_state": the scalars halpernDecide reads or writes, in this order, then StandardForm::scaled (an unscaled
+// solver can then run the `scaled` branch of the statistics on planted scales).  rho, the norms, the offset and `stalled`
+// are not part of it: the check never writes them and the problem sets them.
+constexpr int kHalpernStateLen = 28;
+void stateToArray(const HalpernState& H, bool scaled, double* v) {
+  const double a[kHalpernStateLen] = {
+      H.tau, H.sigma, H.eta, H.omega, H.primalWeight, H.bestPrimalWeight, H.bestGap, H.errSum, H.lastErr, H.fpe, H.initialFpe,
+      H.lastTrialFpe, H.tol, (double)H.iters, (double)H.iterLimit, (double)H.hIter, (double)H.pid, (double)H.terminate,
+      (double)H.nRestarts, (double)H.nChecks, (double)H.fpe0Pending, (double)H.halted, (double)H.converged, (double)H.doRestart,
+      (double)H.run, (double)H.runFpe0, (double)H.termStatus, scaled ? 1.0 : 0.0};
+  std::copy(a, a + kHalpernStateLen, v);
+}
+void arrayToState(const double* v, HalpernState& H, bool& scaled) {
+  H.tau = v[0]; H.sigma = v[1]; H.eta = v[2]; H.omega = v[3]; H.primalWeight = v[4]; H.bestPrimalWeight = v[5]; H.bestGap = v[6];
+  H.errSum = v[7]; H.lastErr = v[8]; H.fpe = v[9]; H.initialFpe = v[10]; H.lastTrialFpe = v[11]; H.tol = v[12];
+  H.iters = (long long)v[13]; H.iterLimit = (long long)v[14]; H.hIter = (int32_t)v[15]; H.pid = (int32_t)v[16];
+  H.terminate = (int32_t)v[17]; H.nRestarts = (int32_t)v[18]; H.nChecks = (int32_t)v[19]; H.fpe0Pending = (int32_t)v[20];
+  H.halted = (int32_t)v[21]; H.converged = (int32_t)v[22]; H.doRestart = (int32_t)v[23]; H.run = (int32_t)v[24];
+  H.runFpe0 = (int32_t)v[25]; H.termStatus = (int32_t)v[26];
+  scaled = v[27] != 0.0;
+}
+constexpr int kHalpernRecordLen = 11;  // "last_record" and what the check stages return
+void recordToArray(const HalpernRecord& r, double* v) {
+  const double a[kHalpernRecordLen] = {(double)r.iters, r.pObj, r.dObj, r.gap, r.relGap, r.pFeas, r.dFeas, r.fpe, r.primalWeight,
+                                       (double)r.restarted, (double)r.converged};
+  std::copy(a, a + kHalpernRecordLen, v);
+}
+}  // namespace
+
+// Stages check_device / check_host: ONE check iteration on the vectors and the state the solver holds (planted through
+// setVector and "halpern_state": nothing is armed here), in the form of the device-driven loop (the gated launches of
+// enqueueUnitTail, the decision kernel, the gated copies) or of the host-driven one (ungated launches, one download,
+// halpernDecide on the host's copy, the copies as hipMemcpyAsync).
+//   mode 0  the statistics only (fixed-point error, convergence sums, restart distances)
+//   mode 1  the whole check; returns the check's record (device form: as the decision kernel wrote it into the ring)
+//   mode 2  mode 1 behind the initial fixed-point error of a block that follows a restart (slots kSlotFpe0..)
+//   mode 3  the fixed-point error's launches only: "delta_y" and "check_aty" then hold y_next - y_reflected and A' of it
+//           (in every other mode the convergence sums overwrite them with A x and A'y)
+void HalpernSolver::checkStage(bool device, int mode, double* out, int32_t cap) {
+  requireUnsharded(device ? "check_device" : "check_host");
+  if (mode < 0 || mode > 3) throw std::runtime_error("check stage: mode 0..3");
+  HalpernState& H = *hostState_;
+  const int32_t* run = device ? &dState_.get()->run : nullptr;
+  double rec[kHalpernRecordLen] = {0};
+  if (mode == 3) {
+    enqueueFpe(kSlotFpe, run);
+    PDLP_HIP(hipStreamSynchronize(stream_));
+    return;
+  }
+  if (mode == 2) {  // (the host-driven loop queues it only behind a restart, the device-driven one behind its gate word)
+    if (device) enqueueFpe(kSlotFpe0, &dState_.get()->runFpe0);
+    else if (H.fpe0Pending) enqueueFpe(kSlotFpe0, nullptr);
+  }
+  if (device) {
+    if (mode == 0) {
+      enqueueCheckSums(run);
+    } else {
+      const int32_t checksBefore = H.nChecks;
+      enqueueUnitTail();
+      pullState();
+      if (H.nChecks != checksBefore) {
+        noteRecord(hostRing_[(H.nChecks - 1) % kHalpernRing]);
+        ++deviceChecks_;
+        recordToArray(lastRecord_, rec);
+      }
+      iters_ = H.iters; nRestarts_ = H.nRestarts; nChecks_ = H.nChecks;
+      if (H.converged) haveOutput_ = true;
+    }
+  } else {
+    enqueueCheckSums(nullptr);
+    fetchStats(kStatOut);
+    if (mode != 0) {
+      hostCheckEnd();
+      recordToArray(lastRecord_, rec);
+      pushState();  // (the loop pushes before its next block: the two copies agree when the stage returns)
+    }
+  }
+  if (mode != 0)
+    for (int i = 0; i < kHalpernRecordLen; ++i)
+      if (out && i < cap) out[i] = rec[i];
+}
+
+// read-only names (forWrite refuses them): what a check leaves behind
+std::pair<double*, int64_t> HalpernSolver::lookup(const std::string& name, bool forWrite) {
   const int64_t n = F_.n, m = mLoc_;  // row vectors are local when sharded
+  if (name == "slack_pos" || name == "slack_neg" || name == "out_x" || name == "out_y" || name == "check_ax" ||
+      name == "check_aty" || name == "delta_y") {
+    requireUnsharded(name);
+    // (the output copy can be written: a test poisons it to see whether a check has touched it)
+    if (forWrite && name != "out_x" && name != "out_y") throw std::runtime_error("vector " + name + " can only be read");
+    if (name == "slack_pos") return {sp_.get(), n};
+    if (name == "slack_neg") return {sn_.get(), n};
+    if (name == "out_x") return {outX_.get(), n};
+    if (name == "out_y") return {outY_.get(), m};
+    if (name == "check_aty") return {tmpN_.get(), n};
+    return {tmpM_.get(), m};  // check_ax, delta_y
+  }
   if (name == "x") return {xc_.get(), n};
   if (name == "y") return {yc_.get(), m};
   if (name == "x_next") return {xn_.get(), n};
@@ -842,6 +961,21 @@ void HalpernSolver::getVector(const std::string& name, double* host, int64_t len
     for (int64_t i = 0; i < len && i < 8; ++i) host[i] = v[i];
     return;
   }
+  if (name == "halpern_state" || name == "check_stats" || name == "last_record") {  // TEST HOOKS (checkStage)
+    requireUnsharded(name);
+    const int64_t want = name == "halpern_state" ? kHalpernStateLen : name == "check_stats" ? kHStatOut : kHalpernRecordLen;
+    if (len != want) throw std::runtime_error("length mismatch for " + name + " (" + std::to_string(want) + ")");
+    if (name == "halpern_state") {
+      if (!hostAhead_) pullState();  // (behind a host-driven check the host's copy is the newer one)
+      stateToArray(*hostState_, F_.scaled, host);
+    } else if (name == "check_stats") {  // the statistics slots as the device holds them
+      PDLP_HIP(hipMemcpyAsync(host, statOut_.get(), sizeof(double) * kHStatOut, hipMemcpyDeviceToHost, stream_));
+      PDLP_HIP(hipStreamSynchronize(stream_));
+    } else {
+      recordToArray(lastRecord_, host);
+    }
+    return;
+  }
   auto [p, l] = lookup(name);
   if (l != len) throw std::runtime_error("length mismatch for vector " + name);
   PDLP_HIP(hipMemcpyAsync(host, p, sizeof(double) * len, hipMemcpyDeviceToHost, stream_));
@@ -856,7 +990,24 @@ void HalpernSolver::setVector(const std::string& name, const double* host, int64
     pushState();
     return;
   }
-  auto [p, l] = lookup(name);
+  if (name == "halpern_state") {  // TEST HOOK: plants the scalars of a check iteration (and StandardForm::scaled)
+    requireUnsharded(name);
+    if (len != kHalpernStateLen) throw std::runtime_error("length mismatch for halpern_state (" + std::to_string(kHalpernStateLen) + ")");
+    bool scaled = F_.scaled;
+    arrayToState(host, *hostState_, scaled);
+    F_.scaled = scaled;
+    iters_ = hostState_->iters; nRestarts_ = hostState_->nRestarts; nChecks_ = hostState_->nChecks;
+    pushState();
+    return;
+  }
+  if (name == "check_stats") {  // TEST HOOK: poisons the statistics slots (a halted check must leave them alone)
+    requireUnsharded(name);
+    if (len != kHStatOut) throw std::runtime_error("length mismatch for check_stats");
+    PDLP_HIP(hipMemcpyAsync(statOut_.get(), host, sizeof(double) * kHStatOut, hipMemcpyHostToDevice, stream_));
+    PDLP_HIP(hipStreamSynchronize(stream_));
+    return;
+  }
+  auto [p, l] = lookup(name, true);
   if (l != len) throw std::runtime_error("length mismatch for vector " + name);
   PDLP_HIP(hipMemcpyAsync(p, host, sizeof(double) * len, hipMemcpyHostToDevice, stream_));
   PDLP_HIP(hipStreamSynchronize(stream_));
@@ -904,6 +1055,18 @@ void HalpernSolver::stage(const std::string& name, double* out, int32_t cap) {
         enqueuePersistent(2, k);
       }
     }
+  } else if (name == "check_device" || name == "check_host") {  // out[0] = mode (checkStage)
+    checkStage(name == "check_device", out && cap > 0 ? (int)out[0] : 0, out, cap);
+  } else if (name == "check_initial") {  // the check of iteration 0 on x / y: returns its record, then `converged`
+    requireUnsharded(name);
+    HalpernRecord r{};
+    const bool conv = initialCheck(r);
+    r.converged = conv ? 1 : 0;
+    double rec[kHalpernRecordLen];
+    recordToArray(r, rec);
+    for (int i = 0; i < kHalpernRecordLen; ++i) put(i, rec[i]);
+  } else if (name == "check_forms") {  // decisions taken so far: by the decision kernel (read from its ring), by the host
+    put(0, (double)deviceChecks_); put(1, (double)hostChecks_);
   } else if (name == "stall_next_block") {
     // TEST HOOK: the next persistent launch ends as one whose roll call (3) or XCD placement check (2) failed — it changes
     // nothing and reports the code — so that the fall-back runs without any launch waiting for its timeout.

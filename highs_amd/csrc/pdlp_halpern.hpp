@@ -76,6 +76,12 @@ class HalpernSolver : public SolverBase {
   void enqueueStepsFrom2(int32_t kLast);       // steps 2..kLast, the last one major: ONE persistent launch where the solver qualifies
   void enqueuePersistent(int32_t kFirst, int32_t kLast);
   void enqueueUnitTail();                      // a unit behind its steps: check + decision + gated copies
+  void enqueueCheckSums(const int32_t* gate);  // the statistics of a check behind a block: fixed-point error, convergence sums, restart distances
+  bool initialCheck(HalpernRecord& r);         // the check of iteration 0 (derived slack): statistics + residuals; true = converged
+  void hostCheckEnd();                         // host-driven loop: the decision on the fetched statistics and the copies it asks for
+  void keepOutput(const double* x, const double* y);
+  void checkStage(bool device, int mode, double* out, int32_t cap);  // TEST HOOKS: stages check_device / check_host
+  void requireUnsharded(const std::string& what) const;
   HalpernSmallShape smallShape() const;
   int32_t persistentReason() const { return halpernSmallReason(smallShape()); }
   bool pullStalled();                          // host-queued blocks: the device's `stalled` word -> host copy; true if set
@@ -95,7 +101,7 @@ class HalpernSolver : public SolverBase {
   double sum(const double* partials, int32_t nBlocks);
   double elapsed() const;
   void log(int level, const char* fmt, ...) const;
-  std::pair<double*, int64_t> lookup(const std::string& name);
+  std::pair<double*, int64_t> lookup(const std::string& name, bool forWrite = false);
 
   pdlp_params_t opt_;
   StandardForm F_;
@@ -127,6 +133,9 @@ class HalpernSolver : public SolverBase {
   int64_t iters_ = 0;
   HalpernRecord* hostRing_ = nullptr;  // pinned: the checks' lines, written by the decision kernel
   hipGraphExec_t unitGraph_ = nullptr; // one unit of the device-driven loop
+  HalpernRecord lastRecord_{};         // the most recent check's line, whichever loop or stage wrote it
+  int64_t deviceChecks_ = 0, hostChecks_ = 0;  // decisions read from the device's ring / taken by the host (stage "check_forms")
+  bool hostAhead_ = false;             // the host's copy of the state is newer than the device's (host-driven decision)
   int termStatus_ = -1;  // -1 not set, 0 optimal, 1 iteration limit, 2 time limit
   bool haveOutput_ = false;
   Res res_;

@@ -73,6 +73,20 @@ typedef struct {
   int chunkA, chunkAt;
 } HLp;
 
+/* Read-out of a solve's check iterations for the tests (hipdlp_oracle_solve_traced): the sums every check's decision is
+ * taken on, in the slots of the product's statistics vector — 0..2 fixed-point error (|dy|^2, |dx|^2, <dx, A'dy>), 3..4 row
+ * sums, 5..8 column sums, 9..11 the fixed-point error behind the first step of the block (a restart came before; else
+ * zero), 12..13 the restart distances (where the PID update ran; else zero) — and what the decision made of them.  The first
+ * record (iters 0) carries the state the loop starts from. */
+typedef struct hipdlp_oracle_check {
+  int iters, restarted, restarts;
+  double stat[16];
+  double fpe, initial_fpe, primal_weight, tau, sigma, eta, omega;
+} hipdlp_oracle_check_t;
+typedef void (*hipdlp_oracle_check_fn)(void* ctx, const hipdlp_oracle_check_t* rec);
+static hipdlp_oracle_check_t* h_rec = NULL; /* non-NULL while a traced solve runs (single-threaded test infrastructure) */
+static double h_fpe_sums[3];
+
 static void* xmalloc(size_t n) { void* p = malloc(n ? n : 1); if (!p) abort(); return p; }
 static double* dvec(long n) { double* p = (double*)xmalloc(sizeof(double) * (size_t)(n > 0 ? n : 1)); memset(p, 0, sizeof(double) * (size_t)(n > 0 ? n : 1)); return p; }
 
@@ -376,6 +390,7 @@ static int h_check(const HLp* L, const double* x, const double* y, const double*
     const double cs0 = g_grid_sum(L->n, e_col0, &cc, scratch), cs1 = g_grid_sum(L->n, e_col1, &cc, scratch);
     const double cs2 = g_grid_sum(L->n, e_col2, &cc, scratch), cs3 = g_grid_sum(L->n, e_col3, &cc, scratch);
     free(scratch);
+    if (h_rec) { h_rec->stat[3] = rs0; h_rec->stat[4] = rs1; h_rec->stat[5] = cs0; h_rec->stat[6] = cs1; h_rec->stat[7] = cs2; h_rec->stat[8] = cs3; }
     r->pFeas = sqrt(rs0);
     r->dFeas = sqrt(cs0);
     r->pObj = L->offset + cs1;
@@ -482,6 +497,7 @@ static double h_fpe(const HState* S) {
     cross = g_sum(L->n, e_diffdot, &c);
   }
   free(dx); free(dy); free(atd);
+  h_fpe_sums[0] = dn; h_fpe_sums[1] = pn; h_fpe_sums[2] = cross;
   const double movement = pn * S->omega + dn / S->omega;
   const double interaction = 2.0 * S->eta * cross;
   return sqrt(fmax(0.0, movement + interaction));
@@ -493,6 +509,7 @@ static void h_update_weight(HState* S, const HRes* res) {
   double pd = 0.0, dd = 0.0;
   pd = x_diff2(S->dev, S->xn, S->xa, L->n);
   dd = x_diff2(S->dev, S->yn, S->ya, L->m);
+  if (h_rec) { h_rec->stat[12] = pd; h_rec->stat[13] = dd; }
   pd = sqrt(pd); dd = sqrt(dd);
   const double relP = res->pFeas / (1.0 + L->bNorm), relD = res->dFeas / (1.0 + L->cNorm);
   const double ratio = relP > 0.0 ? relD / relP : 1e300;
@@ -534,6 +551,17 @@ typedef struct hipdlp_oracle_probe {
   double out_tau, out_sigma, out_fpe, out_lambda;
   int n, m;
 } hipdlp_oracle_probe_t;
+
+static hipdlp_oracle_check_fn h_check_cb = NULL;
+static void* h_check_ctx = NULL;
+static void h_emit(const HState* S, int iters, int restarted, int restarts, double fpe, double initFpe) {
+  if (!h_rec || !h_check_cb) return;
+  h_rec->iters = iters; h_rec->restarted = restarted; h_rec->restarts = restarts;
+  h_rec->fpe = fpe; h_rec->initial_fpe = initFpe; h_rec->primal_weight = S->pw;
+  h_rec->tau = S->tau; h_rec->sigma = S->sigma; h_rec->eta = S->eta; h_rec->omega = S->omega;
+  h_check_cb(h_check_ctx, h_rec);
+  memset(h_rec->stat, 0, sizeof(h_rec->stat));
+}
 
 static int h_solve(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R, hipdlp_oracle_probe_t* probe) {
   const double t0 = nowSec();
@@ -583,10 +611,15 @@ static int h_solve(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_resul
     memcpy(outY, S.yc, sizeof(double) * (size_t)m);
     term = 0;
   }
+  if (h_rec) memset(h_rec->stat, 0, sizeof(h_rec->stat));
+  h_emit(&S, 0, 0, 0, fpe, initFpe);
   while (term < 0 && iters < opt->iter_limit) {
     if (nowSec() - t0 > opt->time_limit) { term = 2; break; }
     h_step(&S, 1, 1);
-    if (doRestart) { fpe = h_fpe(&S); initFpe = fpe; doRestart = 0; }
+    if (doRestart) {
+      fpe = h_fpe(&S); initFpe = fpe; doRestart = 0;
+      if (h_rec) memcpy(h_rec->stat + 9, h_fpe_sums, sizeof(h_fpe_sums));
+    }
     if (probe && probe->steps < H_CHECK_INTERVAL) {
       for (int i = 2; i <= probe->steps; ++i) h_step(&S, i == probe->steps, i);
       break;
@@ -594,6 +627,7 @@ static int h_solve(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_resul
     for (int i = 2; i <= H_CHECK_INTERVAL - 1; ++i) h_step(&S, 0, i);
     h_step(&S, 1, H_CHECK_INTERVAL);
     fpe = h_fpe(&S);
+    if (h_rec) memcpy(h_rec->stat, h_fpe_sums, sizeof(h_fpe_sums));
     if (probe) break;
     S.hIter += H_CHECK_INTERVAL;
     iters += H_CHECK_INTERVAL;
@@ -603,6 +637,7 @@ static int h_solve(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_resul
       memcpy(outX, S.xn, sizeof(double) * (size_t)n);
       memcpy(outY, S.yn, sizeof(double) * (size_t)m);
       term = 0;
+      h_emit(&S, iters, 0, restarts, fpe, initFpe);
       break;
     }
     /* checkRestartCriteria, pdhg.cc:901-927 */
@@ -625,6 +660,7 @@ static int h_solve(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_resul
       lastFpe = INFINITY;
       ++restarts;
     }
+    h_emit(&S, iters, doRestart, restarts, fpe, initFpe);
   }
   if (probe) {
     probe->n = n; probe->m = m;
@@ -675,6 +711,18 @@ int hipdlp_oracle_solve(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_
   if (!P || !opt || !R) return 1;
   if (P->num_row == 0 || P->num_col == 0 || !P->a_start || P->a_start[P->num_col] == 0) return 1; /* HiGHS: solveUnconstrainedLp */
   return h_solve(P, opt, R, NULL);
+}
+
+/* hipdlp_oracle_solve with `cb` called once before the loop and once behind every check iteration (see hipdlp_oracle_check_t) */
+int hipdlp_oracle_solve_traced(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R, hipdlp_oracle_check_fn cb,
+                               void* ctx) {
+  hipdlp_oracle_check_t rec;
+  if (!cb) return 1;
+  memset(&rec, 0, sizeof(rec));
+  h_rec = &rec; h_check_cb = cb; h_check_ctx = ctx;
+  const int rc = hipdlp_oracle_solve(P, opt, R);
+  h_rec = NULL; h_check_cb = NULL; h_check_ctx = NULL;
+  return rc;
 }
 
 int hipdlp_oracle_probe(const pdlp_problem_t* P, const pdlp_params_t* opt, hipdlp_oracle_probe_t* probe) {

@@ -166,6 +166,36 @@ def hipdlp_solve_fn():
     return _hipdlp_lib().hipdlp_oracle_solve
 
 
+class HipdlpCheck(C.Structure):
+    _fields_ = [("iters", C.c_int), ("restarted", C.c_int), ("restarts", C.c_int), ("stat", C.c_double * 16)] + [
+        (k, C.c_double) for k in ("fpe", "initial_fpe", "primal_weight", "tau", "sigma", "eta", "omega")]
+
+
+HIPDLP_CHECK_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(HipdlpCheck))
+
+
+def hipdlp_solve_traced(lp, **kw):
+    """hipdlp_oracle_solve_traced in the device's reduction order: (result, records) — one record before the loop (iters 0:
+    the state it starts from) and one behind every check iteration: the 16 sums the decision was taken on (the slots of
+    the product's statistics vector) and the fixed-point errors, primal weight and step sizes behind it."""
+    lib = _hipdlp_lib()
+    lib.hipdlp_oracle_solve_traced.argtypes = [C.POINTER(abi.PdlpProblem), C.POINTER(abi.PdlpParams), C.POINTER(abi.PdlpResult),
+                                               HIPDLP_CHECK_FN, C.c_void_p]
+    lib.hipdlp_oracle_solve_traced.restype = C.c_int
+    params = abi.default_params(solver="hipdlp", device_reduction_order=True, **kw)
+    P = abi.ProblemHandle(lp)
+    R = abi.ResultHandle(lp.num_col, lp.num_row)
+    recs = []
+
+    def cb(_ctx, t):
+        c = t.contents
+        recs.append(dict(stat=np.array(c.stat[:]), **{k: getattr(c, k) for k, _ in HipdlpCheck._fields_ if k != "stat"}))
+
+    if lib.hipdlp_oracle_solve_traced(C.byref(P.struct), C.byref(params), C.byref(R.struct), HIPDLP_CHECK_FN(cb), None):
+        raise RuntimeError("hipdlp traced solve failed")
+    return R, recs
+
+
 def hipdlp_probe(lp, steps, tau=0.0, sigma=0.0, **kw):
     """State of the oracle after `steps` Halpern steps of the first block (last step major)."""
     params = abi.default_params(solver="hipdlp", **kw)
