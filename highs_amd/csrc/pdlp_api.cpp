@@ -650,6 +650,17 @@ int pdlp_mi355x_host_hipdlp_small_rule(const int32_t* shape, int32_t xcd_local_a
   });
 }
 
+// TEST HOOK, not part of the public header: the rule that decides where a QP's Hessian is extracted (pdlp_setup.hpp
+// hessianExtractionReason — the function gpuPrepare and the solver call), on facts given by hand.  q_start: q_dim + 1
+// entries, or NULL.  *reason: 0 on the device, else why the host walk runs (the codes of stage "hessian_extraction").
+int pdlp_mi355x_host_hessian_extraction_rule(int32_t gpu_setup, int32_t sharded, int32_t hipdlp, int32_t switch_on, int32_t q_dim,
+                                             const int32_t* q_start, int32_t* reason) {
+  return guarded([&] {
+    if (!reason) throw std::runtime_error("null argument");
+    *reason = pdlp::hessianExtractionReason(gpu_setup != 0, sharded != 0, hipdlp != 0, switch_on != 0, q_dim, q_start);
+  });
+}
+
 // TEST HOOK, not part of the public header (no product code calls it): what a solver holds of operand `which` (0: A by rows,
 // 1: A' by columns) after its set-up, on the host or on the device — downloaded as it lies in HBM, with no launch and no
 // change of state.  Stream layout (use_slab = 0): beg / idx / val are the operand's CSR, block_beg its work blocks

@@ -3,6 +3,7 @@
 // done by one thread per major in the reference's traversal order so that the
 // result is bit-identical to the host path and to the reference.
 #include "pdlp_setup.hpp"
+#include "pdlp_update.hpp"
 
 #include <cstring>
 
@@ -312,6 +313,83 @@ __global__ void k_long_copy(const int32_t* __restrict__ beg, const int32_t* __re
   for (int k = threadIdx.x; k < len; k += blockDim.x) { idxOut[dst + k] = idx[src + k]; valOut[dst + k] = val[src + k]; }
 }
 
+// ---- the Hessian's extraction (gpuExtractHessian) ------------------------------------------------------------------------
+// Integer work throughout: one thread per slot, entry or column, grid-stride, unit-stride loads of the caller's arrays;
+// every scatter goes to a rank that a scan of 0/1 flags gave, so no two threads share a destination.
+enum : unsigned long long { kHessSlotOutOfRange = 1, kHessSlotAbove = 2 };  // what is wrong with an offending slot
+
+// col[p] = the column of slot p, as k_col_entries writes cscCol from a_start (q_start runs from 0 to nq without decreasing)
+__global__ void k_hess_cols(const int32_t* __restrict__ qStart, int qDim, int32_t* col) {
+  GSTRIDE(j, qDim)
+    for (int p = qStart[j]; p < qStart[j + 1]; ++p) col[p] = (int)j;
+}
+// The host walk's tests in its order (extractHessian / extractHessianPattern): index outside [0, qDim); a zero value is not
+// taken unless every slot is kept (== 0.0: -0.0 is dropped, a NaN is kept); diagonal; above the diagonal.  The smallest
+// offending slot wins, as the walk meets it first: (p << 2) | kind, an integer minimum.
+__global__ void k_hess_classify(const int32_t* __restrict__ qIndex, const double* __restrict__ qValue,
+                                const int32_t* __restrict__ col, int64_t nq, int qDim, int keepAll, int32_t* diagFlag,
+                                int32_t* offFlag, unsigned long long* offender) {
+  GSTRIDE(p, nq) {
+    const int i = qIndex[p], j = col[p];
+    int d = 0, o = 0;
+    if (i < 0 || i >= qDim) atomicMin(offender, ((unsigned long long)p << 2) | kHessSlotOutOfRange);
+    else if (!keepAll && qValue[p] == 0.0) {}
+    else if (i == j) d = 1;
+    else if (i < j) atomicMin(offender, ((unsigned long long)p << 2) | kHessSlotAbove);
+    else o = 1;
+    diagFlag[p] = d;
+    offFlag[p] = o;
+  }
+}
+// the diagonal's sources in caller order; its starts follow from the ranks, since slots come column by column:
+// dstBeg[j] = diagonal slots in front of column j (columns behind q_dim, slack columns included, have none)
+__global__ void k_hess_diag_sources(const int32_t* __restrict__ diagFlag, const int32_t* __restrict__ diagRank, int64_t nq,
+                                    int32_t* srcSlot) {
+  GSTRIDE(p, nq) if (diagFlag[p]) srcSlot[diagRank[p]] = (int32_t)p;
+}
+__global__ void k_hess_diag_starts(const int32_t* __restrict__ qStart, const int32_t* __restrict__ diagRank, int qDim,
+                                   int n, int32_t* dstBeg) {
+  GSTRIDE(j, (int64_t)n + 1) dstBeg[j] = diagRank[qStart[j < qDim ? j : qDim]];
+}
+// taken off-diagonal slot p = (i, j), rank e of k: head entry e = (row i, column j), tail entry k + e = (row j, column i)
+__global__ void k_hess_entries(const int32_t* __restrict__ qIndex, const int32_t* __restrict__ col,
+                               const int32_t* __restrict__ offFlag, const int32_t* __restrict__ offRank, int64_t nq,
+                               int64_t k, uint32_t* entCol, uint32_t* entRow, int32_t* entSrc) {
+  GSTRIDE(p, nq) if (offFlag[p]) {
+    const int64_t e = offRank[p];
+    const uint32_t i = (uint32_t)qIndex[p], j = (uint32_t)col[p];
+    entCol[e] = j; entRow[e] = i; entSrc[e] = (int32_t)p;
+    entCol[k + e] = i; entRow[k + e] = j; entSrc[k + e] = (int32_t)p;
+  }
+}
+__global__ void k_hess_permute(const int32_t* __restrict__ perm, const uint32_t* __restrict__ in, int64_t count, uint32_t* out) {
+  GSTRIDE(q, count) out[q] = in[perm[q]];
+}
+// after both sorts entry q has row rowS[q], column colS[byRow[q]]: a run of equal (row, column) is one slot of N
+__global__ void k_hess_run_heads(const uint32_t* __restrict__ rowS, const uint32_t* __restrict__ colS,
+                                 const int32_t* __restrict__ byRow, int64_t count, int32_t* head) {
+  GSTRIDE(q, count) head[q] = (q == 0 || rowS[q] != rowS[q - 1] || colS[byRow[q]] != colS[byRow[q - 1]]) ? 1 : 0;
+}
+// the off-diagonal destinations: entry q's source behind the diagonal's dcnt, and per run head slot d of N — its row, its
+// column, its first source; the last entry closes the last run
+__global__ void k_hess_finish(const uint32_t* __restrict__ rowS, const uint32_t* __restrict__ colS,
+                              const int32_t* __restrict__ byRow, const int32_t* __restrict__ byCol,
+                              const int32_t* __restrict__ entSrc, const int32_t* __restrict__ head,
+                              const int32_t* __restrict__ headRank, int64_t count, int n, int32_t dcnt, int32_t* srcSlot,
+                              int32_t* dstBeg, int32_t* offRow, int32_t* offCol) {
+  GSTRIDE(q, count) {
+    const int b = byRow[q];
+    srcSlot[dcnt + q] = entSrc[byCol[b]];
+    const int d = headRank[q];
+    if (head[q]) {
+      offRow[d] = (int32_t)rowS[q];
+      offCol[d] = (int32_t)colS[b];
+      dstBeg[n + d] = (int32_t)(dcnt + q);
+    }
+    if (q == count - 1) dstBeg[n + d + head[q]] = (int32_t)(dcnt + count);
+  }
+}
+
 // ---- rocPRIM helpers -----------------------------------------------------------------
 void exclusiveSum(const int32_t* in, int32_t* out, int64_t n, hipStream_t s) {
   if (n <= 0) return;
@@ -329,7 +407,8 @@ int bitsFor(uint64_t maxKey) {
 }
 // stable sort of (key, position) pairs; returns sorted keys and the permutation
 void sortByKey(const uint32_t* keysIn, int64_t n, uint64_t maxKey, DeviceArray<uint32_t>& keysOut,
-               DeviceArray<int32_t>& perm, hipStream_t s) {
+               DeviceArray<int32_t>& perm, hipStream_t s, size_t* scratchBytes = nullptr /* what it held besides its results */) {
+  if (scratchBytes) *scratchBytes = 0;
   keysOut.alloc((size_t)n);
   perm.alloc((size_t)n);
   if (n <= 0) return;
@@ -342,6 +421,7 @@ void sortByKey(const uint32_t* keysIn, int64_t n, uint64_t maxKey, DeviceArray<u
                                      endBit, s));
   DeviceArray<char> tmp;
   tmp.alloc(bytes);
+  if (scratchBytes) *scratchBytes = bytes + sizeof(int32_t) * (size_t)n;
   PDLP_HIP(rocprim::radix_sort_pairs(tmp.get(), bytes, keysIn, keysOut.get(), iota.get(), perm.get(), (size_t)n, 0u,
                                      endBit, s));
   PDLP_HIP(hipStreamSynchronize(s));
@@ -390,6 +470,167 @@ void copyOf(DeviceArray<T>& dst, const DeviceArray<T>& src, hipStream_t s) {
 }
 
 }  // namespace
+
+int32_t hessianExtractionReason(bool gpuSetup, bool sharded, bool hipdlp, bool switchOn, int32_t qDim, const int32_t* qStart) {
+  if (!gpuSetup) return kHessHostSetup;
+  if (sharded) return kHessSharded;
+  if (hipdlp) return kHessHipdlp;
+  if (qDim <= 0 || !qStart) return kHessNoSlots;
+  if (qStart[0] != 0) return kHessStarts;
+  for (int32_t j = 0; j < qDim; ++j)
+    if (qStart[j + 1] < qStart[j]) return kHessStarts;
+  if (qStart[qDim] <= 0) return kHessNoSlots;
+  return switchOn ? kHessOnDevice : kHessSwitchOff;
+}
+
+// The map is built as the host walk builds it, by sorting instead of walking (tests/test_hessian_extraction_host.py
+// holds the two against each other): all head entries in slot order, then all tail entries, sorted stably by column and
+// then stably by row, are the walk's (row, column, source) sequence — a row's heads have columns below it, ascending with
+// the slots; its tails columns above it, which the walk's insertion sort orders stably — and runs of equal (row, column)
+// come in the order the walk adds repeated pairs.  k_hessian_validate / k_hessian_assemble (pdlp_update.hip) then do on the map what
+// firstNegativeDiagonal / assembleHessian do, operation for operation — and extractHessian does the same ones on the taken
+// slots: a source times the sense, the diagonal summed from 0.0, a slot of N from its first source.
+void gpuExtractHessian(const pdlp_problem_t& P, int32_t n, hipStream_t s, DeviceProblem& D) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const int32_t qDim = P.q_dim;
+  const int64_t nq = P.q_start[qDim];
+  const bool keepAll = D.keepHessianPattern;
+  size_t held = 0, peak = 0;  // HBM of the temporaries (not of what stays: qdiag, N, the kept map)
+  auto got = [&](const auto& a) { held += sizeof(*a.get()) * a.size(); peak = std::max(peak, held); };
+  auto rid = [&](auto& a) { held -= sizeof(*a.get()) * a.size(); a.release(); };
+
+  // 1. the caller's arrays: 16 bytes per slot, 4 per column
+  DeviceArray<int32_t> qStart, qIndex;
+  DeviceArray<double> qValue;
+  qStart.alloc((size_t)qDim + 1); qIndex.alloc((size_t)nq); qValue.alloc((size_t)nq);
+  got(qStart); got(qIndex); got(qValue);
+  qStart.upload(P.q_start, (size_t)qDim + 1, s); qIndex.upload(P.q_index, (size_t)nq, s); qValue.upload(P.q_value, (size_t)nq, s);
+  PDLP_HIP(hipStreamSynchronize(s));
+  const auto t1 = std::chrono::steady_clock::now();
+  D.secUploadHessian = std::chrono::duration<double>(t1 - t0).count();
+
+  // 2. classify; flags and ranks have one element behind the last slot, so that a scan ends in its total
+  DeviceArray<int32_t> col, diagFlag, offFlag, diagRank, offRank;
+  DeviceArray<unsigned long long> offender;
+  col.alloc((size_t)nq); diagFlag.alloc((size_t)nq + 1); offFlag.alloc((size_t)nq + 1);
+  diagRank.alloc((size_t)nq + 1); offRank.alloc((size_t)nq + 1); offender.alloc(1);
+  got(col); got(diagFlag); got(offFlag); got(diagRank); got(offRank);
+  diagFlag.zero(s);
+  offFlag.zero(s);
+  PDLP_HIP(hipMemsetAsync(offender.get(), 0xff, sizeof(unsigned long long), s));
+  hipLaunchKernelGGL(k_hess_cols, dim3(gridFor(qDim)), dim3(kT), 0, s, qStart.get(), qDim, col.get());
+  hipLaunchKernelGGL(k_hess_classify, dim3(gridFor(nq)), dim3(kT), 0, s, qIndex.get(), qValue.get(), col.get(), nq, qDim,
+                     keepAll ? 1 : 0, diagFlag.get(), offFlag.get(), offender.get());
+  PDLP_HIP(hipGetLastError());
+  const unsigned long long first = fetchOne(offender.get(), s);
+  if (first != ~0ull) {  // the walk's sentences (pdlp_host.cpp), for the slot it would have met first
+    const int64_t p = (int64_t)(first >> 2);
+    if ((first & 3) == kHessSlotOutOfRange) throw std::runtime_error("Hessian index out of range");
+    const int32_t j = fetchOne(col.get() + p, s);
+    throw std::runtime_error("pdlp_mi355x: the Hessian must be given by its lower triangle (entry (" + std::to_string(P.q_index[p]) +
+                             "," + std::to_string(j) + ") lies above the diagonal)");
+  }
+
+  // 3. counts, compaction, the two sorts
+  exclusiveSum(diagFlag.get(), diagRank.get(), nq + 1, s);
+  exclusiveSum(offFlag.get(), offRank.get(), nq + 1, s);
+  const int64_t dcnt = fetchOne(diagRank.get() + nq, s), k = fetchOne(offRank.get() + nq, s), nEnt = 2 * k;
+  D.hessianTaken = dcnt + k;
+  D.hessianOffSlots = 0;
+  auto done = [&] {
+    PDLP_HIP(hipStreamSynchronize(s));
+    D.hessianTempBytes = (int64_t)peak;
+    D.secExtract = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+  };
+  if (!keepAll && dcnt + k == 0) return done();  // every value is zero: an LP
+  if (nEnt > 0x7fffffff || dcnt + nEnt > 0x7fffffff) throw std::runtime_error("Hessian too large");
+  DeviceArray<int32_t> dstBeg, srcSlot;
+  srcSlot.alloc((size_t)std::max<int64_t>(dcnt + nEnt, 1));
+  if (!keepAll) got(srcSlot);  // (a plain solver's map is a temporary too)
+  hipLaunchKernelGGL(k_hess_diag_sources, dim3(gridFor(nq)), dim3(kT), 0, s, diagFlag.get(), diagRank.get(), nq, srcSlot.get());
+  DeviceArray<uint32_t> colS, rowS;     // every entry's column after the first sort, its row after the second
+  DeviceArray<int32_t> byCol, byRow, entSrc;  // the two permutations, every entry's source slot
+  DeviceArray<int32_t> head, headRank;
+  int32_t nOff = 0;
+  if (k > 0) {
+    DeviceArray<uint32_t> entCol, entRow, rowIn;
+    entCol.alloc((size_t)nEnt); entRow.alloc((size_t)nEnt); entSrc.alloc((size_t)nEnt);
+    got(entCol); got(entRow); got(entSrc);
+    hipLaunchKernelGGL(k_hess_entries, dim3(gridFor(nq)), dim3(kT), 0, s, qIndex.get(), col.get(), offFlag.get(), offRank.get(), nq, k,
+                       entCol.get(), entRow.get(), entSrc.get());
+    PDLP_HIP(hipStreamSynchronize(s));
+    rid(col); rid(diagFlag); rid(offFlag); rid(offRank); rid(qIndex);
+    size_t scratch = 0;
+    sortByKey(entCol.get(), nEnt, (uint64_t)qDim, colS, byCol, s, &scratch);
+    peak = std::max(peak, held + scratch + 2 * sizeof(int32_t) * (size_t)nEnt);
+    got(colS); got(byCol);
+    rid(entCol);
+    rowIn.alloc((size_t)nEnt);
+    got(rowIn);
+    hipLaunchKernelGGL(k_hess_permute, dim3(gridFor(nEnt)), dim3(kT), 0, s, byCol.get(), entRow.get(), nEnt, rowIn.get());
+    PDLP_HIP(hipStreamSynchronize(s));
+    rid(entRow);
+    sortByKey(rowIn.get(), nEnt, (uint64_t)qDim, rowS, byRow, s, &scratch);
+    peak = std::max(peak, held + scratch + 2 * sizeof(int32_t) * (size_t)nEnt);
+    got(rowS); got(byRow);
+    rid(rowIn);
+    // 4. runs of equal (row, column) -> the slots of N
+    head.alloc((size_t)nEnt + 1); headRank.alloc((size_t)nEnt + 1);
+    got(head); got(headRank);
+    head.zero(s);
+    hipLaunchKernelGGL(k_hess_run_heads, dim3(gridFor(nEnt)), dim3(kT), 0, s, rowS.get(), colS.get(), byRow.get(), nEnt, head.get());
+    exclusiveSum(head.get(), headRank.get(), nEnt + 1, s);
+    nOff = fetchOne(headRank.get() + nEnt, s);
+  }
+  dstBeg.alloc((size_t)n + (size_t)nOff + 1);
+  if (!keepAll) got(dstBeg);
+  hipLaunchKernelGGL(k_hess_diag_starts, dim3(gridFor((int64_t)n + 1)), dim3(kT), 0, s, qStart.get(), diagRank.get(), qDim, n, dstBeg.get());
+  if (nOff > 0) {
+    D.N.nMajor = D.N.nMinor = n;
+    D.N.nnz = nOff;
+    D.N.beg.alloc((size_t)n + 1);
+    D.N.idx.alloc((size_t)nOff + 1);  // one pad element: the kernels clamp, never predicate, their loads
+    D.N.val.alloc((size_t)nOff + 1);
+    D.N.major.alloc((size_t)nOff);
+    D.N.idx.zero(s);
+    D.N.val.zero(s);
+    hipLaunchKernelGGL(k_hess_finish, dim3(gridFor(nEnt)), dim3(kT), 0, s, rowS.get(), colS.get(), byRow.get(), byCol.get(), entSrc.get(),
+                       head.get(), headRank.get(), nEnt, n, (int32_t)dcnt, srcSlot.get(), dstBeg.get(), D.N.major.get(), D.N.idx.get());
+    hipLaunchKernelGGL(k_lower_bounds, dim3(gridFor((int64_t)n + 1)), dim3(kT), 0, s, D.N.major.get(), (int64_t)nOff, (int64_t)n + 1,
+                       D.N.beg.get());
+  }
+  PDLP_HIP(hipGetLastError());
+  D.hessianOffSlots = nOff;
+
+  // 5. the diagonal's sign, then the values
+  DeviceArray<int32_t> bad;
+  bad.alloc(1);
+  PDLP_HIP(hipMemcpyAsync(bad.get(), &n, sizeof(int32_t), hipMemcpyHostToDevice, s));
+  launchHessianValidate(dstBeg.get(), srcSlot.get(), qValue.get(), D.sense, n, bad.get(), s);
+  if (fetchOne(bad.get(), s) < n)
+    throw std::runtime_error("pdlp_mi355x: the Hessian is not positive semidefinite for this objective sense");
+  D.qdiag.alloc((size_t)n);
+  launchHessianAssemble(dstBeg.get(), srcSlot.get(), qValue.get(), D.sense, n, nOff, D.qdiag.get(), nOff > 0 ? D.N.val.get() : nullptr, s);
+  if (keepAll) {  // the map and the unscaled Hessian stay, sized as Solver::keepHessian sizes its uploads
+    DeviceHessianMap& K = D.kmap;
+    K.nSlots = (int32_t)nq;
+    K.nOff = nOff;
+    K.dstBeg = std::move(dstBeg);
+    K.srcSlot = std::move(srcSlot);
+    K.offRow.alloc((size_t)std::max(nOff, 1)); K.offCol.alloc((size_t)std::max(nOff, 1));
+    if (nOff > 0) {
+      PDLP_HIP(hipMemcpyAsync(K.offRow.get(), D.N.major.get(), sizeof(int32_t) * (size_t)nOff, hipMemcpyDeviceToDevice, s));
+      PDLP_HIP(hipMemcpyAsync(K.offCol.get(), D.N.idx.get(), sizeof(int32_t) * (size_t)nOff, hipMemcpyDeviceToDevice, s));
+      K.qoff0.alloc((size_t)nOff);
+      PDLP_HIP(hipMemcpyAsync(K.qoff0.get(), D.N.val.get(), sizeof(double) * (size_t)nOff, hipMemcpyDeviceToDevice, s));
+    }
+    if (!D.keepMatrix) {  // (else MatrixKeep::qdiag0 holds it)
+      K.qdiag0.alloc((size_t)n);
+      PDLP_HIP(hipMemcpyAsync(K.qdiag0.get(), D.qdiag.get(), sizeof(double) * (size_t)n, hipMemcpyDeviceToDevice, s));
+    }
+  }
+  done();  // 6. the temporaries go out of scope here, before any layout is built
+}
 
 void gpuFormulateValues(const int32_t* aStart, const int32_t* aIndex, const double* aValue, const int32_t* rowKind,
                         const int32_t* rowNewIdx, int32_t n0, int32_t m, int64_t nnz0, int64_t nSlack, double* cscVal,
@@ -583,9 +824,15 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
     return;
   }
   // QP (cuPDLP-C form): the diagonal of Q, with the objective sense, rides along with the column scaling, and so does
-  // the off-diagonal part N.  The extraction stays on the host (integer work in the number of slots, and the one
-  // definition of N's entry order and of every refusal); its result is uploaded with a row index per slot.
-  {
+  // the off-diagonal part N.  The host walk (pdlp_host.cpp) is the one definition of N's entry order and of every
+  // refusal; gpuExtractHessian restates it on the device where the rule allows, else the walk's result is uploaded with a
+  // row index per slot.  The checks the walk makes before its first slot are made here, in its words, for both.
+  D.hessianReason = hessianExtractionReason(true, D.hessianSharded, false, D.hessianSwitchOn, P.q_dim, P.q_start);
+  if (D.hessianReason == kHessOnDevice) {
+    if (P.q_dim > P.num_col) throw std::runtime_error("Hessian dimension exceeds the number of columns");
+    if (!P.q_index || !P.q_value) throw std::runtime_error("null Hessian arrays");
+    gpuExtractHessian(P, n, s, D);
+  } else {
     std::vector<double> q;
     Compressed off;
     const auto t0 = std::chrono::steady_clock::now();
@@ -618,6 +865,7 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
     }
     PDLP_HIP(hipStreamSynchronize(s));  // q, off and offRow go out of scope
     D.secUploadHessian = std::chrono::duration<double>(std::chrono::steady_clock::now() - t1).count();
+    D.hessianOffSlots = (int64_t)off.idx.size();
     if (D.keepHessianPattern && !q.empty()) {
       D.hQdiag0 = std::move(q);
       D.hQoff0 = std::move(off.val);

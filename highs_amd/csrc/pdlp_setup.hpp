@@ -51,6 +51,29 @@ struct MatrixKeep {
   }
 };
 
+// What a Hessian-updatable solver keeps of a device-side extraction: pdlp_host.hpp HessianMap's arrays in HBM, sized as
+// Solver::keepHessian sizes its uploads (an empty array holds one element), and the unscaled diagonal and values of N
+// (qdiag0 only where no MatrixKeep holds it).
+struct DeviceHessianMap {
+  int32_t nSlots = 0, nOff = 0;
+  DeviceArray<int32_t> dstBeg, srcSlot, offRow, offCol;
+  DeviceArray<double> qdiag0, qoff0;
+  bool kept() const { return dstBeg.size() != 0; }
+};
+
+// Where a QP's Hessian is extracted.  A pure host function of what the caller knows before any launch; 0 = on the device
+// (gpuExtractHessian), anything else = by the host walk (pdlp_host.hpp extractHessian / extractHessianKept), and why.
+enum : int32_t {
+  kHessOnDevice = 0,
+  kHessHostSetup = 1,   // the set-up itself runs on the host
+  kHessSharded = 2,     // neither downloadForm nor the shard cut carries N
+  kHessHipdlp = 3,      // the HiPDLP form takes no Hessian
+  kHessNoSlots = 4,     // q_dim <= 0, no q_start, or q_start[q_dim] <= 0
+  kHessStarts = 5,      // q_start[0] != 0 or q_start decreases somewhere: the host walk defines what that means
+  kHessSwitchOff = 6,   // PDLP_MI355X_GPU_HESSIAN=0
+};
+int32_t hessianExtractionReason(bool gpuSetup, bool sharded, bool hipdlp, bool switchOn, int32_t qDim, const int32_t* qStart);
+
 struct DeviceProblem {
   int32_t n = 0, m = 0, n0 = 0, nEqs = 0;
   int64_t nnz = 0;
@@ -81,13 +104,23 @@ struct DeviceProblem {
   bool keepMatrix = false;
   MatrixKeep keep;
   // PDLP_UPDATABLE_HESSIAN (set keepHessianPattern before gpuPrepare; cuPDLP-C form only): the Hessian is extracted with
-  // every slot kept (pdlp_host.hpp extractHessianKept); its assembly map, the unscaled diagonal and the unscaled values
-  // of N stay on the host for the solver to take
+  // every slot kept (pdlp_host.hpp extractHessianKept).  Host extraction: its assembly map, the unscaled diagonal and the
+  // unscaled values of N stay on the host for the solver to take.  Device extraction (gpuExtractHessian): they stay in HBM
+  // — kmap; hmap, hQdiag0 and hQoff0 are then empty
   bool keepHessianPattern = false;
   HessianMap hmap;
   std::vector<double> hQdiag0, hQoff0;
-  // wall seconds of three parts of gpuPrepare (cuPDLP-C form; stage "setup_seconds"): the Hessian's extraction on the
-  // host, the upload of its diagonal and of N, the scaling passes
+  DeviceHessianMap kmap;
+  // The Hessian's extraction (hessianExtractionReason): the caller says what the rule cannot see from the problem — may it
+  // run on the device at all (not sharded, the switch PDLP_MI355X_GPU_HESSIAN not 0) — and reads what happened: the
+  // rule's reason code (kHessOnDevice: gpuExtractHessian ran), the taken slots and the slots of N, the most HBM the
+  // extraction's temporaries held at once (stage "hessian_extraction")
+  bool hessianSharded = false, hessianSwitchOn = true;
+  int32_t hessianReason = kHessNoSlots;
+  int64_t hessianTaken = 0, hessianOffSlots = 0, hessianTempBytes = 0;
+  // wall seconds of three parts of gpuPrepare (cuPDLP-C form; stage "setup_seconds"): the Hessian's extraction, the
+  // upload that goes with it (host extraction: its diagonal and N; device extraction: the caller's q_start, q_index,
+  // q_value), the scaling passes
   double secExtract = 0, secUploadHessian = 0, secPasses = 0;
 };
 
@@ -99,6 +132,12 @@ struct HipdlpSetup {
 // Formulate + scale + both orientations on the device.  Throws std::runtime_error.
 void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProblem& out,
                 const HipdlpSetup* hipdlp = nullptr);
+// The Hessian's extraction on the device, for gpuPrepare (pdlp_setup.hip; the rule above decides).  On entry the host's
+// own checks have passed (q_dim <= num_col, no null array) and q_start runs from 0 to q_start[q_dim] > 0 without
+// decreasing.  Writes D.qdiag and D.N (unscaled, with the sense) exactly as an upload of extractHessian's /
+// extractHessianKept's result would, D.kmap when D.keepHessianPattern, the counts and the two times; throws the host
+// walk's sentences.  Everything runs on s; synchronises.
+void gpuExtractHessian(const pdlp_problem_t& P, int32_t n, hipStream_t s, DeviceProblem& D);
 
 // ---- the value-dependent layer of gpuPrepare, shared with pdlp_mi355x_update_matrix (pdlp_update.cpp) ----------------
 // The formulated values of the caller's a_value in reference order: <= rows negated, -1.0 for the nSlack slack entries

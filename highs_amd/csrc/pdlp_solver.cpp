@@ -349,6 +349,7 @@ DevSwitches DevSwitches::fromEnv() {
   w.persistent = num("PDLP_MI355X_PERSISTENT", -1);
   w.persistentQp = num("PDLP_MI355X_PERSISTENT_QP", -1);
   w.persistentHipdlp = num("PDLP_MI355X_PERSISTENT_HIPDLP", -1);
+  w.gpuHessian = num("PDLP_MI355X_GPU_HESSIAN", -1);
   w.barrierTimeoutMs = num("PDLP_MI355X_BARRIER_TIMEOUT_MS", 1000);
   {
     const char* e = getenv("PDLP_MI355X_EXCHANGE");
@@ -486,8 +487,9 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   // PDLP_UPDATABLE_HESSIAN: every slot of the Hessian the caller passes is kept, so the structure follows the pattern
   const bool keepQPattern = (opt_.updatable & PDLP_UPDATABLE_HESSIAN) != 0;
   hasQoff_ = keepQPattern ? hessianHasOffDiagonalSlot(P) : hessianHasOffDiagonal(P);
-  // (one GPU: the off-diagonal part N of Q is scaled with the columns inside the device-side passes too and its layouts
-  // are built from the device arrays, pdlp_setup.hip k_scale_qoff; only its extraction is host work)
+  // (one GPU: the off-diagonal part N of Q is extracted on the device, pdlp_setup.hip gpuExtractHessian — unless
+  // PDLP_MI355X_GPU_HESSIAN=0 — scaled with the columns inside the device-side passes, k_scale_qoff, and its layouts are
+  // built from the device arrays)
   // sharded: every rank still prepares the WHOLE problem (Ruiz scaling couples all rows and columns) but does it on
   // its device and copies the result back once; only the row-block cut and the upload of its shard stay on the host.
   // Not with an off-diagonal Hessian: neither downloadForm nor the shard cut on the device knows about N, so such a
@@ -506,6 +508,8 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   devProb.keepPasses = updatable_;
   devProb.keepMatrix = matrixUpdatable_;
   devProb.keepHessianPattern = keepQPattern;
+  devProb.hessianSharded = sharded_;
+  devProb.hessianSwitchOn = sw_.gpuHessian != 0;
   F_.keepPasses = updatable_;
   if (gpuSetup_) {
     // formulate + scale + both orientations on the device; F_ keeps only the host-side bookkeeping
@@ -523,13 +527,21 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
     setupParts_[0] = devProb.secExtract; setupParts_[1] = devProb.secUploadHessian; setupParts_[2] = devProb.secPasses;
     if (updatable_) keepForUpdates(&devProb);
     if (matrixUpdatable_) mk_ = std::move(devProb.keep);
-    if (hessianUpdatable_) {
+    hessReason_ = devProb.hessianReason;
+    hessOffSlots_ = devProb.hessianOffSlots;
+    hessTempBytes_ = devProb.hessianTempBytes;
+    if (hessReason_ == kHessOnDevice) hessTaken_ = devProb.hessianTaken;
+    if (hessianUpdatable_ && devProb.kmap.kept()) {
+      keepHessian(devProb.kmap);
+    } else if (hessianUpdatable_) {
       F_.hmap = std::move(devProb.hmap);
       keepHessian(devProb.hQdiag0, devProb.hQoff0);
       devProb.hQdiag0 = devProb.hQoff0 = std::vector<double>();
     }
+    devProb.kmap = DeviceHessianMap();  // (a solver that is not Hessian-updatable keeps none of it)
   } else if (shardedGpuSetup) {
     gpuPrepare(P, doScale, stream_, devProb);
+    hessReason_ = devProb.hessianReason;  // (a diagonal Hessian: walked on the host, kHessSharded)
     sumCost2_ = devProb.sumCost2;
     sumRhs2_ = devProb.sumRhs2;
     // A rank keeps only its shard (round 6): in the mesh exchange's layout both operands of a rank are CONTIGUOUS pieces
@@ -562,12 +574,20 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
     if (doScale) scale(F_);
     finalize(F_);
     if (updatable_) keepForUpdates(nullptr);
+    hessOffSlots_ = F_.qoff.beg.empty() ? 0 : (int64_t)F_.qoff.beg[F_.n];
     if (hessianUpdatable_) keepHessian(F_.qdiag0, F_.qoff0);
     if (matrixUpdatable_) keepMatrixFromHost(P);
     sumCost2_ = 0.0;
     for (double v : F_.cost) sumCost2_ += v * v;
     sumRhs2_ = 0.0;
     for (double v : F_.rhs) sumRhs2_ += v * v;
+  }
+  if (!gpuSetup_ && !shardedGpuSetup) hessReason_ = hessianExtractionReason(false, sharded_, false, sw_.gpuHessian != 0, P.q_dim, P.q_start);
+  if (hessReason_ != kHessOnDevice && hessReason_ != kHessNoSlots && P.q_dim > 0 && P.q_start && P.q_value) {
+    // (the host walk has accepted the problem; what it took: every slot when the pattern is kept, else the non-zero ones)
+    const int64_t nq = P.q_start[P.q_dim];
+    hessTaken_ = 0;
+    for (int64_t p = 0; p < nq; ++p) hessTaken_ += (keepQPattern || P.q_value[p] != 0.0) ? 1 : 0;
   }
   log(1, "Using cost norm = %9.3g and RHS norm = %9.3g\n", F_.normCost, F_.normRhs);
   if (F_.nnz < 50000)  // DESIGN.md section 3, "Small LPs": three dependent launches of ~5 us per iteration
@@ -791,8 +811,8 @@ void Solver::keepForUpdates(DeviceProblem* D) {
   F_.rsPass = std::vector<double>();
 }
 
-// Hessian-updatable solver: the assembly map (F_.hmap, built on the host in both set-up paths) and the unscaled Hessian go
-// to HBM.  A solver created without a Hessian keeps nothing and refuses q_value later.
+// Hessian-updatable solver: the assembly map (F_.hmap, built by the host walk) and the unscaled Hessian go to HBM.  A
+// solver created without a Hessian keeps nothing and refuses q_value later.
 void Solver::keepHessian(const std::vector<double>& qdiag0, const std::vector<double>& qoff0) {
   const HessianMap& M = F_.hmap;
   if (!M.kept()) return;
@@ -813,6 +833,22 @@ void Solver::keepHessian(const std::vector<double>& qdiag0, const std::vector<do
   F_.hmap = HessianMap();  // (the host copies are released; F_.qdiag0 is keepMatrixFromHost's to release)
   F_.qoff0 = std::vector<double>();
   if (!matrixUpdatable_) F_.qdiag0 = std::vector<double>();
+}
+
+// ... the device-side extraction's form: its arrays are adopted, sized as the uploads above size theirs
+void Solver::keepHessian(DeviceHessianMap& K) {
+  hk_.nSlots = K.nSlots;
+  hk_.nOff = K.nOff;
+  hk_.dstBeg = std::move(K.dstBeg);
+  hk_.srcSlot = std::move(K.srcSlot);
+  hk_.offRow = std::move(K.offRow);
+  hk_.offCol = std::move(K.offCol);
+  if (!matrixUpdatable_) hk_.qdiag0 = std::move(K.qdiag0);  // (else mk_.qdiag0 holds it: qdiag0Dev)
+  if (K.nOff > 0) {
+    hk_.qoff0 = std::move(K.qoff0);
+    hk_.qoffScaled.alloc((size_t)K.nOff);
+  }
+  K = DeviceHessianMap();
 }
 
 // dQ_ has just been built from tagged values (value of qoff slot k = k + 1): its value arrays become their source
@@ -2335,6 +2371,21 @@ void Solver::getVector(const std::string& name, double* host, int64_t len) {
     for (int64_t i = 0; i < len && i < 8; ++i) host[i] = v[i];
     return;
   }
+  // a Hessian-updatable solver's kept assembly map (pdlp_host.hpp HessianMap), read-only: 32-bit integers, exact in doubles
+  // (srcSlot: the first `len` of its dstBeg[n + nOff] entries)
+  auto mapArray = [&](const char* mapName, const DeviceArray<int32_t>& arr, int64_t count) {
+    if (name != mapName) return false;
+    if (!hk_.dstBeg.size()) throw std::runtime_error("unknown vector name: " + name + " (this solver keeps no Hessian map)");
+    if (count != len) throw std::runtime_error("length mismatch for vector " + name);
+    std::vector<int32_t> h((size_t)len);
+    arr.download(h.data(), (size_t)len, stream_);
+    PDLP_HIP(hipStreamSynchronize(stream_));
+    for (int64_t i = 0; i < len; ++i) host[i] = (double)h[i];
+    return true;
+  };
+  if (mapArray("dstBeg", hk_.dstBeg, (int64_t)F_.n + hk_.nOff + 1) || mapArray("srcSlot", hk_.srcSlot, std::min<int64_t>(len, (int64_t)hk_.srcSlot.size())) ||
+      mapArray("offRow", hk_.offRow, hk_.nOff) || mapArray("offCol", hk_.offCol, hk_.nOff))
+    return;
   auto [p, l] = lookup(name);
   if (l != len) throw std::runtime_error("length mismatch for vector " + name);
   PDLP_HIP(hipMemcpyAsync(host, p, sizeof(double) * len, hipMemcpyDeviceToHost, stream_));
@@ -2457,9 +2508,19 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     // sumRhs2, nEqs, n0, scaled}, then [8] 1 = formulated, scaled and laid out on the device (pdlp_setup.hip), 0 = on the host
     put(0, F_.normCost); put(1, F_.normRhs); put(2, F_.matNormInf); put(3, sumCost2_); put(4, sumRhs2_);
     put(5, (double)F_.nEqs); put(6, (double)F_.n0); put(7, F_.scaled ? 1.0 : 0.0); put(8, gpuSetup_ ? 1.0 : 0.0);
-  } else if (name == "setup_seconds") {  // launches nothing: wall seconds of parts of a device-side set-up — the Hessian's extraction on
-    // the host, the upload of its diagonal and of N, the scaling passes, N's layout build (zeros after a host set-up) — and
-    // [4] the whole create
+  } else if (name == "hessian_extraction") {  // launches nothing: [0] 1 = the Hessian was extracted on the device
+    // (pdlp_setup.hip gpuExtractHessian), 0 = by the host walk; [1] why (pdlp_setup.hpp hessianExtractionReason: 0 on the
+    // device, 1 host set-up, 2 sharded, 3 HiPDLP, 4 no slots, 5 q_start does not run from 0 upwards, 6 switched off);
+    // [2] slots taken (all of them for a Hessian-updatable solver, else the non-zero ones), [3] slots of N, [4] the most HBM
+    // the device extraction's temporaries held at once, bytes
+    put(0, hessReason_ == kHessOnDevice ? 1.0 : 0.0);
+    put(1, (double)hessReason_);
+    put(2, (double)hessTaken_);
+    put(3, (double)hessOffSlots_);
+    put(4, (double)hessTempBytes_);
+  } else if (name == "setup_seconds") {  // launches nothing: wall seconds of parts of a device-side set-up — the Hessian's extraction
+    // (host walk or device), the upload that goes with it (the walk's diagonal and N, or the caller's three Hessian arrays),
+    // the scaling passes, N's layout build (zeros after a host set-up) — and [4] the whole create
     for (int k = 0; k < 4; ++k) put(k, setupParts_[k]);
     put(4, setupSeconds_);
   } else if (name == "trial_launches") {  // kernels per trial step of the hot loop (2 = fused decision + primal step)

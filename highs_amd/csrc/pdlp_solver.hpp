@@ -32,6 +32,7 @@ struct DevSwitches {
   int constCached = -1;   // PDLP_MI355X_CONST_CACHED=0|1 (development): c, l, u of the primal step non-temporal / ordinary loads (default: by size)
   int fused = -1, persistent = -1, xcdLocal = -1, hierBarrier = -1, deviceCheck = -1, checkSmall = -1;
   int persistentQp = -1;  // PDLP_MI355X_PERSISTENT_QP=0: small QPs with off-diagonal Hessian entries keep their launches per trial (LPs, diagonal QPs: not read)
+  int gpuHessian = -1;    // PDLP_MI355X_GPU_HESSIAN=0: a device-side set-up extracts a QP's Hessian by the host walk (LPs: not read)
   int persistentHipdlp = -1;  // PDLP_MI355X_PERSISTENT_HIPDLP=0: the HiPDLP path keeps its two launches per Halpern step on small LPs too
   int primalInA = -1;     // PDLP_MI355X_PRIMAL_IN_A: the persistent loop without its P phase (pdlp_small.hip PINA); -1 = where measured faster
   int barrierTimeoutMs = 1000;  // PDLP_MI355X_BARRIER_TIMEOUT_MS: how long a grid barrier / roll call waits for missing workgroups
@@ -224,6 +225,7 @@ class Solver : public SolverBase {
   // Hessian-updatable solvers (pdlp_update.hpp): the assembly map and the unscaled Hessian into hk_; dQ_'s source indices
   // out of its tagged build and the first refill; the parts of an update
   void keepHessian(const std::vector<double>& qdiag0, const std::vector<double>& qoff0);
+  void keepHessian(DeviceHessianMap& K);  // device-side extraction: the map and the unscaled Hessian are in HBM already
   void finishHessianKeep(const std::vector<double>& qoffScaled);  // host set-up: the scaled values of N from the form
   void finishHessianKeep(const DeviceArray<double>& qoffScaled);  // device-side set-up: device to device
   void finishHessianKeep(const double* qoffScaled, hipMemcpyKind from);
@@ -302,9 +304,13 @@ class Solver : public SolverBase {
   int32_t rank_ = 0, world_ = 1, r0_ = 0, r1_ = 0, mLoc_ = 0;
   Comm* comm_ = nullptr;
   bool gpuSetup_ = true;   // formulate/scale/transpose/slab layout on the device (pdlp_setup.hip)
-  // device-side set-up: wall seconds of the Hessian's host extraction, its upload, the scaling passes and N's layout build
-  // (stage "setup_seconds"; zeros after a host set-up)
+  // device-side set-up: wall seconds of the Hessian's extraction, the upload that goes with it, the scaling passes and N's
+  // layout build (stage "setup_seconds"; zeros after a host set-up)
   double setupParts_[4] = {};
+  // stage "hessian_extraction": the rule's reason code (pdlp_setup.hpp hessianExtractionReason; 0 = on the device), the
+  // taken slots, the slots of N, the most HBM the device extraction's temporaries held at once
+  int32_t hessReason_ = kHessNoSlots;
+  int64_t hessTaken_ = 0, hessOffSlots_ = 0, hessTempBytes_ = 0;
   double sumCost2_ = 0, sumRhs2_ = 0;  // left-to-right sums of the scaled c, b
   bool sharded_ = false;  // row-block sharded kernel sequence (world > 1, or forced for testing)
   bool shardOnDevice_ = false;  // sharded + device-side set-up: the rank's shard is cut on the device (uploadShardFromDevice)

@@ -582,6 +582,21 @@ class DeviceSolver:
         gpu_setup, 1.0 where the device formulated, scaled and laid the problem out."""
         return dict(zip(self.SETUP_SCALARS, self.stage("setup_scalars", len(self.SETUP_SCALARS)).tolist()))
 
+    HESSIAN_EXTRACTION = ("on_device", "reason", "taken_slots", "n_slots", "temp_bytes")
+
+    def hessian_extraction(self):
+        """Stage "hessian_extraction" as a dict: on_device 1.0 where the set-up extracted the Hessian on the device, the
+        rule's reason code (HESSIAN_REASONS), the slots taken, the slots of N, the peak of the extraction's temporary HBM."""
+        return dict(zip(self.HESSIAN_EXTRACTION, self.stage("hessian_extraction", len(self.HESSIAN_EXTRACTION)).tolist()))
+
+    def hessian_map(self):
+        """A Hessian-updatable solver's kept assembly map (read-only test hook): dst_beg [n + nOff + 1], src_slot, off_row,
+        off_col [nOff] as int64 arrays."""
+        n_off = int(self.hessian_extraction()["n_slots"])
+        dst_beg = self.get("dstBeg", self.n + n_off + 1).astype(np.int64)
+        return dict(dst_beg=dst_beg, src_slot=self.get("srcSlot", int(dst_beg[-1])).astype(np.int64),
+                    off_row=self.get("offRow", n_off).astype(np.int64), off_col=self.get("offCol", n_off).astype(np.int64))
+
     def device_matrix(self, which):
         """pdlp_mi355x_device_matrix: what the solver holds of operand `which` (0: A by rows, 1: A' by columns), downloaded
         as it lies in HBM (no launch, no change of state).  A dict of numbers and numpy copies: beg / idx / val are the
@@ -798,6 +813,22 @@ def host_prepare_qp(lp, a_value=None, q_value=None, update=None, update_then=Non
     lib().pdlp_mi355x_free_prepared(C.byref(F))
     lib().pdlp_mi355x_free_prepared_hessian(C.byref(Q))
     return form, hess
+
+
+# reason codes of the rule that decides where a QP's Hessian is extracted (csrc/pdlp_setup.hpp hessianExtractionReason)
+HESSIAN_REASONS = ("on_device", "host_setup", "sharded", "hipdlp", "no_slots", "q_start", "switched_off")
+
+
+def hessian_extraction_rule(q_start, gpu_setup=True, sharded=False, hipdlp=False, switch_on=True):
+    """pdlp_mi355x_host_hessian_extraction_rule (a test hook outside the public header; needs no device): the name of the
+    rule's reason for a Hessian with these column starts (None: no Hessian)."""
+    fn = lib().pdlp_mi355x_host_hessian_extraction_rule
+    fn.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, abi.c_i32p, C.POINTER(C.c_int32)]
+    st = None if q_start is None else np.ascontiguousarray(q_start, dtype=np.int32)
+    reason = C.c_int32(-1)
+    _check(fn(int(gpu_setup), int(sharded), int(hipdlp), int(switch_on), 0 if st is None else len(st) - 1,
+              None if st is None else st.ctypes.data_as(abi.c_i32p), C.byref(reason)), "hessian_extraction_rule")
+    return HESSIAN_REASONS[reason.value]
 
 
 def stream_plan(form, which, slab_long_limit=0, extra_blocks=0):

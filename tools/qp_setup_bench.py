@@ -16,6 +16,15 @@ values, spread (max - min); for this tree also the parts of stage "setup_seconds
 upload of its diagonal and of N, the scaling passes, N's layout build — and the rest.  `device_is_faster`: the device
 median is below both other medians by more than the larger of the spreads involved.  Prints one JSON line and writes it to
 --out.  Nothing is asserted: these are measurements.
+
+  python tools/qp_setup_bench.py --extraction --parent-lib ... [--out profiles/qp_hessian_extraction.json]
+
+The Hessian's extraction alone: parent / `walk` (this tree with PDLP_MI355X_GPU_HESSIAN=0: the host walk
+and the upload of its result, as the parent) / device (this tree's default: pdlp_setup.hip gpuExtractHessian).  Every process
+creates twice; the second create carries no module load.  Per way and create: median, all values and spread of
+`extraction_and_upload` = slots 0 + 1 of stage "setup_seconds", and of the whole create.  `device_is_below_parent`: the device's
+median is below the parent's by more than the larger of the two spreads; `walk_agrees_with_parent`: the two medians differ by
+no more than the parent's spread.  Also what stage "hessian_extraction" reports (path, slots, peak of temporary HBM).
 """
 import argparse
 import json
@@ -61,6 +70,51 @@ def workload(hessian, n):
     return lp
 
 
+def extraction_worker(hessian, n):
+    """Two creates in this process (the second without the module load) -> one JSON line."""
+    from highs_amd import solver
+    lp = workload(hessian, n)
+    out = dict(hessian_slots=int(len(lp.hessian[2])), m=int(lp.num_row), n=int(lp.num_col), nnz=int(lp.num_nz), creates=[])
+    for _ in range(2):
+        ds = solver.DeviceSolver(lp, **OPTIONS)
+        sec = ds.stage("setup_seconds", 5)
+        rec = dict(create_seconds=float(sec[4]), extraction_and_upload=float(sec[0] + sec[1]), extraction=float(sec[0]), upload=float(sec[1]),
+                   gpu_setup=ds.setup_scalars()["gpu_setup"])
+        try:
+            rec["hessian_extraction"] = ds.hessian_extraction()
+        except RuntimeError:  # (a library from before this stage)
+            rec["hessian_extraction"] = None
+        out["creates"].append(rec)
+        ds.close()
+    print(json.dumps(out))
+
+
+def measure_extraction(hessian, n, reps, parent_lib):
+    ways = (("parent",) if parent_lib else ()) + ("walk", "device")
+    runs = {w: [] for w in ways}
+    one(hessian, n, "device", parent_lib, "--extraction-worker")  # (not kept: warms the driver's caches)
+    for _ in range(reps):
+        for w in ways:
+            runs[w].append(one(hessian, n, w, parent_lib, "--extraction-worker"))
+    first = runs["device"][0]
+    out = dict(hessian=hessian, m=first["m"], n=first["n"], nnz=first["nnz"], hessian_slots=first["hessian_slots"], reps=reps)
+    med = statistics.median
+    for w in ways:
+        res = dict(hessian_extraction=runs[w][0]["creates"][0]["hessian_extraction"])
+        for k, which in enumerate(("first_create", "second_create")):
+            res[which] = {}
+            for key in ("extraction_and_upload", "extraction", "upload", "create_seconds"):
+                v = [r["creates"][k][key] for r in runs[w]]
+                res[which][key] = dict(median=med(v), all=v, spread=max(v) - min(v))
+        out[w] = res
+    if parent_lib:
+        for which in ("first_create", "second_create"):
+            P, W, D = (out[w][which]["extraction_and_upload"] for w in ("parent", "walk", "device"))
+            out["device_is_below_parent_" + which] = P["median"] - D["median"] > max(P["spread"], D["spread"])
+            out["walk_agrees_with_parent_" + which] = abs(W["median"] - P["median"]) <= P["spread"]
+    return out
+
+
 def worker(hessian, n):
     """One create in this process, with whatever library and switches its environment names -> one JSON line."""
     from highs_amd import solver
@@ -76,15 +130,18 @@ def worker(hessian, n):
     print(json.dumps(out))
 
 
-def one(hessian, n, how, parent_lib):
+def one(hessian, n, how, parent_lib, worker_flag="--worker"):
     env = dict(os.environ)
     env.pop("PDLP_MI355X_GPU_SETUP", None)
+    env.pop("PDLP_MI355X_GPU_HESSIAN", None)
     env.pop("PDLP_MI355X_LIB", None)
     if how == "parent":
         env["PDLP_MI355X_LIB"] = parent_lib
     elif how == "host":
         env["PDLP_MI355X_GPU_SETUP"] = "0"
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--worker", hessian, "--n", str(n)], env=env, capture_output=True,
+    elif how == "walk":
+        env["PDLP_MI355X_GPU_HESSIAN"] = "0"
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), worker_flag, hessian, "--n", str(n)], env=env, capture_output=True,
                        text=True, timeout=600)
     if r.returncode != 0:
         raise SystemExit(f"worker {hessian}/{how} failed ({r.returncode}):\n{r.stderr[-2000:]}")
@@ -120,15 +177,32 @@ def measure(hessian, n, reps, parent_lib):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--worker", default=None, help="(internal) one create of this Hessian in this process")
+    ap.add_argument("--extraction-worker", default=None, help="(internal) two creates of this Hessian in this process")
+    ap.add_argument("--extraction", action="store_true", help="measure the Hessian's extraction and upload: parent / walk / device")
     ap.add_argument("--hessians", default=",".join(HESSIANS))
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--n", type=int, default=500_000, help="rows = columns of the workload (bench.py's is 500 000)")
     ap.add_argument("--parent-lib", default=None, help="libpdlp_mi355x.so built from the parent commit")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "qp_setup_device_vs_host.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/qp_setup_device_vs_host.json, with --extraction "
+                                                "profiles/qp_hessian_extraction.json")
     args = ap.parse_args()
     if args.worker:
         return worker(args.worker, args.n)
+    if args.extraction_worker:
+        return extraction_worker(args.extraction_worker, args.n)
     parent = os.path.abspath(args.parent_lib) if args.parent_lib else None
+    args.out = args.out or os.path.join(ROOT, "profiles", "qp_hessian_extraction.json" if args.extraction else "qp_setup_device_vs_host.json")
+    if args.extraction:
+        out = dict(what="the Hessian's extraction and the upload that goes with it (slots 0 + 1 of stage setup_seconds) inside "
+                        "pdlp_mi355x_create: the parent commit's library, this tree with PDLP_MI355X_GPU_HESSIAN=0, this tree's "
+                        "default; a process per measurement with two creates, alternating, median of reps",
+                   parent_measured=parent is not None, results=[measure_extraction(h, args.n, args.reps, parent) for h in args.hessians.split(",")])
+        line = json.dumps(out)
+        print(line)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+        return
     out = dict(what="pdlp_mi355x_create (setup_seconds) on a QP with an off-diagonal Hessian: the parent commit's library, this "
                     "tree with the host set-up forced, this tree's default; a process per measurement, alternating, median of reps",
                parent_measured=parent is not None, results=[measure(h, args.n, args.reps, parent) for h in args.hessians.split(",")])
