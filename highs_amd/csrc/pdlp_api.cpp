@@ -17,6 +17,7 @@
 #include "pdlp_halpern.hpp"
 #include "pdlp_mps.hpp"
 #include "pdlp_pool.hpp"
+#include "pdlp_resident.hpp"
 #include "pdlp_session.hpp"
 #include "pdlp_solver.hpp"
 #include "pdlp_update.hpp"
@@ -849,6 +850,74 @@ void pdlp_mi355x_batch_destroy(pdlp_mi355x_batch_t* B) {
 }
 
 int64_t pdlp_mi355x_batch_info_size(void) { return sizeof(pdlp_batch_info_t); }
+
+// ---- device-resident entries (pdlp_resident.hpp) -------------------------------------------------------------------------
+}  // extern "C"
+namespace {
+// guarded(), with the entry's name in front of whatever is refused
+template <typename Fn>
+int guardedAs(const char* entry, Fn&& fn) {
+  return guarded([&] {
+    try {
+      fn();
+    } catch (const std::exception& e) {
+      throw std::runtime_error(std::string(entry) + ": " + e.what());
+    }
+  });
+}
+}  // namespace
+extern "C" {
+
+int pdlp_mi355x_create_device(const pdlp_problem_t* P_dev, const pdlp_params_t* opt, void* stream, pdlp_mi355x_solver_t** out) {
+  return guardedAs(pdlp::kEntryCreateDevice, [&] {
+    if (!P_dev || !opt || !out) throw std::runtime_error("null argument");
+    *out = nullptr;
+    // what needs no device comes before any HIP call
+    if (opt->algorithm != 0 && opt->algorithm != 1) throw std::runtime_error("unknown algorithm (0 = cuPDLP-C path, 1 = HiPDLP path)");
+    if (const char* why = pdlp::sessionOneShotReason(*opt)) throw std::runtime_error(why);
+    pdlp::residentProblemShape(*P_dev);
+    int nDev = 0;
+    if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0)
+      throw std::runtime_error("pdlp_mi355x: no HIP device available (this library has no CPU fallback)");
+    pdlp::requireDeviceProblem(*P_dev, opt->device);
+    pdlp::ResidentProblem RP(*P_dev, (hipStream_t)stream);
+    *out = new pdlp_mi355x_solver{new pdlp::Solver(RP, *opt)};
+  });
+}
+
+int pdlp_mi355x_update_device(pdlp_mi355x_solver_t* s, const double* a_value_dev, int64_t num_nz, const double* q_value_dev,
+                              int64_t num_q_nz, const pdlp_update_t* u_dev, void* stream) {
+  return guardedAs(pdlp::kEntryUpdateDevice, [&] {
+    if (!s || !s->impl) throw std::runtime_error("null solver");
+    s->impl->updateDevice(a_value_dev, num_nz, q_value_dev, num_q_nz, u_dev, (hipStream_t)stream);
+  });
+}
+
+int pdlp_mi355x_run_device(pdlp_mi355x_solver_t* s, pdlp_result_t* R_dev) {
+  return guardedAs(pdlp::kEntryRunDevice, [&] {
+    if (!s || !s->impl) throw std::runtime_error("null solver");
+    s->impl->runDevice(R_dev);
+  });
+}
+
+// Test hook, not part of the public header: what pdlp_mi355x_update_device refuses before any HIP call, for a solver created
+// on P with opt — from the pointers' being NULL or not alone; no array of the update is read, no device call is made.
+int pdlp_mi355x_host_update_device_refusal(const pdlp_problem_t* P, const pdlp_params_t* opt, const double* a_value, int64_t num_nz,
+                                           const double* q_value, int64_t num_q_nz, const pdlp_update_t* u) {
+  return guardedAs(pdlp::kEntryUpdateDevice, [&] {
+    if (!P || !opt) throw std::runtime_error("null argument");
+    if (const char* why = pdlp::sessionOneShotReason(*opt)) throw std::runtime_error(why);
+    pdlp::ValueUpdateFacts f;
+    f.updatable = opt->updatable;
+    f.nnz = P->num_col > 0 && P->a_start ? (int64_t)P->a_start[P->num_col] : 0;
+    f.qSlots = (opt->updatable & PDLP_UPDATABLE_HESSIAN) ? pdlp::sessionHessianSlots(*P) : 0;
+    f.hasQoff = (opt->updatable & PDLP_UPDATABLE_HESSIAN) ? pdlp::hessianHasOffDiagonalSlot(*P) : pdlp::hessianHasOffDiagonal(*P);
+    static const pdlp_update_t kNoData{};
+    if (pdlp::residentRoute(opt->updatable, a_value, num_nz, q_value, num_q_nz) == pdlp::kRouteUpdate && !u)
+      throw std::runtime_error("pdlp_mi355x_update: null update");
+    pdlp::residentUpdateRefusal(f, a_value, num_nz, q_value, num_q_nz, u ? *u : kNoData);
+  });
+}
 
 // ---- pools (pdlp_pool.hpp) ----------------------------------------------------------------------------------------------
 int pdlp_mi355x_solve_many(int32_t K, const pdlp_problem_t* const* P, const pdlp_params_t* opt, int32_t lanes, pdlp_result_t* R,

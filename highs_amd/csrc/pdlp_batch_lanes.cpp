@@ -45,7 +45,7 @@ void Solver::validateUpdate(const pdlp_update_t& u) const {
 // first (refuseValueUpdate); then the all-zero matrix by the host's rule on the caller's array, and the negative diagonal
 // by the update's own head (the assembly map lives on the device only): stageHessian writes the staging copy of q_value
 // and the validation kernel's word, which nothing but an update's head reads — nothing of the solver's problem.
-void Solver::validateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t& u) const {
+ValueUpdateFacts Solver::valueUpdateFacts() const {
   ValueUpdateFacts f;
   f.sharded = sharded_;
   f.updatable = opt_.updatable;
@@ -54,6 +54,11 @@ void Solver::validateValues(const double* aValue, int64_t numNz, const double* q
   f.hasQoff = hasQoff_;
   f.rowKind = F_.rowKind.data();
   f.m = F_.m;
+  return f;
+}
+
+void Solver::validateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t& u) const {
+  const ValueUpdateFacts f = valueUpdateFacts();
   refuseValueUpdate(f, aValue, numNz, qValue, numQNz, u);
   if (aValue) {
     bool anyNonzero = false;  // (a NaN among the values is not zero, as for create and for the device's absolute maximum)

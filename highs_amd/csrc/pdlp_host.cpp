@@ -52,6 +52,13 @@ const double kInf = std::numeric_limits<double>::infinity();
 // Structural checks of the caller's CSC arrays (shared by both formulations and the device-side setup):
 // the starts must begin at 0, never decrease and end at num_nz; row indices must be in range.
 void validateProblem(const pdlp_problem_t& P) {
+  validateProblemStarts(P);
+  const int64_t nnz = P.num_col > 0 ? (int64_t)P.a_start[P.num_col] : 0;
+  for (int64_t p = 0; p < nnz; ++p)
+    if (P.a_index[p] < 0 || P.a_index[p] >= P.num_row) throw std::runtime_error("row index out of range");
+}
+
+void validateProblemStarts(const pdlp_problem_t& P) {
   if (P.num_col < 0 || P.num_row < 0) throw std::runtime_error("negative dimensions");
   if (P.num_col > 0 && (!P.a_start || !P.col_cost || !P.col_lower || !P.col_upper))
     throw std::runtime_error("null column arrays");
@@ -63,8 +70,6 @@ void validateProblem(const pdlp_problem_t& P) {
   const int64_t nnz = P.a_start[P.num_col];
   if (P.num_nz > 0 && nnz > P.num_nz) throw std::runtime_error("a_start[num_col] exceeds num_nz");
   if (nnz > 0 && (!P.a_index || !P.a_value)) throw std::runtime_error("null matrix arrays");
-  for (int64_t p = 0; p < nnz; ++p)
-    if (P.a_index[p] < 0 || P.a_index[p] >= P.num_row) throw std::runtime_error("row index out of range");
 }
 
 // Diagonal of the (lower-triangular, column-wise) HighsHessian times the objective sense, padded with zeros

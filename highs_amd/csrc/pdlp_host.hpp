@@ -98,6 +98,8 @@ struct StandardForm {
 
 // Throws std::runtime_error on malformed input.
 void validateProblem(const pdlp_problem_t& P);
+// validateProblem without its walk over a_index: what can be checked of a problem whose a_index is not in host memory
+void validateProblemStarts(const pdlp_problem_t& P);
 void requireConstraints(const pdlp_problem_t& P);  // throws for LPs without rows / columns / nonzeros
 void extractDiagonalHessian(const pdlp_problem_t& P, double sense, int32_t n, std::vector<double>& q);
 // The Hessian of a QP, given as HiGHS gives it (model/HighsHessian.h:22-34: lower triangle, column-wise), split into

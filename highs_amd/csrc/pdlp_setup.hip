@@ -494,20 +494,30 @@ void gpuExtractHessian(const pdlp_problem_t& P, int32_t n, hipStream_t s, Device
   const auto t0 = std::chrono::steady_clock::now();
   const int32_t qDim = P.q_dim;
   const int64_t nq = P.q_start[qDim];
+  // 1. the caller's arrays: 16 bytes per slot, 4 per column
+  DeviceHessianInputs in;
+  in.ownStart.alloc((size_t)qDim + 1); in.ownIndex.alloc((size_t)nq); in.ownValue.alloc((size_t)nq);
+  in.ownStart.upload(P.q_start, (size_t)qDim + 1, s); in.ownIndex.upload(P.q_index, (size_t)nq, s); in.ownValue.upload(P.q_value, (size_t)nq, s);
+  PDLP_HIP(hipStreamSynchronize(s));
+  in.qStart = in.ownStart.get(); in.qIndex = in.ownIndex.get(); in.qValue = in.ownValue.get();
+  D.secUploadHessian = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  gpuExtractHessianFromDevice(P, in, n, s, D);
+}
+
+// P: q_dim and a host copy of q_start; the slots are read from `in` alone
+void gpuExtractHessianFromDevice(const pdlp_problem_t& P, DeviceHessianInputs& in, int32_t n, hipStream_t s, DeviceProblem& D) {
+  const auto t1 = std::chrono::steady_clock::now();
+  const int32_t qDim = P.q_dim;
+  const int64_t nq = P.q_start[qDim];
   const bool keepAll = D.keepHessianPattern;
   size_t held = 0, peak = 0;  // HBM of the temporaries (not of what stays: qdiag, N, the kept map)
   auto got = [&](const auto& a) { held += sizeof(*a.get()) * a.size(); peak = std::max(peak, held); };
   auto rid = [&](auto& a) { held -= sizeof(*a.get()) * a.size(); a.release(); };
-
-  // 1. the caller's arrays: 16 bytes per slot, 4 per column
-  DeviceArray<int32_t> qStart, qIndex;
-  DeviceArray<double> qValue;
-  qStart.alloc((size_t)qDim + 1); qIndex.alloc((size_t)nq); qValue.alloc((size_t)nq);
-  got(qStart); got(qIndex); got(qValue);
-  qStart.upload(P.q_start, (size_t)qDim + 1, s); qIndex.upload(P.q_index, (size_t)nq, s); qValue.upload(P.q_value, (size_t)nq, s);
-  PDLP_HIP(hipStreamSynchronize(s));
-  const auto t1 = std::chrono::steady_clock::now();
-  D.secUploadHessian = std::chrono::duration<double>(t1 - t0).count();
+  // (the uploaded copies are temporaries of the extraction; a caller's own arrays in HBM are not, and count as nothing)
+  got(in.ownStart); got(in.ownIndex); got(in.ownValue);
+  const int32_t* const qStartDev = in.qStart;
+  const int32_t* const qIndexDev = in.qIndex;
+  const double* const qValueDev = in.qValue;
 
   // 2. classify; flags and ranks have one element behind the last slot, so that a scan ends in its total
   DeviceArray<int32_t> col, diagFlag, offFlag, diagRank, offRank;
@@ -518,8 +528,8 @@ void gpuExtractHessian(const pdlp_problem_t& P, int32_t n, hipStream_t s, Device
   diagFlag.zero(s);
   offFlag.zero(s);
   PDLP_HIP(hipMemsetAsync(offender.get(), 0xff, sizeof(unsigned long long), s));
-  hipLaunchKernelGGL(k_hess_cols, dim3(gridFor(qDim)), dim3(kT), 0, s, qStart.get(), qDim, col.get());
-  hipLaunchKernelGGL(k_hess_classify, dim3(gridFor(nq)), dim3(kT), 0, s, qIndex.get(), qValue.get(), col.get(), nq, qDim,
+  hipLaunchKernelGGL(k_hess_cols, dim3(gridFor(qDim)), dim3(kT), 0, s, qStartDev, qDim, col.get());
+  hipLaunchKernelGGL(k_hess_classify, dim3(gridFor(nq)), dim3(kT), 0, s, qIndexDev, qValueDev, col.get(), nq, qDim,
                      keepAll ? 1 : 0, diagFlag.get(), offFlag.get(), offender.get());
   PDLP_HIP(hipGetLastError());
   const unsigned long long first = fetchOne(offender.get(), s);
@@ -527,7 +537,7 @@ void gpuExtractHessian(const pdlp_problem_t& P, int32_t n, hipStream_t s, Device
     const int64_t p = (int64_t)(first >> 2);
     if ((first & 3) == kHessSlotOutOfRange) throw std::runtime_error("Hessian index out of range");
     const int32_t j = fetchOne(col.get() + p, s);
-    throw std::runtime_error("pdlp_mi355x: the Hessian must be given by its lower triangle (entry (" + std::to_string(P.q_index[p]) +
+    throw std::runtime_error("pdlp_mi355x: the Hessian must be given by its lower triangle (entry (" + std::to_string(fetchOne(qIndexDev + p, s)) +
                              "," + std::to_string(j) + ") lies above the diagonal)");
   }
 
@@ -556,10 +566,10 @@ void gpuExtractHessian(const pdlp_problem_t& P, int32_t n, hipStream_t s, Device
     DeviceArray<uint32_t> entCol, entRow, rowIn;
     entCol.alloc((size_t)nEnt); entRow.alloc((size_t)nEnt); entSrc.alloc((size_t)nEnt);
     got(entCol); got(entRow); got(entSrc);
-    hipLaunchKernelGGL(k_hess_entries, dim3(gridFor(nq)), dim3(kT), 0, s, qIndex.get(), col.get(), offFlag.get(), offRank.get(), nq, k,
+    hipLaunchKernelGGL(k_hess_entries, dim3(gridFor(nq)), dim3(kT), 0, s, qIndexDev, col.get(), offFlag.get(), offRank.get(), nq, k,
                        entCol.get(), entRow.get(), entSrc.get());
     PDLP_HIP(hipStreamSynchronize(s));
-    rid(col); rid(diagFlag); rid(offFlag); rid(offRank); rid(qIndex);
+    rid(col); rid(diagFlag); rid(offFlag); rid(offRank); rid(in.ownIndex);
     size_t scratch = 0;
     sortByKey(entCol.get(), nEnt, (uint64_t)qDim, colS, byCol, s, &scratch);
     peak = std::max(peak, held + scratch + 2 * sizeof(int32_t) * (size_t)nEnt);
@@ -584,7 +594,7 @@ void gpuExtractHessian(const pdlp_problem_t& P, int32_t n, hipStream_t s, Device
   }
   dstBeg.alloc((size_t)n + (size_t)nOff + 1);
   if (!keepAll) got(dstBeg);
-  hipLaunchKernelGGL(k_hess_diag_starts, dim3(gridFor((int64_t)n + 1)), dim3(kT), 0, s, qStart.get(), diagRank.get(), qDim, n, dstBeg.get());
+  hipLaunchKernelGGL(k_hess_diag_starts, dim3(gridFor((int64_t)n + 1)), dim3(kT), 0, s, qStartDev, diagRank.get(), qDim, n, dstBeg.get());
   if (nOff > 0) {
     D.N.nMajor = D.N.nMinor = n;
     D.N.nnz = nOff;
@@ -606,11 +616,11 @@ void gpuExtractHessian(const pdlp_problem_t& P, int32_t n, hipStream_t s, Device
   DeviceArray<int32_t> bad;
   bad.alloc(1);
   PDLP_HIP(hipMemcpyAsync(bad.get(), &n, sizeof(int32_t), hipMemcpyHostToDevice, s));
-  launchHessianValidate(dstBeg.get(), srcSlot.get(), qValue.get(), D.sense, n, bad.get(), s);
+  launchHessianValidate(dstBeg.get(), srcSlot.get(), qValueDev, D.sense, n, bad.get(), s);
   if (fetchOne(bad.get(), s) < n)
     throw std::runtime_error("pdlp_mi355x: the Hessian is not positive semidefinite for this objective sense");
   D.qdiag.alloc((size_t)n);
-  launchHessianAssemble(dstBeg.get(), srcSlot.get(), qValue.get(), D.sense, n, nOff, D.qdiag.get(), nOff > 0 ? D.N.val.get() : nullptr, s);
+  launchHessianAssemble(dstBeg.get(), srcSlot.get(), qValueDev, D.sense, n, nOff, D.qdiag.get(), nOff > 0 ? D.N.val.get() : nullptr, s);
   if (keepAll) {  // the map and the unscaled Hessian stay, sized as Solver::keepHessian sizes its uploads
     DeviceHessianMap& K = D.kmap;
     K.nSlots = (int32_t)nq;
@@ -695,33 +705,45 @@ double gpuAbsMax(const double* val, int64_t count, hipStream_t s) {
 }
 
 void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProblem& D, const HipdlpSetup* hp) {
-  const bool H = hp != nullptr;  // HiPDLP form (pdhg.cc:152-357 + scaling.cc) instead of the cuPDLP-C one
   validateProblem(P);
   const int32_t n0 = P.num_col, m = P.num_row;
   const int64_t nnz0 = n0 > 0 ? P.a_start[n0] : 0;
   if (nnz0 > 0 && (!P.a_index || !P.a_value)) throw std::runtime_error("null matrix arrays");
   for (int32_t j = 0; j < n0; ++j)
     if (P.a_start[j + 1] < P.a_start[j]) throw std::runtime_error("a_start not monotone");
+
+  // upload the caller's arrays
+  DeviceInputs in;
+  DeviceArray<double> aValue, cIn, clIn, cuIn, rlIn, ruIn;
+  in.ownStart.alloc((size_t)n0 + 1); in.ownIndex.alloc((size_t)nnz0); aValue.alloc((size_t)nnz0);
+  cIn.alloc(n0); clIn.alloc(n0); cuIn.alloc(n0); rlIn.alloc(m); ruIn.alloc(m);
+  in.ownStart.upload(P.a_start, (size_t)n0 + 1, s); in.ownIndex.upload(P.a_index, (size_t)nnz0, s);
+  aValue.upload(P.a_value, (size_t)nnz0, s);
+  cIn.upload(P.col_cost, n0, s); clIn.upload(P.col_lower, n0, s); cuIn.upload(P.col_upper, n0, s);
+  rlIn.upload(P.row_lower, m, s); ruIn.upload(P.row_upper, m, s);
+  in.aStart = in.ownStart.get(); in.aIndex = in.ownIndex.get(); in.aValue = aValue.get();
+  in.colCost = cIn.get(); in.colLower = clIn.get(); in.colUpper = cuIn.get(); in.rowLower = rlIn.get(); in.rowUpper = ruIn.get();
+  gpuPrepareFromDevice(P, in, doScale, s, D, hp);
+}
+
+// P: the sizes, the scalars and HOST copies of a_start, col_cost, row_lower, row_upper and q_start (the monotone checks,
+// the left-to-right norms, the Hessian rule); every other array of P is only asked whether it is NULL.  The caller has
+// made validateProblem's checks of the starts.
+void gpuPrepareFromDevice(const pdlp_problem_t& P, DeviceInputs& in, bool doScale, hipStream_t s, DeviceProblem& D,
+                          const HipdlpSetup* hp) {
+  const bool H = hp != nullptr;  // HiPDLP form (pdhg.cc:152-357 + scaling.cc) instead of the cuPDLP-C one
+  const int32_t n0 = P.num_col, m = P.num_row;
+  const int64_t nnz0 = n0 > 0 ? P.a_start[n0] : 0;
   D.n0 = n0;
   D.m = m;
   D.offset = P.offset;
   D.sense = P.sense < 0 ? -1.0 : 1.0;
   const double costSense = H ? 1.0 : D.sense;  // HiPDLP does not apply the objective sense (pdhg.cc:171)
 
-  // upload the caller's arrays
-  DeviceArray<int32_t> aStart, aIndex;
-  DeviceArray<double> aValue, cIn, clIn, cuIn, rlIn, ruIn;
-  aStart.alloc((size_t)n0 + 1); aIndex.alloc((size_t)nnz0); aValue.alloc((size_t)nnz0);
-  cIn.alloc(n0); clIn.alloc(n0); cuIn.alloc(n0); rlIn.alloc(m); ruIn.alloc(m);
-  aStart.upload(P.a_start, (size_t)n0 + 1, s); aIndex.upload(P.a_index, (size_t)nnz0, s);
-  aValue.upload(P.a_value, (size_t)nnz0, s);
-  cIn.upload(P.col_cost, n0, s); clIn.upload(P.col_lower, n0, s); cuIn.upload(P.col_upper, n0, s);
-  rlIn.upload(P.row_lower, m, s); ruIn.upload(P.row_upper, m, s);
-
   // rows: classify, rank, permute
   DeviceArray<int32_t> kind, eqF, inF, slF, eqR, inR, slR, rowNew;
   kind.alloc(m); eqF.alloc(m); inF.alloc(m); slF.alloc(m); eqR.alloc(m); inR.alloc(m); slR.alloc(m); rowNew.alloc(m);
-  hipLaunchKernelGGL(k_row_classify, dim3(gridFor(m)), dim3(kT), 0, s, rlIn.get(), ruIn.get(), m,
+  hipLaunchKernelGGL(k_row_classify, dim3(gridFor(m)), dim3(kT), 0, s, in.rowLower, in.rowUpper, m,
                      H ? (double)INFINITY : kBoundInf, H ? (int)kRowFree : (int)kRowBound, kind.get(), eqF.get(),
                      inF.get(), slF.get());
   exclusiveSum(eqF.get(), eqR.get(), m, s);
@@ -746,9 +768,9 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
   cscBeg.alloc((size_t)n + 1); cscIdx.alloc((size_t)nnz); cscCol.alloc((size_t)nnz); cscVal.alloc((size_t)nnz);
   bad.alloc(1);
   bad.zero(s);
-  hipLaunchKernelGGL(k_col_setup, dim3(gridFor(n0)), dim3(kT), 0, s, cIn.get(), clIn.get(), cuIn.get(), aStart.get(),
+  hipLaunchKernelGGL(k_col_setup, dim3(gridFor(n0)), dim3(kT), 0, s, in.colCost, in.colLower, in.colUpper, in.aStart,
                      n0, costSense, H ? 0 : 1, D.cost.get(), D.lower.get(), D.upper.get(), cscBeg.get());
-  hipLaunchKernelGGL(k_row_finish, dim3(gridFor(m)), dim3(kT), 0, s, rlIn.get(), ruIn.get(), kind.get(), eqR.get(),
+  hipLaunchKernelGGL(k_row_finish, dim3(gridFor(m)), dim3(kT), 0, s, in.rowLower, in.rowUpper, kind.get(), eqR.get(),
                      inR.get(), slR.get(), m, n0, nEq, nnz0, rowNew.get(), D.rhs.get(), D.cost.get(), D.lower.get(),
                      D.upper.get(), cscBeg.get(), cscIdx.get(), cscCol.get(), cscVal.get(),
                      H ? D.rowUpper.get() : nullptr);
@@ -758,7 +780,7 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
     PDLP_HIP(hipMemcpyAsync(cscBeg.get() + n, &last, sizeof(int32_t), hipMemcpyHostToDevice, s));
     PDLP_HIP(hipStreamSynchronize(s));
   }
-  hipLaunchKernelGGL(k_col_entries<false>, dim3(gridFor(n0)), dim3(kT), 0, s, aStart.get(), aIndex.get(), aValue.get(),
+  hipLaunchKernelGGL(k_col_entries<false>, dim3(gridFor(n0)), dim3(kT), 0, s, in.aStart, in.aIndex, in.aValue,
                      kind.get(), rowNew.get(), n0, m, cscIdx.get(), cscCol.get(), cscVal.get(), bad.get());
   if (fetchOne(bad.get(), s) != 0) throw std::runtime_error("row index out of range");
 
@@ -831,7 +853,8 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
   if (D.hessianReason == kHessOnDevice) {
     if (P.q_dim > P.num_col) throw std::runtime_error("Hessian dimension exceeds the number of columns");
     if (!P.q_index || !P.q_value) throw std::runtime_error("null Hessian arrays");
-    gpuExtractHessian(P, n, s, D);
+    if (in.hessian) gpuExtractHessianFromDevice(P, *in.hessian, n, s, D);
+    else gpuExtractHessian(P, n, s, D);
   } else {
     std::vector<double> q;
     Compressed off;
@@ -903,7 +926,13 @@ void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProb
   if (keepM) {  // the arrays a plain set-up frees here; the layouts take D.A's, so the row-major structure is copied
     MatrixKeep& K = D.keep;
     K.nnz0 = nnz0;
-    K.aStart = std::move(aStart); K.aIndex = std::move(aIndex);
+    if (in.ownStart.size()) {
+      K.aStart = std::move(in.ownStart); K.aIndex = std::move(in.ownIndex);
+    } else {  // the caller's own arrays in HBM: copied, the caller may free them after the return
+      K.aStart.alloc((size_t)n0 + 1); K.aIndex.alloc((size_t)nnz0);
+      PDLP_HIP(hipMemcpyAsync(K.aStart.get(), in.aStart, sizeof(int32_t) * ((size_t)n0 + 1), hipMemcpyDeviceToDevice, s));
+      if (nnz0 > 0) PDLP_HIP(hipMemcpyAsync(K.aIndex.get(), in.aIndex, sizeof(int32_t) * (size_t)nnz0, hipMemcpyDeviceToDevice, s));
+    }
     K.cscBeg = std::move(cscBeg); K.cscIdx = std::move(cscIdx); K.cscCol = std::move(cscCol); K.cscVal = std::move(cscVal);
     copyOf(K.aBeg, D.A.beg, s); copyOf(K.aMajor, D.A.major, s);
     K.aIdx.alloc((size_t)nnz); K.aVal.alloc((size_t)nnz);

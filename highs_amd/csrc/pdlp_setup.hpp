@@ -129,15 +129,36 @@ struct HipdlpSetup {
   bool ruiz = true, pc = true, l2 = false;
   int ruizIters = 10;
 };
-// Formulate + scale + both orientations on the device.  Throws std::runtime_error.
+// The caller's arrays in HBM, as the set-up reads them: gpuPrepare's uploads (ownStart / ownIndex then own a_start /
+// a_index, which a matrix-updatable solver takes over), or the arrays a device-resident entry was given (pdlp_resident.hpp;
+// nothing is owned, what is kept is copied).  hessian: the Hessian's arrays where they are in HBM already, else nullptr.
+struct DeviceHessianInputs {
+  const int32_t *qStart = nullptr, *qIndex = nullptr;
+  const double* qValue = nullptr;
+  DeviceArray<int32_t> ownStart, ownIndex;  // gpuExtractHessian's uploads: temporaries of the extraction
+  DeviceArray<double> ownValue;
+};
+struct DeviceInputs {
+  const int32_t *aStart = nullptr, *aIndex = nullptr;
+  const double *aValue = nullptr, *colCost = nullptr, *colLower = nullptr, *colUpper = nullptr, *rowLower = nullptr, *rowUpper = nullptr;
+  DeviceArray<int32_t> ownStart, ownIndex;
+  DeviceHessianInputs* hessian = nullptr;
+};
+// Formulate + scale + both orientations on the device.  Throws std::runtime_error.  gpuPrepare = validate + upload +
+// gpuPrepareFromDevice, which reads of P only the sizes, the scalars and HOST copies of a_start, col_cost, row_lower,
+// row_upper and q_start; every other array is taken from `in`.
 void gpuPrepare(const pdlp_problem_t& P, bool doScale, hipStream_t s, DeviceProblem& out,
                 const HipdlpSetup* hipdlp = nullptr);
+void gpuPrepareFromDevice(const pdlp_problem_t& P, DeviceInputs& in, bool doScale, hipStream_t s, DeviceProblem& out,
+                          const HipdlpSetup* hipdlp = nullptr);
 // The Hessian's extraction on the device, for gpuPrepare (pdlp_setup.hip; the rule above decides).  On entry the host's
 // own checks have passed (q_dim <= num_col, no null array) and q_start runs from 0 to q_start[q_dim] > 0 without
 // decreasing.  Writes D.qdiag and D.N (unscaled, with the sense) exactly as an upload of extractHessian's /
 // extractHessianKept's result would, D.kmap when D.keepHessianPattern, the counts and the two times; throws the host
 // walk's sentences.  Everything runs on s; synchronises.
 void gpuExtractHessian(const pdlp_problem_t& P, int32_t n, hipStream_t s, DeviceProblem& D);
+// gpuExtractHessian = upload + this; reads of P only q_dim and a HOST copy of q_start, the slots from `in`
+void gpuExtractHessianFromDevice(const pdlp_problem_t& P, DeviceHessianInputs& in, int32_t n, hipStream_t s, DeviceProblem& D);
 
 // ---- the value-dependent layer of gpuPrepare, shared with pdlp_mi355x_update_matrix (pdlp_update.cpp) ----------------
 // The formulated values of the caller's a_value in reference order: <= rows negated, -1.0 for the nSlack slack entries

@@ -4,6 +4,7 @@
 // reference's check iterations (nIter < 10, nIter % 40 == 0, last iteration).
 #include "pdlp_solver.hpp"
 #include "pdlp_detmath.h"
+#include "pdlp_resident.hpp"
 #include "pdlp_update.hpp"
 
 #include <algorithm>
@@ -461,11 +462,25 @@ Solver::Solver(const pdlp_problem_t& P, const pdlp_params_t& opt, int32_t rank, 
   }
 }
 
-void Solver::construct(const pdlp_problem_t& P, const void* id128) {
+Solver::Solver(ResidentProblem& RP, const pdlp_params_t& opt) : opt_(opt), rank_(0), world_(1) {
+  try {
+    construct(RP.shadow, nullptr, &RP);
+  } catch (...) {
+    release();
+    throw;
+  }
+}
+
+// resident (pdlp_mi355x_create_device): P is its host shadow, filled in below once the stream exists — a_start, costs, row
+// bounds, q_start and a hot start are host copies, every other array of P is the caller's pointer into HBM and is never
+// read here.  What the host entry finds by walking a_index, a_value, q_index, q_value is then found by kernels.
+void Solver::construct(const pdlp_problem_t& P, const void* id128, ResidentProblem* resident) {
   const auto t0 = std::chrono::steady_clock::now();
   if (world_ < 1 || rank_ < 0 || rank_ >= world_) throw std::runtime_error("bad rank/world");
-  validateProblem(P);
-  requireConstraints(P);
+  if (!resident) {
+    validateProblem(P);
+    requireConstraints(P);
+  }
   int nDev = 0;
   if (hipGetDeviceCount(&nDev) != hipSuccess || nDev <= 0)
     throw std::runtime_error("pdlp_mi355x: no HIP device available (this library has no CPU fallback)");
@@ -473,6 +488,12 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   PDLP_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   sw_ = DevSwitches::fromEnv();
   if (sw_.graph >= 0) useGraph_ = sw_.graph != 0;
+  if (resident) {
+    resident->fetchShadow(stream_);  // (orders stream_ behind the caller's stream first)
+    validateProblemStarts(P);
+    const int64_t nnz = P.num_col > 0 ? (int64_t)P.a_start[P.num_col] : 0;
+    if (P.num_row == 0 || P.num_col == 0 || nnz == 0) throwAllZeroMatrix();  // (requireConstraints' words; no index to look at)
+  }
 
   adaptive_ = !(opt_.features_off & PDLP_FEATURE_ADAPTIVE_STEP_OFF);
   restartOn_ = !(opt_.features_off & PDLP_FEATURE_RESTART_OFF) && opt_.restart_method != 0;
@@ -484,9 +505,11 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   const int64_t nnzIn = P.num_col > 0 && P.a_start ? (int64_t)P.a_start[P.num_col] : 0;
   gpuSetup_ = nnzIn >= 200000;
   if (sw_.gpuSetup >= 0) gpuSetup_ = sw_.gpuSetup != 0;
+  if (resident) gpuSetup_ = true;  // (the host set-up would need the matrix on the host; both give the same bits)
   // PDLP_UPDATABLE_HESSIAN: every slot of the Hessian the caller passes is kept, so the structure follows the pattern
   const bool keepQPattern = (opt_.updatable & PDLP_UPDATABLE_HESSIAN) != 0;
-  hasQoff_ = keepQPattern ? hessianHasOffDiagonalSlot(P) : hessianHasOffDiagonal(P);
+  if (resident) hasQoff_ = resident->hasOffDiagonalHessian(keepQPattern, sw_.gpuHessian != 0, stream_);
+  else hasQoff_ = keepQPattern ? hessianHasOffDiagonalSlot(P) : hessianHasOffDiagonal(P);
   // (one GPU: the off-diagonal part N of Q is extracted on the device, pdlp_setup.hip gpuExtractHessian — unless
   // PDLP_MI355X_GPU_HESSIAN=0 — scaled with the columns inside the device-side passes, k_scale_qoff, and its layouts are
   // built from the device arrays)
@@ -495,6 +518,7 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   // Not with an off-diagonal Hessian: neither downloadForm nor the shard cut on the device knows about N, so such a
   // sharded QP is prepared on the host (pdlp_host.cpp applyScaling)
   const bool shardedGpuSetup = sharded_ && gpuSetup_ && !hasQoff_;
+  if (sharded_ && resident) throw std::runtime_error("sharded solvers (sharding forced) do not take updates");  // (the entry has refused already)
   if (sharded_) gpuSetup_ = false;
   const bool doScale = !(opt_.features_off & PDLP_FEATURE_SCALING_OFF);
   updatable_ = opt_.updatable != 0 && !sharded_;  // (a sharded solver refuses updates: nothing to keep)
@@ -513,7 +537,14 @@ void Solver::construct(const pdlp_problem_t& P, const void* id128) {
   F_.keepPasses = updatable_;
   if (gpuSetup_) {
     // formulate + scale + both orientations on the device; F_ keeps only the host-side bookkeeping
-    gpuPrepare(P, doScale, stream_, devProb);
+    if (resident) {
+      // create's order: a row index out of range (validateProblem; here k_col_entries inside the set-up) comes before the
+      // all-zero matrix (requireConstraints; here the absolute maximum of the caller's values)
+      gpuPrepareFromDevice(P, resident->in, doScale, stream_, devProb);
+      if (gpuAbsMax(resident->in.aValue, nnzIn, stream_) == 0.0) throwAllZeroMatrix();
+    } else {
+      gpuPrepare(P, doScale, stream_, devProb);
+    }
     F_ = StandardForm();
     F_.n = devProb.n; F_.m = devProb.m; F_.n0 = devProb.n0; F_.nEqs = devProb.nEqs; F_.nnz = devProb.nnz;
     F_.scaled = devProb.scaled; F_.offset = devProb.offset; F_.sense = devProb.sense;
@@ -2211,7 +2242,7 @@ void Solver::run(pdlp_result_t* R) {
 }
 
 // What run() does behind its loop (a batch lane ends its run here too): the summary and the post-solve.
-void Solver::finishRun(pdlp_result_t* R) {
+void Solver::finishRun(pdlp_result_t* R, bool resultOnDevice) {
   solveSeconds_ = elapsed();
   if (opt_.log_level > 0 && rank_ == 0) {
     const Residuals& r = (termCode_ == PDLP_TERM_OPTIMAL && termIterate_ == 1) ? avg_ : cur_;
@@ -2225,7 +2256,8 @@ void Solver::finishRun(pdlp_result_t* R) {
            r.dFeas / (1.0 + F_.normCost), "Duality gap (rel):", r.relGap, "Number of iterations:",
            hostState_->nIter);
   }
-  if (R) postsolve(R);
+  if (R && resultOnDevice) postsolveDevice(R);
+  else if (R) postsolve(R);
 }
 
 void Solver::iterate(int32_t nIters, pdlp_iter_stats_t* st) {
@@ -2312,6 +2344,11 @@ void Solver::postsolve(pdlp_result_t* R) {
     }
     rd = true;
   }
+  postsolveScalars(R, cv, cd, rv, rd);
+}
+
+void Solver::postsolveScalars(pdlp_result_t* R, bool cv, bool cd, bool rv, bool rd) {
+  const bool useAvg = (termCode_ == PDLP_TERM_OPTIMAL && termIterate_ == 1);
   const Residuals& r = useAvg ? avg_ : cur_;
   R->value_valid = cv && rv;
   R->dual_valid = cd && rd;

@@ -101,6 +101,8 @@ void buildSlabTuned(DeviceMatrix& out, DeviceCsrData& M, const DevSwitches& sw, 
 
 class Comm;  // RCCL wrapper (pdlp_comm.cpp)
 struct DataStage;          // pdlp_update.hpp
+struct ValueUpdateFacts;   // pdlp_update.hpp
+struct ResidentProblem;    // pdlp_resident.hpp
 struct LaneUnit;           // pdlp_batch.hpp
 enum LaneVerdict : int;    // pdlp_batch.hpp
 
@@ -134,11 +136,18 @@ class SolverBase {
   // New tolerances, limits and log sink for the runs that follow (pdlp_params_t primal_tol, dual_tol, gap_tol, time_limit,
   // iter_limit, log_level, log_callback, log_ctx); every other field of opt is ignored.  Only the cuPDLP-C path takes them.
   virtual void setRuntimeOptions(const pdlp_params_t& opt);
+  // pdlp_mi355x_run_device / pdlp_mi355x_update_device (pdlp_resident.hpp): the four vectors of R, every array of u and
+  // a_value / q_value are in HBM on the solver's device.  Only the cuPDLP-C path takes them.
+  virtual void runDevice(pdlp_result_t* R);
+  virtual void updateDevice(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t* u,
+                            hipStream_t callerStream);
 };
 
 class Solver : public SolverBase {
  public:
   Solver(const pdlp_problem_t& P, const pdlp_params_t& opt, int32_t rank, int32_t world, const void* id128);
+  // pdlp_mi355x_create_device: the problem's arrays are in HBM on opt.device (pdlp_resident.cpp fills RP's host shadow)
+  Solver(ResidentProblem& RP, const pdlp_params_t& opt);
   ~Solver() override;
 
   void run(pdlp_result_t* R) override;                          // LP_SolvePDHG
@@ -156,6 +165,9 @@ class Solver : public SolverBase {
   void updateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz,
                     const pdlp_update_t* u) override;  // pdlp_update.cpp
   void setRuntimeOptions(const pdlp_params_t& opt) override;  // pdlp_session.cpp
+  void runDevice(pdlp_result_t* R) override;  // pdlp_resident.cpp
+  void updateDevice(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t* u,
+                    hipStream_t callerStream) override;  // pdlp_resident.cpp
 
   // ---- what a session drives (pdlp_session.hpp; all in pdlp_session.cpp) ----
   // The caller's a_value, costs, bounds and (QPs) Hessian arrays into HBM copies of their own, for later comparisons.
@@ -189,6 +201,7 @@ class Solver : public SolverBase {
   // a solver without PDLP_UPDATABLE_HESSIAN —, the all-zero matrix and the negative diagonal included; nothing of the
   // solver's problem is changed (the Hessian's values go through the update's own staging buffer and validation kernel)
   void validateValues(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t& u) const;
+  ValueUpdateFacts valueUpdateFacts() const;  // what those refusals depend on, from this solver (pdlp_update.hpp)
   void laneBegin();
   bool laneIdle() const { return loop_.noLoop; }  // the iteration limit is reached before the first round: laneFinish may follow at once
   void laneQueue(int32_t ahead, std::vector<LaneUnit>& units);
@@ -205,7 +218,7 @@ class Solver : public SolverBase {
 
  private:
   // setup
-  void construct(const pdlp_problem_t& P, const void* id128);
+  void construct(const pdlp_problem_t& P, const void* id128, ResidentProblem* resident = nullptr);
   void release() noexcept;
   void uploadProblem();
   void uploadProblemFromDevice(DeviceProblem& D);
@@ -277,13 +290,15 @@ class Solver : public SolverBase {
   // the records of a persistent trial launch and of a one-launch check, accounted for as launched: every caller's way to them
   SmallTrialsLaunch smallTrialsLaunch(int32_t maxTrials);
   CheckSmallLaunch checkSmallLaunch();
-  void finishRun(pdlp_result_t* R);
+  void finishRun(pdlp_result_t* R, bool resultOnDevice = false);
   void enqueueCheckDevice();
   void uploadCtl(bool terminate, int64_t iterLim);
   void downloadCtl();
   void processRecords(bool terminate, int64_t iterLim, int& logSinceHeader);
   void logCheckLine(int32_t it, const Residuals& cur, const Residuals& avg, double t, int& logSinceHeader) const;
   void postsolve(pdlp_result_t* R);
+  void postsolveDevice(pdlp_result_t* R);  // pdlp_resident.cpp: the same bits, the four vectors written in HBM
+  void postsolveScalars(pdlp_result_t* R, bool cv, bool cd, bool rv, bool rd);  // what both write to the host struct
   // linear algebra on device (sharding-aware)
   void deviceAx(const double* x, double* axLocal);
   void deviceATy(const double* yLocal, double* aty);
@@ -413,6 +428,10 @@ class Solver : public SolverBase {
   DeviceArray<int32_t> sessQPat_, updPat_, sessRec_;
   int32_t* hostRec_ = nullptr;
   int32_t sessQDim_ = 0;
+  // run_device (pdlp_resident.hpp): the rank among the ranged-or-free rows of every original row and, for a solver that is
+  // not updatable (rowKindDev_ / rowNewIdxDev_ are then empty), its kind and permuted index — uploaded by the first
+  // run_device (the kinds never change: an update that would change one is refused); stage "update_state" does not count them
+  DeviceArray<int32_t> postKind_, postNewIdx_, postRank_;
   enum { kUpdStage, kUpdKernels, kUpdSums, kUpdBounds, kUpdCapture, kUpdReset, kUpdSlots };
   double updSeconds_[kUpdSlots] = {};  // upload + validation, kernels, norms + sums, block bounds, graph capture, reset
   int32_t barrierFallbacks_ = 0, smallLaunches_ = 0;

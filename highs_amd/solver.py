@@ -51,6 +51,7 @@ EXPORTS = [
     "pdlp_mi355x_batch_create", "pdlp_mi355x_batch_run", "pdlp_mi355x_batch_info", "pdlp_mi355x_batch_destroy",
     "pdlp_mi355x_batch_info_size", "pdlp_mi355x_batch_run_values", "pdlp_mi355x_variant_size",
     "pdlp_mi355x_solve_many", "pdlp_mi355x_pool_info_size",
+    "pdlp_mi355x_create_device", "pdlp_mi355x_update_device", "pdlp_mi355x_run_device",
 ]
 
 
@@ -70,6 +71,14 @@ def lib():
             raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                                "(the PDLP path has no CPU fallback)")
         L = C.CDLL(LIB_PATH)
+        # One HIP runtime per process (tensors.py): a PyTorch wheel bundles a libamdhip64 of its own and asks for it by the
+        # name "libamdhip64.so".  Registering the copy this library has just brought in under that name makes a LATER
+        # `import torch` bind to it instead of loading a second runtime, which would find no device (or leave this one
+        # without).  With torch imported first the library has bound to torch's copy already; without torch this is a no-op.
+        try:
+            C.CDLL("libamdhip64.so", mode=C.RTLD_GLOBAL)
+        except OSError:
+            pass
         pP, pO, pR = C.POINTER(abi.PdlpProblem), C.POINTER(abi.PdlpParams), C.POINTER(abi.PdlpResult)
         H = C.c_void_p
         L.pdlp_mi355x_default_params.argtypes = [pO]
@@ -152,6 +161,13 @@ def lib():
             if L.pdlp_mi355x_pool_info_size() != C.sizeof(abi.PdlpPoolInfo):
                 raise RuntimeError("pdlp_pool_info_t: the library's size %d differs from abi.PdlpPoolInfo's %d" %
                                    (L.pdlp_mi355x_pool_info_size(), C.sizeof(abi.PdlpPoolInfo)))
+        # (a build from before the device-resident entries, given through PDLP_MI355X_LIB: tools/resident_bench.py's host side)
+        if hasattr(L, "pdlp_mi355x_create_device"):
+            L.pdlp_mi355x_create_device.argtypes = [pP, pO, C.c_void_p, C.POINTER(H)]
+            L.pdlp_mi355x_update_device.argtypes = [H, abi.c_f64p, C.c_int64, abi.c_f64p, C.c_int64, pU, C.c_void_p]
+            L.pdlp_mi355x_run_device.argtypes = [H, pR]
+            # (a test hook outside the public header: update_device's refusals that need no device)
+            L.pdlp_mi355x_host_update_device_refusal.argtypes = [pP, pO, abi.c_f64p, C.c_int64, abi.c_f64p, C.c_int64, pU]
         L.pdlp_mi355x_row_partition.argtypes = [pPrep, C.c_int32, abi.c_i32p]
         pSlab = C.POINTER(abi.PdlpSlabLayout)
         L.pdlp_mi355x_host_slab_layout.argtypes = [pPrep, C.c_int32, C.c_int32, pSlab]
@@ -538,6 +554,100 @@ class DeviceSolver:
             if offset is not None:
                 lp.offset = float(offset)
             self.lp = lp
+
+    # ---- problems, updates and solutions as tensors in HBM (tensors.py; include/pdlp_mi355x.h "device-resident entries") ----
+    @classmethod
+    def from_tensors(cls, tp, start=None, **options):
+        """pdlp_mi355x_create_device: a solver for a tensors.TensorProblem, whose arrays are in HBM already.  Bit for bit
+        the solver DeviceSolver(lp, **options) is for the same problem in numpy arrays.  start: dict with col_value,
+        row_value, row_dual as tensors on tp's device, or None.  The library reads the tensors behind torch's current
+        stream; they may be changed or freed once this returns."""
+        import torch
+
+        from . import tensors as T
+
+        if not isinstance(tp, T.TensorProblem):
+            raise TypeError("from_tensors: a tensors.TensorProblem is needed, got %s" % type(tp).__name__)
+        self = cls.__new__(cls)
+        given = options.pop("params", None)
+        self.params = given or abi.default_params(**options)
+        if given is None and "device" not in options:
+            self.params.device = T.device_ordinal(tp.device)
+        elif self.params.device != T.device_ordinal(tp.device):
+            raise ValueError("from_tensors: the problem is on %s, the options ask for device %d" % (tp.device, self.params.device))
+        T.init()
+        self._keep = None
+        self.lp = None
+        self.h = C.c_void_p()
+        P, keep = tp.struct(start)
+        with torch.cuda.device(tp.device):
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = lib().pdlp_mi355x_create_device(C.byref(P), C.byref(self.params), C.c_void_p(stream), C.byref(self.h))
+        del keep
+        _check(rc, "pdlp_mi355x_create_device")
+        n, m, nnz, ne = C.c_int32(), C.c_int32(), C.c_int64(), C.c_int32()
+        _check(lib().pdlp_mi355x_dims(self.h, C.byref(n), C.byref(m), C.byref(nnz), C.byref(ne)), "dims")
+        self.n, self.m, self.nnz, self.n_eqs = n.value, m.value, nnz.value, ne.value
+        self.num_col, self.num_row = tp.num_col, tp.num_row
+        return self
+
+    def _tensor_device(self):
+        import torch
+
+        return torch.device("cuda", self.params.device)
+
+    def _tensor_sizes(self):
+        if getattr(self, "num_col", None) is not None:
+            return self.num_col, self.num_row
+        if self.lp is not None:
+            return self.lp.num_col, self.lp.num_row
+        raise ValueError("the solver was built from a problem struct: set num_col and num_row on it first")
+
+    def update_tensors(self, a_value=None, q_value=None, col_cost=None, col_lower=None, col_upper=None, row_lower=None,
+                       row_upper=None, offset=None, start=None):
+        """pdlp_mi355x_update_device: update() / update_matrix() / update_values() with every array a float64 tensor on the
+        solver's device (None = unchanged; start: dict of three tensors or None = cold start).  Neither a_value nor q_value:
+        a data update; a_value alone on a solver without updatable="...hessian": a matrix update; else a value update.  The
+        tensors are read behind torch's current stream, without synchronising it, and may be changed once this returns.
+        Raises with the library's message when the update is refused (the solver is then unchanged).  self.lp, a host
+        copy, does not follow: read results with run_tensors()."""
+        import torch
+
+        from . import tensors as T
+
+        dev = self._tensor_device()
+        n0, m = self._tensor_sizes()
+        if a_value is not None:
+            T.check_tensor("a_value", a_value, "float64", None, dev)
+        if q_value is not None:
+            T.check_tensor("q_value", q_value, "float64", None, dev)
+        U = T.TensorUpdate(n0, m, dev, col_cost, col_lower, col_upper, row_lower, row_upper, offset, start)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream().cuda_stream
+            rc = lib().pdlp_mi355x_update_device(self.h, T.pointer(a_value, abi.c_f64p), 0 if a_value is None else a_value.numel(),
+                                                 T.pointer(q_value, abi.c_f64p), 0 if q_value is None else q_value.numel(),
+                                                 C.byref(U.struct), C.c_void_p(stream))
+        _check(rc, "pdlp_mi355x_update_device")
+
+    def run_tensors(self, out=None):
+        """pdlp_mi355x_run_device -> tensors.TensorResult: col_value, col_dual, row_value, row_dual as float64 tensors on
+        the solver's device — those given in `out` (a dict by these names; a loop reuses its buffers), fresh ones
+        otherwise — and the scalars of pdlp_result_t.  The tensors are complete when this returns.  With `out`, torch's
+        current stream is synchronised first: work queued there may still read the previous solution from those tensors,
+        and the library writes them on a stream of its own."""
+        import torch
+
+        from . import tensors as T
+
+        n0, m = self._tensor_sizes()
+        dev = self._tensor_device()
+        R = T.TensorResult(n0, m, dev, out)
+        with torch.cuda.device(dev):
+            if out:  # (run_device takes no stream: what torch has queued that still reads the given tensors ends first)
+                torch.cuda.current_stream().synchronize()
+            rc = lib().pdlp_mi355x_run_device(self.h, C.byref(R.struct))
+        _check(rc, "pdlp_mi355x_run_device")
+        return R
 
     def solve(self):
         """pdlp_mi355x_run on the held problem, returned as solveLpCupdlp returns it: a family of LPs over one matrix

@@ -20,6 +20,7 @@
  *                          cupdlp_solver.c:1437-1498          pdlp_mi355x_run
  *   PDHG_Destroy + frees   CupdlpWrapper.cpp:218,253-269      pdlp_mi355x_destroy
  *   (all of the above, one shot)                              pdlp_mi355x_solve
+ *   (create / run with every array in HBM already)            pdlp_mi355x_create_device, pdlp_mi355x_run_device
  *
  * Plain C types only: pointers, sizes, doubles, int32. No C++/torch types.
  * All input arrays are caller-owned and read-only; all output arrays are
@@ -458,6 +459,56 @@ int pdlp_mi355x_solve_many(int32_t K, const pdlp_problem_t* const* P, const pdlp
                            pdlp_result_t* R, int32_t* path /* [K] PDLP_POOL_*, may be NULL */,
                            pdlp_pool_info_t* info /* may be NULL */);
 int64_t pdlp_mi355x_pool_info_size(void); /* sizeof(pdlp_pool_info_t); pdlp_mi355x_sizeof keeps its indices */
+
+/* ---- device-resident entries: problems, updates and solutions as arrays already in HBM -------------
+ * For callers that produce the next problem's data on the GPU and read the solution there (successive linear programming,
+ * SQP, MPC, scenario sweeps, a training loop around an LP / QP layer): nothing bounces through host memory.  The structs
+ * above are reused; in these entries EVERY ARRAY POINTER inside them is a pointer into HBM ON THE SOLVER'S DEVICE
+ * (pdlp_params_t.device), scalars and the struct itself stay in host memory.
+ *
+ * stream: the hipStream_t (as void*) on which the caller produced the arrays; the library orders its own stream behind an
+ * event recorded there and never synchronises the caller's stream.  NULL: the arrays are complete, or were produced on the
+ * default stream (the event is then recorded there).  The caller's arrays are read-only, and may be reused or freed as soon
+ * as the call returns; results are complete when the call returns.
+ *
+ * THE POINTER CHECK: before its first launch or copy each entry asks the runtime about every non-NULL array pointer it was
+ * given (hipPointerGetAttributes).  Host memory — pageable, pinned or registered —, managed memory and another device's
+ * memory are refused: non-zero return, pdlp_mi355x_last_error names the field ("pdlp_mi355x_update_device: col_cost is not
+ * device memory on device 0"), the solver stays as it was.
+ *
+ * pdlp_mi355x_create_device: the solver is, bit for bit, the one pdlp_mi355x_create gives for the same problem in host arrays
+ * with the same opt.  Algorithm 0 on one device: HiPDLP, num_devices > 1 and forced sharding are refused before any device
+ * call.  Always the device-side set-up; the library downloads a_start, col_cost, row_lower, row_upper, q_start and a hot
+ * start (O(num_col + num_row): the monotone checks and the left-to-right norms are the host's), never a_index, a_value,
+ * q_index or q_value — a row index out of range, an entry above the diagonal, an all-zero matrix are found by kernels and
+ * refused in pdlp_mi355x_create's words.  A Hessian whose q_start does not run from 0 without decreasing is refused.
+ *
+ * pdlp_mi355x_update_device: ONE entry for the three updates, routed as pdlp_mi355x_batch_run_values routes a variant —
+ *     neither array ................................................ pdlp_mi355x_update(s, u)
+ *     a_value only, a solver without PDLP_UPDATABLE_HESSIAN ......... pdlp_mi355x_update_matrix(s, a_value, num_nz, u)
+ *     otherwise .................................................... pdlp_mi355x_update_values(s, a_value, num_nz, q_value, num_q_nz, u)
+ * with that entry's checks, order, words (behind "pdlp_mi355x_update_device: ") and all-or-nothing rule; afterwards the
+ * solver has the bits that entry gives for the same arrays in host memory.  The staging copy is device to device; costs,
+ * row bounds and a start are also downloaded (the ordered norms, the kind-change message, the start's formulation).
+ *
+ * pdlp_mi355x_run_device: pdlp_mi355x_run with the four vectors of R in HBM: the loop is the same, the post-solve runs as
+ * kernels and gives the bits of the host's.  A NULL vector is skipped; value_valid, dual_valid, every count and scalar are
+ * written to the host struct as always.  Sharded solvers are refused.  The entry takes no stream: whatever the caller has
+ * queued that still READS the vectors of R (the previous solution, where a loop reuses its buffers) must have completed
+ * before the call — the post-solve overwrites them on the library's own stream.
+ *
+ * SIZES are the caller's contract, as in every other entry: the pointer check establishes where an array lives, not how
+ * long it is; each array must hold the count its field's comment gives.
+ *
+ * The solver does not remember where its problem came from: host and device entries mix freely on one solver. */
+int pdlp_mi355x_create_device(const pdlp_problem_t* P_dev, const pdlp_params_t* opt, void* stream, pdlp_mi355x_solver_t** out);
+int pdlp_mi355x_update_device(pdlp_mi355x_solver_t* s, const double* a_value_dev, int64_t num_nz, const double* q_value_dev,
+                              int64_t num_q_nz, const pdlp_update_t* u_dev, void* stream);
+int pdlp_mi355x_run_device(pdlp_mi355x_solver_t* s, pdlp_result_t* R_dev);
+/* ONE HIP RUNTIME PER PROCESS: the caller's arrays and this library must live in the same copy of the HIP runtime.  A
+ * process that holds two — a PyTorch wheel bundles its own libamdhip64 — has the GPU in whichever started first; the other
+ * finds no device ("no HIP device available").  highs_amd.solver.lib() registers the system's copy under the name a later
+ * `import torch` asks for, so both share it. */
 
 /* Host-only restatement of the session's decision for the CPU tests: `held` / held_opt are the problem and options of the
  * previous call (held == NULL: nothing is held), P / opt those of this one.  Same ladder (one function shared with the
