@@ -2364,6 +2364,26 @@ void Solver::postsolveScalars(pdlp_result_t* R, bool cv, bool cd, bool rv, bool 
 }
 
 // ---- test / measurement hooks -----------------------------------------------------
+namespace {
+// "trial_state": every scalar of DevState (pdlp_kernels.hpp) — what one trial's decision reads or writes — in this order.
+// The two table pointers are not part of it: refreshPowTable owns them, powBase / powCount say what they cover.
+constexpr int kTrialStateLen = 27;
+void trialStateToArray(const DevState& s, double* v) {
+  const double a[kTrialStateLen] = {
+      s.eta, s.beta, s.tau, s.sigma, s.primalStep, s.dualStep, s.sumPrimalStep, s.sumDualStep, s.avgW, s.avgWx, s.dX2, s.dY2, s.inter,
+      s.movement, s.limit, s.qint, (double)s.nIter, (double)s.nTrials, (double)s.cur, (double)s.halted, (double)s.haltIter,
+      (double)s.adaptive, (double)s.lastAccepted, (double)s.powBase, (double)s.powCount, (double)s.commError, (double)s.pending};
+  std::copy(a, a + kTrialStateLen, v);
+}
+// (powBase, powCount, commError and pending are read-only: the next pushState decides the first two and clears the last)
+void arrayToTrialState(const double* v, DevState& s) {
+  s.eta = v[0]; s.beta = v[1]; s.tau = v[2]; s.sigma = v[3]; s.primalStep = v[4]; s.dualStep = v[5]; s.sumPrimalStep = v[6];
+  s.sumDualStep = v[7]; s.avgW = v[8]; s.avgWx = v[9]; s.dX2 = v[10]; s.dY2 = v[11]; s.inter = v[12]; s.movement = v[13];
+  s.limit = v[14]; s.qint = v[15]; s.nIter = (int32_t)v[16]; s.nTrials = (int32_t)v[17]; s.cur = (int32_t)v[18] & 1;
+  s.halted = (int32_t)v[19]; s.haltIter = (int32_t)v[20]; s.adaptive = (int32_t)v[21]; s.lastAccepted = (int32_t)v[22];
+}
+}  // namespace
+
 std::pair<double*, int64_t> Solver::lookup(const std::string& name) {
   const int c = hostState_->cur, u = c ^ 1;
   const int64_t n = F_.n, m = mLoc_;
@@ -2408,6 +2428,12 @@ void Solver::getVector(const std::string& name, double* host, int64_t len) {
     for (int64_t i = 0; i < len && i < 8; ++i) host[i] = v[i];
     return;
   }
+  if (name == "trial_state") {  // TEST HOOK: every scalar of the device's state record (trialStateToArray has the order)
+    if (sharded_) throw std::runtime_error("trial_state: not on a sharded solver");
+    if (len != kTrialStateLen) throw std::runtime_error("length mismatch for trial_state (" + std::to_string(kTrialStateLen) + ")");
+    trialStateToArray(*hostState_, host);
+    return;
+  }
   // a Hessian-updatable solver's kept assembly map (pdlp_host.hpp HessianMap), read-only: 32-bit integers, exact in doubles
   // (srcSlot: the first `len` of its dstBeg[n + nOff] entries)
   auto mapArray = [&](const char* mapName, const DeviceArray<int32_t>& arr, int64_t count) {
@@ -2437,6 +2463,16 @@ void Solver::setVector(const std::string& name, const double* host, int64_t len)
     s.tau = host[0]; s.sigma = host[1]; s.beta = host[2];
     s.eta = std::sqrt(s.tau * s.sigma);
     s.primalStep = s.tau; s.dualStep = s.sigma;
+    pushState();
+    return;
+  }
+  if (name == "trial_state") {  // TEST HOOK: plants the scalars a trial starts from.  Through pushState, as the loop's own
+    // stops: the power table follows the planted trial counter (refreshPowTable), nothing is pending.  The arrival words of
+    // the grid barriers follow the trial counter, which may now start lower: zeroed, as by reset().
+    if (sharded_) throw std::runtime_error("trial_state: not on a sharded solver");
+    if (len != kTrialStateLen) throw std::runtime_error("length mismatch for trial_state (" + std::to_string(kTrialStateLen) + ")");
+    arrayToTrialState(host, *hostState_);
+    if (fused_ || persistent_) { gridBar_.zero(stream_); smallSeq_ = 0; }
     pushState();
     return;
   }
@@ -2484,6 +2520,16 @@ void Solver::stage(const std::string& name, double* out, int32_t cap) {
     hostState_->halted = 0;
     pushState();
     enqueueTrial();
+    syncState();
+    const DevState& s = *hostState_;
+    put(0, s.dX2); put(1, s.dY2); put(2, s.inter); put(3, (double)s.lastAccepted);
+    put(4, s.tau); put(5, s.sigma); put(6, s.eta); put(7, s.movement); put(8, s.limit); put(9, s.qint);
+  } else if (name == "trial_as_is") {  // the same trial from the state as it stands: a planted haltIter halts the device, a halted
+    // device takes no trial, and nothing is pushed — the fused form goes on from the primal step its last launch left, as its loop does
+    if (sharded_) throw std::runtime_error("trial_as_is: not on a sharded solver");
+    BarrierRound round{*this, beginBarrierRound()};
+    enqueueTrial();
+    endBarrierRound(round.gate);
     syncState();
     const DevState& s = *hostState_;
     put(0, s.dX2); put(1, s.dY2); put(2, s.inter); put(3, (double)s.lastAccepted);

@@ -132,6 +132,12 @@ typedef struct {
   int slabA, slabAt, nLongA, nLongAt, chunkA, chunkAt;
   int *longMapA, *longMapAt, *longBegA, *longBegAt;
   double *gPartA, *gPartB, *gStat;
+  /* optional per-trial read-out (pdlp_oracle_solve_trials): reads the solve, changes nothing in it */
+  pdlp_oracle_trial_fn trialFn;
+  void* trialCtx;
+  double lastDX2, lastDY2; /* the two halves of the last movement */
+  pdlp_oracle_trial_t held; /* an accepted trial waits here for update_average's step sums */
+  int haveHeld;
 } Work;
 
 static double* dalloc(long n) { return (double*)calloc((size_t)(n > 0 ? n : 1), sizeof(double)); }
@@ -817,6 +823,7 @@ static void movement_interaction(Work* w, double* movement, double* interaction,
     double dX2, dY2;
     g_trial_sums(w, &dX2, &dY2, interaction, qint);
     *movement = dX2 * 0.5 * sb + dY2 / (2.0 * sb);
+    w->lastDX2 = dX2; w->lastDY2 = dY2;
     return;
   }
   double* d2 = w->bufMax2;
@@ -829,6 +836,7 @@ static void movement_interaction(Work* w, double* movement, double* interaction,
   memcpy(d3, w->aty[c], sizeof(double) * (size_t)n); o_axpy(n, -1.0, w->aty[u], d3);
   *interaction = o_dot(n, d2, d3);
   *movement = dX * 0.5 * sb + dY / (2.0 * sb);
+  w->lastDX2 = dX; w->lastDY2 = dY;
   if (w->qnBeg) { /* dx . N dx (d2 still holds x - x+) */
     memcpy(d3, w->nx[c], sizeof(double) * (size_t)n); o_axpy(n, -1.0, w->nx[u], d3);
     *qint = o_dot(n, d2, d3);
@@ -860,6 +868,12 @@ static int update_adaptive(Work* w) {
     }
     const double first = (1.0 - pow(w->nStepSizeIter + 1.0, -0.3)) * limit;  /* cupdlp_defs.h:29-31 */
     const double second = (1.0 + pow(w->nStepSizeIter + 1.0, -0.6)) * eta;
+    if (w->trialFn) { /* read-out only */
+      pdlp_oracle_trial_t t = {w->nIter, w->nStepSizeIter, done, eta, tau, sigma, w->beta, w->lastDX2, w->lastDY2, inter, qint, mov, limit,
+                               fmin(first, second), w->primalStep, w->dualStep, w->sumPrimalStep, w->sumDualStep};
+      if (done) { w->held = t; w->haveHeld = 1; }
+      else w->trialFn(w->trialCtx, &t);
+    }
     eta = fmin(first, second);
   }
   w->primalStep = eta / sqrt(w->beta);
@@ -886,6 +900,12 @@ static void update_average(Work* w) {
   o_axpy(w->m, wgt, w->y[u], w->ySum);
   w->sumPrimalStep += wgt;
   w->sumDualStep += wgt;
+  if (w->trialFn && w->haveHeld) { /* the accepted trial's record, now that its step sizes and sums are known */
+    w->held.primal_step = w->primalStep; w->held.dual_step = w->dualStep;
+    w->held.sum_primal_step = w->sumPrimalStep; w->held.sum_dual_step = w->sumDualStep;
+    w->haveHeld = 0;
+    w->trialFn(w->trialCtx, &w->held);
+  }
 }
 /* PDHG_Compute_Average_Iterate :377-420 */
 static void compute_average(Work* w) {
@@ -1233,12 +1253,13 @@ static int work_setup(Work* w, const pdlp_problem_t* P, const pdlp_params_t* opt
   return 0;
 }
 
-int pdlp_oracle_solve_traced(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R,
-                             pdlp_oracle_trace_fn trace, void* trace_ctx) {
+static int solve_read_out(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R, pdlp_oracle_trace_fn trace,
+                          void* trace_ctx, pdlp_oracle_trial_fn trial, void* trial_ctx) {
   if (!P || !opt || !R) return 1;
   Work w;
   const double t0 = o_now();
   if (work_setup(&w, P, opt)) { work_free(&w); return 1; }
+  w.trialFn = trial; w.trialCtx = trial_ctx; w.haveHeld = 0;
   const double t1 = o_now();
   /* LP_SolvePDHG cupdlp_solver.c:1437-1498 */
   presolve_hot_start(&w, P);
@@ -1262,6 +1283,17 @@ int pdlp_oracle_solve_traced(const pdlp_problem_t* P, const pdlp_params_t* opt, 
   postsolve(&w, R);
   work_free(&w);
   return 0;
+}
+
+int pdlp_oracle_solve_traced(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R,
+                             pdlp_oracle_trace_fn trace, void* trace_ctx) {
+  return solve_read_out(P, opt, R, trace, trace_ctx, NULL, NULL);
+}
+/* The same solve with one record per trial of the adaptive rule (pdlp_oracle_trial_t): a rejected trial's at once, an
+ * accepted one's behind PDHG_Update_Average. */
+int pdlp_oracle_solve_trials(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R,
+                             pdlp_oracle_trial_fn trial, void* trial_ctx) {
+  return solve_read_out(P, opt, R, NULL, NULL, trial, trial_ctx);
 }
 
 int pdlp_oracle_solve(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R) {

@@ -28,6 +28,20 @@ int pdlp_oracle_solve(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_re
 int pdlp_oracle_solve_traced(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R,
                              pdlp_oracle_trace_fn trace, void* trace_ctx);
 
+/* One trial of the adaptive step rule (cupdlp_step.c:237-306) as the solve took it: the state it started from (eta, tau,
+ * sigma, beta), its sums, its decision, the eta the rule leaves, and the step sizes and step sums behind it — those of
+ * PDHG_Update_Average for an accepted trial, unchanged ones for a rejected trial. */
+typedef struct pdlp_oracle_trial {
+  int iter, trials, accepted; /* trials: nStepSizeIter including this one */
+  double eta, tau, sigma, beta;
+  double dx2, dy2, inter, qint, movement, limit;
+  double eta_out;
+  double primal_step, dual_step, sum_primal_step, sum_dual_step;
+} pdlp_oracle_trial_t;
+typedef void (*pdlp_oracle_trial_fn)(void* ctx, const pdlp_oracle_trial_t* t);
+int pdlp_oracle_solve_trials(const pdlp_problem_t* P, const pdlp_params_t* opt, pdlp_result_t* R,
+                             pdlp_oracle_trial_fn trial, void* trial_ctx);
+
 /* block boundaries of the slab layout as the device-order mode models them; blockBeg needs 256 + nMajor / 16 + 3 ints */
 int pdlp_oracle_slab_blocks(int nMajor, int nMinor, const int* beg, const int* idx, int longLimit, int which, int* blockBeg);
 /* exp(x[i]) and log(x[i]) of the oracle's own plain-arithmetic functions (det_math.h) */

@@ -22,6 +22,15 @@ class Trace(C.Structure):
 TRACE_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(Trace))
 
 
+class Trial(C.Structure):  # pdlp_oracle_trial_t
+    _fields_ = [("iter", C.c_int), ("trials", C.c_int), ("accepted", C.c_int)] + [
+        (k, C.c_double) for k in ("eta", "tau", "sigma", "beta", "dx2", "dy2", "inter", "qint", "movement", "limit", "eta_out",
+                                  "primal_step", "dual_step", "sum_primal_step", "sum_dual_step")]
+
+
+TRIAL_FN = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(Trial))
+
+
 class Formulated(C.Structure):
     _fields_ = [("n", C.c_int), ("m", C.c_int), ("n_eqs", C.c_int), ("nnz", C.c_long),
                 ("csc_beg", abi.c_i32p), ("csc_idx", abi.c_i32p), ("csc_val", abi.c_f64p),
@@ -101,6 +110,25 @@ def _solve_with(fn, lp, params, start=None, trace=None):
 def oracle_solve(lp, params=None, start=None, trace=None, **kw):
     params = params or abi.default_params(**kw)
     return _solve_with(oracle().pdlp_oracle_solve, lp, params, start, trace)
+
+
+def oracle_solve_trials(lp, params=None, **kw):
+    """pdlp_oracle_solve_trials: (result, one dict per trial of the adaptive step rule, in the order the solve took them)."""
+    params = params or abi.default_params(**kw)
+    lib = oracle()
+    lib.pdlp_oracle_solve_trials.argtypes = lib.pdlp_oracle_solve.argtypes + [TRIAL_FN, C.c_void_p]
+    lib.pdlp_oracle_solve_trials.restype = C.c_int
+    P = abi.ProblemHandle(lp)
+    R = abi.ResultHandle(lp.num_col, lp.num_row)
+    recs = []
+
+    def cb(_ctx, t):
+        recs.append({k: getattr(t.contents, k) for k, _ in Trial._fields_})
+
+    rc = lib.pdlp_oracle_solve_trials(C.byref(P.struct), C.byref(params), C.byref(R.struct), TRIAL_FN(cb), None)
+    if rc != 0:
+        raise RuntimeError("oracle solve failed rc=%d" % rc)
+    return R, recs
 
 
 def ref_solve(lp, params=None, start=None, **kw):
