@@ -90,19 +90,24 @@ def options(values):
     return dict(solver="hipdlp", pdlp_features_off=1) if values == "integer" else dict(solver="hipdlp")
 
 
-Form = namedtuple("Form", "n m n_eqs A cost rhs lower upper col_scale row_scale norm_cost norm_rhs")
+Form = namedtuple("Form", "n m n_eqs A cost rhs lower upper col_scale row_scale norm_cost norm_rhs row_upper")
 _forms = {}
 
 
+def formulated_lp(lp, values):
+    """Any LP as the oracle's own formulation and scaling of this path hold it (hipdlp_oracle_prepare: independent of the
+    product's set-up, which other tests compare with it array for array), under options(values)."""
+    P = O.hipdlp_prepared(lp, **{k: v for k, v in options(values).items() if k != "solver"})
+    A = sp.csc_matrix((P["val"], P["idx"], P["beg"]), shape=(P["m"], P["n"]))
+    return Form(P["n"], P["m"], P["n_eqs"], A, P["cost"], P["row_lower"], P["lower"], P["upper"], P["col_scale"],
+                P["row_scale"], P["norm_cost"], P["norm_rhs"], P["row_upper"])
+
+
 def formulated(size, values):
-    """The problem as the oracle's own formulation and scaling of this path hold it (hipdlp_oracle_prepare: independent of the
-    product's set-up, which other tests compare with it array for array)."""
+    """formulated_lp of a case of this file.  Made once."""
     key = (case_name(size), values)
     if key not in _forms:
-        P = O.hipdlp_prepared(case_lp(size, values), **{k: v for k, v in options(values).items() if k != "solver"})
-        A = sp.csc_matrix((P["val"], P["idx"], P["beg"]), shape=(P["m"], P["n"]))
-        _forms[key] = Form(P["n"], P["m"], P["n_eqs"], A, P["cost"], P["row_lower"], P["lower"], P["upper"], P["col_scale"],
-                           P["row_scale"], P["norm_cost"], P["norm_rhs"])
+        _forms[key] = formulated_lp(case_lp(size, values), values)
     return _forms[key]
 
 
