@@ -139,6 +139,10 @@ class PdlpVariant(C.Structure):
     ]
 
 
+# The keys of one variant of DeviceBatch.run / run_tensors: PdlpVariant's arrays, PdlpUpdate's, and the variant's own limit
+VARIANT_KEYS = ("a_value", "q_value", "col_cost", "col_lower", "col_upper", "row_lower", "row_upper", "offset", "start", "iter_limit")
+
+
 # pdlp_session_info_t.path / .changed (include/pdlp_mi355x.h)
 SESSION_NONE, SESSION_CREATE, SESSION_UPDATE, SESSION_UPDATE_MATRIX, SESSION_UPDATE_VALUES, SESSION_ONE_SHOT = range(6)
 SESSION_PATH_NAME = {0: "none", 1: "create", 2: "update", 3: "update matrix", 4: "update values", 5: "one-shot"}

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "pdlp_batch.hpp"
+#include "pdlp_batch_resident.hpp"
 #include "pdlp_halpern.hpp"
 #include "pdlp_mps.hpp"
 #include "pdlp_pool.hpp"
@@ -830,6 +831,58 @@ int pdlp_mi355x_host_batch_variants_refusal(const pdlp_problem_t* P, const pdlp_
       const std::string why = pdlp::batchVariantRefusal(*P, *opt, v[k]);
       if (!why.empty()) throw std::runtime_error("variant " + std::to_string(k) + ": " + why);
     }
+  });
+}
+
+// Variants and solutions as arrays already in HBM on the batch's device (pdlp_batch_resident.hpp).  The refusals that need
+// no device come first, the arguments' before the handle's.
+int pdlp_mi355x_batch_run_device(pdlp_mi355x_batch_t* B, int32_t K, const pdlp_variant_t* v_dev, pdlp_result_t* R_dev, void* stream) {
+  return guarded([&] {
+    pdlp::refuseBatchArguments(pdlp::kEntryBatchRunDevice, K, v_dev, R_dev);
+    if (!B || !B->impl) throw std::runtime_error("pdlp_mi355x_batch_run_device: null batch");
+    B->impl->runDevice(K, v_dev, R_dev, (hipStream_t)stream);
+  });
+}
+
+// Test hook, not part of the public header: refusal step 1 of pdlp_mi355x_batch_run_device, for a batch created on P with
+// opt — from the pointers' being NULL or not alone; no array of a variant is read, no device call is made.
+int pdlp_mi355x_host_batch_device_variants_refusal(const pdlp_problem_t* P, const pdlp_params_t* opt, int32_t K,
+                                                   const pdlp_variant_t* v, const pdlp_result_t* R) {
+  return guarded([&] {
+    if (!P || !opt) throw std::runtime_error("null argument");
+    pdlp::refuseBatchArguments(pdlp::kEntryBatchRunDevice, K, v, R);
+    for (int32_t k = 0; k < K; ++k) {
+      const std::string why = pdlp::batchVariantDeviceRefusal(*P, *opt, v[k]);
+      if (!why.empty()) throw std::runtime_error("variant " + std::to_string(k) + ": " + why);
+    }
+  });
+}
+
+// Test hook, not part of the public header: refusal step 3's verdict on canned records (three int32 per variant:
+// firstBadRow, anyNonzero, firstNegDiag) — what pdlp_mi355x_batch_run_device makes of the validation launch's output.  The
+// arrays of v are HOST arrays here: they are asked whether they are NULL, and the named row's two bounds are read.
+int pdlp_mi355x_host_batch_records_verdict(int32_t K, const pdlp_variant_t* v, const int32_t* records, const int32_t* row_kind,
+                                           int32_t m, int32_t n) {
+  return guarded([&] {
+    if (K < 1 || !v || !records || (m > 0 && !row_kind)) throw std::runtime_error("null argument");
+    static_assert(sizeof(pdlp::VariantRecord) == 3 * sizeof(int32_t), "three int32 per record");
+    pdlp::refuseByRecords(K, v, reinterpret_cast<const pdlp::VariantRecord*>(records), row_kind, m, n,
+                          [&](int32_t k, int32_t row, double* lo, double* up) {
+                            *lo = v[k].u.row_lower[row];
+                            *up = v[k].u.row_upper[row];
+                          });
+  });
+}
+
+// Test hook, not part of the public header and NOT ABI — unsupported, it may change or go without an ABI version step: the
+// validation launch alone.  Unlike the host-only hooks above it works on a live batch and on the device: it runs step 1 and
+// the pointer check on v_dev first (so no host pointer reaches the kernel), then initialises n_rec >= K records, launches
+// the K jobs and writes all n_rec records, three int32 each, to out — out must hold 3 * n_rec int32; K < 1, a null
+// argument and n_rec < K are refused.  Nothing of a lane is written.
+int pdlp_mi355x_batch_variant_records(pdlp_mi355x_batch_t* B, int32_t K, const pdlp_variant_t* v_dev, int32_t n_rec, int32_t* out) {
+  return guarded([&] {
+    if (!B || !B->impl) throw std::runtime_error("pdlp_mi355x_batch_variant_records: null batch");
+    B->impl->variantRecords(K, v_dev, n_rec, out);
   });
 }
 

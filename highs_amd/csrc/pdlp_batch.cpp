@@ -30,26 +30,36 @@ BaseData::BaseData(const pdlp_problem_t& P)
   if (slots > 0) qValue.assign(P.q_value, P.q_value + slots);
 }
 
-LaneUpdatePlan planLaneUpdate(const Variant& v, int differs, const BaseData& base) {
+BaseView BaseData::view() const {
+  BaseView b;
+  b.cost = cost.data(); b.colLower = colLower.data(); b.colUpper = colUpper.data();
+  b.rowLower = rowLower.data(); b.rowUpper = rowUpper.data();
+  b.aValue = aValue.data(); b.qValue = qValue.data();
+  b.nnz = (int64_t)aValue.size(); b.qSlots = (int64_t)qValue.size();
+  b.offset = offset;
+  return b;
+}
+
+LaneUpdatePlan planLaneUpdate(const Variant& v, int differs, const BaseView& base) {
   LaneUpdatePlan plan;
   plan.v = v;
   pdlp_update_t& u = plan.v.u;
   int now = 0;
-  auto take = [&](const double*& field, const std::vector<double>& kept, int bit) {
+  auto take = [&](const double*& field, const double* kept, int bit) {
     if (field) now |= bit;
-    else if (differs & bit) field = kept.data();
+    else if (differs & bit) field = kept;
   };
   take(u.col_cost, base.cost, kLaneCost);
   take(u.col_lower, base.colLower, kLaneColLower);
   take(u.col_upper, base.colUpper, kLaneColUpper);
   if (u.row_lower) now |= kLaneRows;  // (given together: validated)
-  else if (differs & kLaneRows) { u.row_lower = base.rowLower.data(); u.row_upper = base.rowUpper.data(); }
+  else if (differs & kLaneRows) { u.row_lower = base.rowLower; u.row_upper = base.rowUpper; }
   if (u.has_offset) now |= kLaneOffset;
   else if (differs & kLaneOffset) { u.has_offset = 1; u.offset = base.offset; }
   take(plan.v.a_value, base.aValue, kLaneMatrix);
-  if (!(now & kLaneMatrix) && plan.v.a_value) plan.v.num_nz = (int64_t)base.aValue.size();
+  if (!(now & kLaneMatrix) && plan.v.a_value) plan.v.num_nz = base.nnz;
   take(plan.v.q_value, base.qValue, kLaneHessian);
-  if (!(now & kLaneHessian) && plan.v.q_value) plan.v.num_q_nz = (int64_t)base.qValue.size();
+  if (!(now & kLaneHessian) && plan.v.q_value) plan.v.num_q_nz = base.qSlots;
   plan.now = now;
   plan.call = plan.v.q_value ? kCallUpdateValues : plan.v.a_value ? kCallUpdateMatrix : kCallUpdate;
   return plan;
@@ -60,14 +70,19 @@ void refuseBatchArguments(const char* entry, int32_t K, const void* variants, co
   if (!variants || !results) throw std::runtime_error(std::string(entry) + ": null argument");
 }
 
-void BatchDriver::run(int32_t K, const Variant* u, pdlp_result_t* R, const char* entry) {
+void BatchDriver::run(int32_t K, const Variant* u, pdlp_result_t* R, const char* entry, LaneMode mode) {
   refuseBatchArguments(entry, K, u, R);
+  for (BatchLane* l : lanes_) l->setMode(mode);  // (per call: a refusal below leaves nothing behind)
   // all-or-nothing: every variant is validated before the first one changes a lane
-  for (int32_t k = 0; k < K; ++k) {
-    try {
-      lanes_[0]->validate(u[k]);
-    } catch (const std::exception& e) {
-      throw std::runtime_error("variant " + std::to_string(k) + ": " + e.what());
+  if (mode == kLaneDevice) {
+    lanes_[0]->validateDevice(K, u, R);  // (the arrays cannot be read here: one pass over all of them, on the device)
+  } else {
+    for (int32_t k = 0; k < K; ++k) {
+      try {
+        lanes_[0]->validate(u[k]);
+      } catch (const std::exception& e) {
+        throw std::runtime_error("variant " + std::to_string(k) + ": " + e.what());
+      }
     }
   }
   const auto t0 = std::chrono::steady_clock::now();

@@ -43,13 +43,28 @@ using Variant = pdlp_variant_t;
 inline bool hasValues(const Variant& v) { return v.a_value || v.q_value || v.num_nz != 0 || v.num_q_nz != 0; }
 constexpr const char* kEntryBatchRun = "pdlp_mi355x_batch_run";
 constexpr const char* kEntryBatchRunValues = "pdlp_mi355x_batch_run_values";
+constexpr const char* kEntryBatchRunDevice = "pdlp_mi355x_batch_run_device";
 
-// What of P an update can change, kept on the host: variant k is P with v[k] applied, whatever variant the lane solved
-// before — so what an earlier variant changed on a lane and this one leaves alone goes back to P's values.
+// Where the arrays of ONE call live: in host memory (batch_run, batch_run_values) or in HBM on the batch's device
+// (batch_run_device, pdlp_batch_resident.hpp).  A call never mixes the two: what a lane restores comes from the copy of P
+// that lives where the variants do.
+enum LaneMode : int { kLaneHost = 0, kLaneDevice = 1 };
+
+// What of P an update can change, as pointers and counts: a BaseData's vectors, or their copy in HBM (the plan hands the
+// pointers on and never reads through them).
+struct BaseView {
+  const double *cost = nullptr, *colLower = nullptr, *colUpper = nullptr, *rowLower = nullptr, *rowUpper = nullptr;
+  const double *aValue = nullptr, *qValue = nullptr;
+  int64_t nnz = 0, qSlots = 0;
+  double offset = 0.0;
+};
+// ... kept on the host: variant k is P with v[k] applied, whatever variant the lane solved before — so what an earlier
+// variant changed on a lane and this one leaves alone goes back to P's values.
 struct BaseData {
   std::vector<double> cost, colLower, colUpper, rowLower, rowUpper, aValue, qValue;
   double offset = 0.0;
   explicit BaseData(const pdlp_problem_t& P);
+  BaseView view() const;
 };
 
 // The ONE update call that takes a lane's solver, which differs from P in the arrays `differs` names, to variant v: what v
@@ -62,7 +77,7 @@ struct LaneUpdatePlan {
   LaneCall call = kCallUpdate;  // no value array: the plain update; a_value alone: update_matrix (which is update_values on a
                                 // Hessian-updatable solver); else update_values
 };
-LaneUpdatePlan planLaneUpdate(const Variant& v, int differs, const BaseData& base);
+LaneUpdatePlan planLaneUpdate(const Variant& v, int differs, const BaseView& base);
 
 // What the driver asks of a resident solver (SolverLane: Solver's lane steps, pdlp_solver.hpp).
 class BatchLane {
@@ -70,7 +85,13 @@ class BatchLane {
   virtual ~BatchLane() = default;
   virtual std::string sequentialReason() = 0;  // empty: the launches can be shared
   virtual int32_t workBlocks() = 0;
+  // kLaneDevice: what follows in this call — update, finish, runAlone — takes the variants' arrays and writes the results'
+  // vectors in HBM, and restores from P's copy there.  Set on every lane at the start of every call.
+  virtual void setMode(LaneMode mode) = 0;
   virtual void validate(const Variant& v) = 0;  // throws with the words of the update entry v maps to; changes nothing
+  // kLaneDevice, asked of lane 0 once per call: all K variants and results at once, in the order of pdlp_batch_resident.hpp
+  // (value-free refusals, the pointer check, one validation launch); throws "variant k: ..." / "result k: ..."; changes nothing
+  virtual void validateDevice(int32_t K, const Variant* v, const pdlp_result_t* R) = 0;
   virtual void setVariant(int32_t k, int32_t iterLimit) = 0;  // log prefix and iteration limit (0: the batch's) of what follows
   virtual void update(const Variant& v) = 0;
   virtual void runAlone(pdlp_result_t* R) = 0;  // the ordinary run, with its own fall-backs
@@ -93,7 +114,8 @@ class BatchBackend {
 class BatchDriver {
  public:
   BatchDriver(std::vector<BatchLane*> lanes, BatchBackend* backend);
-  void run(int32_t K, const Variant* v, pdlp_result_t* R, const char* entry = kEntryBatchRun);  // entry: named in the refusals
+  // entry: named in the refusals; mode: where the arrays of v and R live
+  void run(int32_t K, const Variant* v, pdlp_result_t* R, const char* entry = kEntryBatchRun, LaneMode mode = kLaneHost);
   const pdlp_batch_info_t& info() const { return info_; }
 
  private:
@@ -111,6 +133,9 @@ void refuseBatchArguments(const char* entry, int32_t K, const void* variants, co
 // Refusals of one variant of pdlp_mi355x_batch_run_values that look at no matrix or Hessian VALUE, for a batch created on P
 // with opt (the batch's own DATA bit is added here): empty, or the words of the update entry the variant maps to.
 std::string batchVariantRefusal(const pdlp_problem_t& P, const pdlp_params_t& opt, const Variant& v);
+// ... of pdlp_mi355x_batch_run_device: the same, from the pointers' being NULL or not alone (no array is read: the row
+// kinds are compared on the device)
+std::string batchVariantDeviceRefusal(const pdlp_problem_t& P, const pdlp_params_t& opt, const Variant& v);
 
 // The batch behind the C ABI: the solvers, their lanes, the device backend and the driver.
 class Batch {
@@ -119,6 +144,11 @@ class Batch {
   ~Batch();
   void run(int32_t K, const pdlp_update_t* u, pdlp_result_t* R);
   void runValues(int32_t K, const Variant* v, pdlp_result_t* R);
+  // pdlp_mi355x_batch_run_device: every array of v[k] and every vector of R[k] in HBM on the batch's device
+  void runDevice(int32_t K, const Variant* vDev, pdlp_result_t* RDev, hipStream_t callerStream);
+  // Test hook: the validation launch alone on vDev (after the pointer check), with nRec >= K records initialised; all nRec
+  // records, three int32 each, into out
+  void variantRecords(int32_t K, const Variant* vDev, int32_t nRec, int32_t* out);
   const pdlp_batch_info_t& info() const { return driver_->info(); }
 
  private:

@@ -5,7 +5,9 @@
 #include <cstring>
 
 #include "pdlp_batch.hpp"
+#include "pdlp_batch_resident.hpp"
 #include "pdlp_pool.hpp"
+#include "pdlp_resident.hpp"
 #include "pdlp_session.hpp"
 #include "pdlp_solver.hpp"
 #include "pdlp_update.hpp"
@@ -127,19 +129,161 @@ int32_t Solver::laneXcc() {
   return id == 0 ? -1 : (int32_t)id - 1;
 }
 
-void Solver::laneFinish(pdlp_result_t* R) {
+void Solver::laneFinish(pdlp_result_t* R, bool resultOnDevice) {
   if (!loop_.noLoop) endDeviceLoop();
-  finishRun(R);
+  finishRun(R, resultOnDevice);
+}
+
+Solver::VariantCheckFacts Solver::laneVariantCheckFacts() const {
+  VariantCheckFacts f;
+  if (rowKindDev_.size() == (size_t)F_.m) f.rowKindDev = rowKindDev_.get();
+  f.rowKindHost = F_.rowKind.data();
+  if (hessianUpdatable_ && hk_.dstBeg.size() > (size_t)F_.n && hk_.nSlots > 0) {
+    f.dstBeg = hk_.dstBeg.get();
+    f.srcSlot = hk_.srcSlot.get();
+  }
+  f.sense = F_.sense;
+  f.m = F_.m;
+  f.n = F_.n;
+  f.nnz = nnzIn_;
+  return f;
 }
 
 namespace {
 
+// What a batch keeps for its device runs (pdlp_mi355x_batch_run_device): P's updatable data in HBM — uploaded by the first
+// device run, kept with the batch; what a lane restores in a device call comes from here —, the table and the records of
+// the validation launch, and the stream of the call in progress.
+struct BatchResident {
+  int32_t device = 0;
+  const BaseData* base = nullptr;
+  std::vector<Solver*> solvers;
+  hipStream_t callerStream = nullptr;  // of the call in progress
+  DeviceArray<double> baseDev;         // cost, colLower, colUpper, rowLower, rowUpper, aValue, qValue, back to back
+  BaseView view;                       // ... as the plan takes it
+  bool uploaded = false;
+  DeviceArray<VariantJob> jobs;
+  DeviceArray<VariantRecord> rec;
+
+  // P's data into HBM, once (on lane 0's stream; synchronises)
+  void ensureBase() {
+    if (uploaded) return;
+    const BaseData& b = *base;
+    const std::vector<double>* part[7] = {&b.cost, &b.colLower, &b.colUpper, &b.rowLower, &b.rowUpper, &b.aValue, &b.qValue};
+    size_t total = 0;
+    for (const auto* p : part) total += p->size();
+    baseDev.alloc(total);
+    const double* at[7];
+    size_t off = 0;
+    hipStream_t s = solvers[0]->laneStream();
+    for (int i = 0; i < 7; ++i) {
+      at[i] = baseDev.get() + off;
+      if (!part[i]->empty())
+        PDLP_HIP(hipMemcpyAsync(baseDev.get() + off, part[i]->data(), sizeof(double) * part[i]->size(), hipMemcpyHostToDevice, s));
+      off += part[i]->size();
+    }
+    PDLP_HIP(hipStreamSynchronize(s));
+    view = b.view();
+    view.cost = at[0]; view.colLower = at[1]; view.colUpper = at[2]; view.rowLower = at[3]; view.rowUpper = at[4];
+    view.aValue = at[5]; view.qValue = at[6];
+    uploaded = true;
+  }
+
+  // Refusal step 1 of pdlp_mi355x_batch_run_device: what the entry a variant maps to refuses without looking at a value,
+  // from host facts.  No HIP call.
+  void refuseValueFree(int32_t K, const Variant* v) const {
+    const ValueUpdateFacts f = solvers[0]->valueUpdateFacts();
+    for (int32_t k = 0; k < K; ++k) {
+      try {
+        residentUpdateRefusal(f, v[k].a_value, v[k].num_nz, v[k].q_value, v[k].num_q_nz, v[k].u);
+        // updateDevice's own last value-free refusal.  A lane is never sharded and keeps its matrix exactly where the line
+        // above lets an a_value pass (the MATRIX bit, and no off-diagonal Hessian without the HESSIAN bit), so this does
+        // not fire; it stands here so that nothing an update refuses without looking at a value is left for mid-run.
+        if (v[k].a_value && !solvers[0]->laneKeepsMatrix())
+          throw std::runtime_error("pdlp_mi355x_update_matrix: the solver kept nothing for matrix updates");
+      } catch (const std::exception& e) {
+        throw std::runtime_error("variant " + std::to_string(k) + ": " + e.what());
+      }
+    }
+  }
+  // Step 2, THE POINTER CHECK (pdlp_resident.hpp): every array of every variant, then every vector of every result.
+  // Launches nothing, copies nothing.
+  void requirePointers(int32_t K, const Variant* v, const pdlp_result_t* R) const {
+    auto named = [&](const char* what, int32_t k, auto&& check) {
+      try {
+        check();
+      } catch (const std::exception& e) {
+        throw std::runtime_error(std::string(what) + " " + std::to_string(k) + ": " + e.what());
+      }
+    };
+    for (int32_t k = 0; k < K; ++k) named("variant", k, [&] { requireDeviceUpdate(v[k].a_value, v[k].q_value, &v[k].u, device); });
+    if (R)
+      for (int32_t k = 0; k < K; ++k) named("result", k, [&] { requireDeviceResult(R[k], device); });
+  }
+  // Every lane's stream behind ONE event recorded on the caller's stream, which is never synchronised
+  void orderLanes() const {
+    hipEvent_t ev = nullptr;
+    PDLP_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    hipError_t e = hipEventRecord(ev, callerStream);
+    for (size_t l = 0; l < solvers.size() && e == hipSuccess; ++l) e = hipStreamWaitEvent(solvers[l]->laneStream(), ev, 0);
+    (void)hipEventDestroy(ev);  // (released once the waits have passed it)
+    PDLP_HIP(e);
+  }
+  // Step 3's launch on lane 0's stream: nRec >= K records initialised to {m, 0, n}, the K jobs' in ONE launch, all nRec
+  // records back in one copy; synchronises.
+  std::vector<VariantRecord> records(int32_t K, const Variant* v, int32_t nRec) {
+    const Solver::VariantCheckFacts f = solvers[0]->laneVariantCheckFacts();
+    hipStream_t s = solvers[0]->laneStream();
+    std::vector<VariantJob> table((size_t)K);
+    bool rows = false;
+    for (int32_t k = 0; k < K; ++k) {
+      table[(size_t)k] = VariantJob{v[k].u.row_lower, v[k].u.row_upper, v[k].a_value, v[k].q_value};
+      rows = rows || v[k].u.row_lower;
+    }
+    if (rows && f.m > 0 && !f.rowKindDev) throw std::runtime_error("pdlp_mi355x_batch_run_device: the lanes did not keep their row kinds");
+    std::vector<VariantRecord> rec0((size_t)nRec, VariantRecord{f.m, 0, f.n});
+    if (jobs.size() < (size_t)K) jobs.alloc((size_t)K);
+    if (rec.size() < (size_t)nRec) rec.alloc((size_t)nRec);
+    jobs.upload(table.data(), (size_t)K, s);
+    rec.upload(rec0.data(), (size_t)nRec, s);
+    VariantsValidateArgs a{};
+    a.jobs = jobs.get(); a.K = K;
+    a.rowKind = f.rowKindDev; a.dstBeg = f.dstBeg; a.srcSlot = f.srcSlot;
+    a.sense = f.sense; a.m = f.m; a.n = f.n; a.nnz = f.nnz;
+    a.rec = rec.get();
+    launchVariantsValidate(a, s);
+    rec.download(rec0.data(), (size_t)nRec, s);
+    PDLP_HIP(hipStreamSynchronize(s));
+    return rec0;
+  }
+  // The three steps, in their fixed order; all-or-nothing: nothing of a lane is written
+  void validate(int32_t K, const Variant* v, const pdlp_result_t* R) {
+    refuseValueFree(K, v);
+    requirePointers(K, v, R);
+    // ---- from here on every pointer is known to be HBM of this device ----
+    PDLP_HIP(hipSetDevice(device));
+    ensureBase();
+    orderLanes();
+    const std::vector<VariantRecord> rec0 = records(K, v, K);
+    const Solver::VariantCheckFacts f = solvers[0]->laneVariantCheckFacts();
+    hipStream_t s = solvers[0]->laneStream();
+    refuseByRecords(K, v, rec0.data(), f.rowKindHost, f.m, f.n, [&](int32_t k, int32_t row, double* lo, double* up) {
+      PDLP_HIP(hipMemcpyAsync(lo, v[k].u.row_lower + row, sizeof(double), hipMemcpyDeviceToHost, s));  // that row's two bounds only
+      PDLP_HIP(hipMemcpyAsync(up, v[k].u.row_upper + row, sizeof(double), hipMemcpyDeviceToHost, s));
+      PDLP_HIP(hipStreamSynchronize(s));
+    });
+  }
+};
+
 class SolverLane : public BatchLane {
  public:
-  SolverLane(Solver* s, const pdlp_params_t& opt, const BaseData* base) : s_(s), opt_(opt), base_(base) {
+  SolverLane(Solver* s, const pdlp_params_t& opt, const BaseData* base, BatchResident* resident)
+      : s_(s), opt_(opt), hostView_(base->view()), resident_(resident) {
     tap_.sink = opt.log_callback;
     tap_.sinkCtx = opt.log_ctx;
   }
+  void setMode(LaneMode mode) override { mode_ = mode; }
+  void validateDevice(int32_t K, const Variant* v, const pdlp_result_t* R) override { resident_->validate(K, v, R); }
   std::string sequentialReason() override { return s_->laneSequentialReason(); }
   int32_t workBlocks() override { return s_->laneWorkBlocks(); }
   void validate(const Variant& v) override {
@@ -158,27 +302,35 @@ class SolverLane : public BatchLane {
     s_->setRuntimeOptions(o);
   }
   void update(const Variant& v) override {
-    const LaneUpdatePlan plan = planLaneUpdate(v, differs_, *base_);
+    const bool dev = mode_ == kLaneDevice;  // (the batch's copy of P in HBM is there: validateDevice has run)
+    const LaneUpdatePlan plan = planLaneUpdate(v, differs_, dev ? resident_->view : hostView_);
     const Variant& w = plan.v;
     differs_ |= plan.now;  // (also when the update throws half-way: a needless restore costs time only)
-    if (plan.call == kCallUpdate) s_->update(w.u);
+    // (device: ONE entry routes the three updates as the plan does; the lane's stream is ordered behind the caller's already)
+    if (dev) s_->updateDeviceBehind(w.a_value, w.num_nz, w.q_value, w.num_q_nz, &w.u, resident_->callerStream, false);
+    else if (plan.call == kCallUpdate) s_->update(w.u);
     else if (plan.call == kCallUpdateMatrix) s_->updateMatrix(w.a_value, w.num_nz, &w.u);
     else s_->updateValues(w.a_value, w.num_nz, w.q_value, w.num_q_nz, &w.u);
     differs_ = plan.now;
   }
-  void runAlone(pdlp_result_t* R) override { s_->run(R); }
+  void runAlone(pdlp_result_t* R) override {
+    if (mode_ == kLaneDevice) s_->runDevice(R);
+    else s_->run(R);
+  }
   void begin() override { s_->laneBegin(); }
   bool idle() override { return s_->laneIdle(); }
   void queue(int32_t ahead, std::vector<LaneUnit>& units) override { s_->laneQueue(ahead, units); }
   LaneVerdict afterRound() override { return s_->laneAfterRound(); }
-  void finish(pdlp_result_t* R) override { s_->laneFinish(R); }
+  void finish(pdlp_result_t* R) override { s_->laneFinish(R, mode_ == kLaneDevice); }
   int32_t xcc() override { return s_->laneXcc(); }
 
  private:
   Solver* s_;
   pdlp_params_t opt_;
-  const BaseData* base_;
-  int differs_ = 0;  // the arrays in which the solver's problem differs from P
+  BaseView hostView_;  // P's data where a host call restores from (the batch keeps the vectors)
+  BatchResident* resident_;
+  LaneMode mode_ = kLaneHost;  // of the call in progress
+  int differs_ = 0;  // the arrays in which the solver's problem differs from P (wherever the arrays came from)
   LogTap tap_;
 };
 
@@ -232,11 +384,27 @@ std::string batchVariantRefusal(const pdlp_problem_t& P, const pdlp_params_t& op
   return std::string();
 }
 
+std::string batchVariantDeviceRefusal(const pdlp_problem_t& P, const pdlp_params_t& opt, const Variant& v) {
+  try {
+    const SessionShape shape = sessionShapeOf(P);
+    ValueUpdateFacts f;  // (as above; no kinds: residentUpdateRefusal leaves them to the device)
+    f.updatable = opt.updatable | PDLP_UPDATABLE_DATA;
+    f.nnz = shape.nnz;
+    f.qSlots = (opt.updatable & PDLP_UPDATABLE_HESSIAN) ? shape.qSlots : 0;
+    f.hasQoff = (opt.updatable & PDLP_UPDATABLE_HESSIAN) ? hessianHasOffDiagonalSlot(P) : hessianHasOffDiagonal(P);
+    residentUpdateRefusal(f, v.a_value, v.num_nz, v.q_value, v.num_q_nz, v.u);
+  } catch (const std::exception& e) {
+    return e.what();
+  }
+  return std::string();
+}
+
 struct Batch::Impl {
   std::vector<std::unique_ptr<Solver>> solvers;
   std::vector<std::unique_ptr<SolverLane>> lanes;
   std::unique_ptr<DeviceBackend> backend;
   std::unique_ptr<BaseData> base;
+  BatchResident resident;
   int32_t device = 0;
 };
 
@@ -248,14 +416,17 @@ Batch::Batch(const pdlp_problem_t& P, const pdlp_params_t& opt, int32_t lanes) :
   impl_->device = o.device;
   validateProblem(P);
   impl_->base.reset(new BaseData(P));
+  impl_->resident.device = o.device;
+  impl_->resident.base = impl_->base.get();
   std::vector<BatchLane*> ls;
   std::vector<Solver*> ss;
   for (int32_t l = 0; l < lanes; ++l) {
     impl_->solvers.emplace_back(new Solver(P, o, 0, 1, nullptr));
-    impl_->lanes.emplace_back(new SolverLane(impl_->solvers.back().get(), o, impl_->base.get()));
+    impl_->lanes.emplace_back(new SolverLane(impl_->solvers.back().get(), o, impl_->base.get(), &impl_->resident));
     ls.push_back(impl_->lanes.back().get());
     ss.push_back(impl_->solvers.back().get());
   }
+  impl_->resident.solvers = ss;
   impl_->backend.reset(new DeviceBackend(ss, o.device));
   driver_.reset(new BatchDriver(ls, impl_->backend.get()));
 }
@@ -278,6 +449,26 @@ void Batch::run(int32_t K, const pdlp_update_t* u, pdlp_result_t* R) {
 void Batch::runValues(int32_t K, const Variant* v, pdlp_result_t* R) {
   PDLP_HIP(hipSetDevice(impl_->device));
   driver_->run(K, v, R, kEntryBatchRunValues);
+}
+
+void Batch::runDevice(int32_t K, const Variant* vDev, pdlp_result_t* RDev, hipStream_t callerStream) {
+  // (no HIP call here: the refusals that need none come first, inside the driver's validation — BatchResident::validate)
+  impl_->resident.callerStream = callerStream;
+  driver_->run(K, vDev, RDev, kEntryBatchRunDevice, kLaneDevice);
+}
+
+void Batch::variantRecords(int32_t K, const Variant* vDev, int32_t nRec, int32_t* out) {
+  refuseBatchArguments("pdlp_mi355x_batch_variant_records", K, vDev, out);
+  if (nRec < K) throw std::runtime_error("pdlp_mi355x_batch_variant_records: fewer records than variants");
+  BatchResident& r = impl_->resident;
+  r.refuseValueFree(K, vDev);
+  r.requirePointers(K, vDev, nullptr);
+  PDLP_HIP(hipSetDevice(impl_->device));
+  r.callerStream = nullptr;
+  r.orderLanes();
+  const std::vector<VariantRecord> rec = r.records(K, vDev, nRec);
+  static_assert(sizeof(VariantRecord) == 3 * sizeof(int32_t), "three int32 per record");
+  memcpy(out, rec.data(), sizeof(VariantRecord) * (size_t)nRec);
 }
 
 }  // namespace pdlp

@@ -170,6 +170,11 @@ void SolverBase::updateDevice(const double*, int64_t, const double*, int64_t, co
 // message, a hot start), and the caller's pointers for those it only asks about (never read: staged_).
 void Solver::updateDevice(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t* u,
                           hipStream_t callerStream) {
+  updateDeviceBehind(aValue, numNz, qValue, numQNz, u, callerStream, true);
+}
+
+void Solver::updateDeviceBehind(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t* u,
+                                hipStream_t callerStream, bool order) {
   const auto t0 = std::chrono::steady_clock::now();
   static const pdlp_update_t kNoData{};
   const pdlp_update_t& ud = u ? *u : kNoData;
@@ -185,7 +190,7 @@ void Solver::updateDevice(const double* aValue, int64_t numNz, const double* qVa
   const int32_t mask = updateMask(ud);
   PDLP_HIP(hipSetDevice(opt_.device));
   PDLP_HIP(hipStreamSynchronize(stream_));
-  orderBehind(stream_, callerStream);
+  if (order) orderBehind(stream_, callerStream);
   std::vector<double> hCost, hRowLower, hRowUpper, hStartCol, hStartRow, hStartDual;
   auto pull = [&](std::vector<double>& host, const double* dev, size_t count) {
     host.resize(count);

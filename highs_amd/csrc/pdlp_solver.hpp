@@ -168,6 +168,10 @@ class Solver : public SolverBase {
   void runDevice(pdlp_result_t* R) override;  // pdlp_resident.cpp
   void updateDevice(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t* u,
                     hipStream_t callerStream) override;  // pdlp_resident.cpp
+  // updateDevice for a caller that has ordered this solver's stream behind the stream the arrays were filled on already
+  // (a batch: ONE event for all its lanes, pdlp_batch_resident.hpp): orderBehind false records and waits for nothing
+  void updateDeviceBehind(const double* aValue, int64_t numNz, const double* qValue, int64_t numQNz, const pdlp_update_t* u,
+                          hipStream_t callerStream, bool orderBehind);
 
   // ---- what a session drives (pdlp_session.hpp; all in pdlp_session.cpp) ----
   // The caller's a_value, costs, bounds and (QPs) Hessian arrays into HBM copies of their own, for later comparisons.
@@ -209,7 +213,17 @@ class Solver : public SolverBase {
   LaneVerdict laneAfterRound();           // (the shared stream has been synchronised)
   int32_t laneCommError() const { return loop_.commError; }
   int32_t laneXcc();                      // the XCC id this solver's workers published at their last placement check, or -1
-  void laneFinish(pdlp_result_t* R);
+  void laneFinish(pdlp_result_t* R, bool resultOnDevice = false);  // resultOnDevice: R's vectors are in HBM (run_device's post-solve)
+  // What the validation launch of a device batch reads of this solver (pdlp_batch_resident.hpp): the kept kinds in HBM and
+  // on the host, the Hessian assembly map (NULL: none kept), the sense and the sizes
+  struct VariantCheckFacts {
+    const int32_t *rowKindDev = nullptr, *rowKindHost = nullptr, *dstBeg = nullptr, *srcSlot = nullptr;
+    double sense = 1.0;
+    int32_t m = 0, n = 0;
+    int64_t nnz = 0;
+  };
+  VariantCheckFacts laneVariantCheckFacts() const;
+  bool laneKeepsMatrix() const { return matrixUpdatable_; }  // what updateDevice asks before it takes an a_value
   hipStream_t laneStream() const { return stream_; }
   // the device gate for a round of shared launches (BarrierRound of doSolveDevice) on a stream the caller names: a batch's
   // lane 0's, or one that is no solver's own (a pool's: its solvers come and go, pdlp_pool.hpp)

@@ -56,8 +56,12 @@ void refuseKindChange(const int32_t* rowKind, int32_t m, const double* rowLower,
 }
 
 void refuseKindChangeAt(const int32_t* rowKind, int32_t row, const double* rowLower, const double* rowUpper) {
-  throw std::runtime_error("pdlp_mi355x_update: row " + std::to_string(row) + " would change its kind from " + kindName(rowKind[row]) +
-                           " to " + kindName(rowKindOf(rowLower[row], rowUpper[row])) +
+  refuseKindChangeAt(rowKind[row], row, rowLower[row], rowUpper[row]);
+}
+
+void refuseKindChangeAt(int32_t kindWas, int32_t row, double lower, double upper) {
+  throw std::runtime_error("pdlp_mi355x_update: row " + std::to_string(row) + " would change its kind from " + kindName(kindWas) +
+                           " to " + kindName(rowKindOf(lower, upper)) +
                            " (the kind decides row order, slack columns and signs: create a new solver)");
 }
 

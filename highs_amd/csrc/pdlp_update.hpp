@@ -30,6 +30,8 @@ void checkUpdateShape(const pdlp_update_t& u);
 // second form is for a row the device's validation kernel has found already.
 void refuseKindChange(const int32_t* rowKind, int32_t m, const double* rowLower, const double* rowUpper);
 [[noreturn]] void refuseKindChangeAt(const int32_t* rowKind, int32_t row, const double* rowLower, const double* rowUpper);
+// ... from that row's kept kind and its two new bounds alone (the arrays are in HBM: pdlp_batch_resident.hpp)
+[[noreturn]] void refuseKindChangeAt(int32_t kindWas, int32_t row, double lower, double upper);
 
 // The refusals that depend on how the solver was created, each sentence in ONE place; `entry` is the C entry that refuses.
 constexpr const char* kEntryUpdate = "pdlp_mi355x_update";

@@ -52,6 +52,7 @@ EXPORTS = [
     "pdlp_mi355x_batch_info_size", "pdlp_mi355x_batch_run_values", "pdlp_mi355x_variant_size",
     "pdlp_mi355x_solve_many", "pdlp_mi355x_pool_info_size",
     "pdlp_mi355x_create_device", "pdlp_mi355x_update_device", "pdlp_mi355x_run_device",
+    "pdlp_mi355x_batch_run_device",
 ]
 
 
@@ -147,6 +148,14 @@ def lib():
                 if L.pdlp_mi355x_variant_size() != C.sizeof(abi.PdlpVariant):
                     raise RuntimeError("pdlp_variant_t: the library's size %d differs from abi.PdlpVariant's %d" %
                                        (L.pdlp_mi355x_variant_size(), C.sizeof(abi.PdlpVariant)))
+            # (a build from before the device batches has none of these: tools/batch_resident_bench.py's parent side)
+            if hasattr(L, "pdlp_mi355x_batch_run_device"):
+                L.pdlp_mi355x_batch_run_device.argtypes = [H, C.c_int32, pV, pR, C.c_void_p]
+                # (test hooks outside the public header: batch_run_device's refusals that need no device, its verdict on
+                # canned records of the validation launch, and that launch alone)
+                L.pdlp_mi355x_host_batch_device_variants_refusal.argtypes = [pP, pO, C.c_int32, pV, pR]
+                L.pdlp_mi355x_host_batch_records_verdict.argtypes = [C.c_int32, pV, abi.c_i32p, abi.c_i32p, C.c_int32, C.c_int32]
+                L.pdlp_mi355x_batch_variant_records.argtypes = [H, C.c_int32, pV, C.c_int32, abi.c_i32p]
             L.pdlp_mi355x_batch_info.argtypes = [H, pB]
             L.pdlp_mi355x_batch_destroy.argtypes = [H]
             L.pdlp_mi355x_batch_destroy.restype = None
@@ -807,6 +816,82 @@ class DeviceBatch:
             status = kOk if ms == kOptimal or ms == kUnboundedOrInfeasible else kWarning
             out.append(PdlpOutcome(status, ms, sol, int(R.num_iter), info, R))
         return out
+
+    # ---- variants and solutions as tensors in HBM (tensors.py; include/pdlp_mi355x.h pdlp_mi355x_batch_run_device) ----
+    def _tensor_variants(self, variants):
+        """-> (the pdlp_variant_t array, what keeps its tensors alive); TypeError / ValueError name the variant."""
+        import torch
+
+        from . import tensors as T
+
+        dev = torch.device("cuda", self.params.device)
+        V = (abi.PdlpVariant * max(len(variants), 1))()
+        keep = []
+        for k, v in enumerate(variants):
+            unknown = set(v) - set(abi.VARIANT_KEYS)
+            if unknown:
+                raise ValueError(f"variants[{k}]: unknown keys {sorted(unknown)}; a variant takes {abi.VARIANT_KEYS}")
+            try:
+                tv = T.TensorVariant(self.lp.num_col, self.lp.num_row, dev, **v)
+            except (TypeError, ValueError) as e:
+                raise type(e)(f"variants[{k}]: {e}") from None
+            keep.append(tv)
+            V[k] = tv.struct
+        return V, keep
+
+    def run_tensors(self, variants, out=None):
+        """pdlp_mi355x_batch_run_device: run() with every array of every variant a float64 tensor on the batch's device —
+        rows of a contiguous [K, n] tensor are valid entries (tensors.stacked) — and the solutions left there.  -> one
+        tensors.TensorResult per variant, bit for bit what run() gives for the same arrays as numpy.  out: None (fresh
+        tensors), a list with one dict per variant as DeviceSolver.run_tensors takes it (a vector mapped to None is not
+        asked for), or ONE dict of two-dimensional tensors, col_value / col_dual as [K, num_col], row_value / row_dual as
+        [K, num_row], row k being variant k's vector.  The variants' tensors are read behind torch's current stream,
+        without synchronising it; with `out`, that stream is synchronised first, as for DeviceSolver.run_tensors."""
+        import torch
+
+        from . import tensors as T
+
+        K = len(variants)
+        n0, m = self.lp.num_col, self.lp.num_row
+        dev = torch.device("cuda", self.params.device)
+        V, keep = self._tensor_variants(variants)
+        if out is None:
+            outs = [None] * K
+        elif isinstance(out, dict):
+            sizes = dict(col_value=n0, col_dual=n0, row_value=m, row_dual=m)
+            unknown = set(out) - set(sizes)
+            if unknown:
+                raise ValueError(f"out: unknown vectors {sorted(unknown)}; the four are {T.TensorResult.VECTORS}")
+            for name, t in out.items():
+                if not isinstance(t, torch.Tensor):
+                    raise TypeError(f"out[{name!r}]: a torch tensor is needed, got {type(t).__name__}")
+                if t.dim() != 2 or tuple(t.shape) != (K, sizes[name]):
+                    raise ValueError(f"out[{name!r}]: shape ({K}, {sizes[name]}) is needed, got {tuple(t.shape)}")
+            outs = [{name: t[k] for name, t in out.items()} for k in range(K)]
+        else:
+            outs = list(out)
+            if len(outs) != K:
+                raise ValueError(f"out: one entry per variant is needed ({K}), got {len(outs)}")
+        results = []
+        Rs = (abi.PdlpResult * max(K, 1))()
+        for k in range(K):
+            o = outs[k] or {}
+            try:
+                R = T.TensorResult(n0, m, dev, {a: t for a, t in o.items() if t is not None}, [a for a, t in o.items() if t is None])
+            except (TypeError, ValueError) as e:
+                raise type(e)(f"variant {k}: {e}") from None
+            results.append(R)
+            Rs[k] = R.struct
+        with torch.cuda.device(dev):
+            cur = torch.cuda.current_stream()
+            if out is not None:  # (what torch has queued that still reads the given tensors ends first)
+                cur.synchronize()
+            rc = lib().pdlp_mi355x_batch_run_device(self.h, K, V, Rs, C.c_void_p(cur.cuda_stream))
+        _check(rc, "pdlp_mi355x_batch_run_device")
+        del keep
+        for k in range(K):
+            results[k].struct = Rs[k]
+        return results
 
     def info(self):
         """About the last run."""

@@ -167,24 +167,73 @@ class TensorUpdate:
         self.struct = U
 
 
+class TensorVariant:
+    """A pdlp_variant_t whose arrays are tensors: one variant of DeviceBatch.run_tensors — a_value / q_value (None = the
+    values of the batch's problem), iter_limit for this variant alone, and the arguments of TensorUpdate.  Rows of a
+    contiguous [K, n] tensor are valid arrays."""
+
+    def __init__(self, num_col, num_row, device, a_value=None, q_value=None, iter_limit=None, **update):
+        self.update = TensorUpdate(num_col, num_row, device, **update)
+        V = abi.PdlpVariant()
+        self.keep = list(self.update.keep)
+        if a_value is not None:
+            check_tensor("a_value", a_value, "float64", None, device)
+            V.a_value, V.num_nz = pointer(a_value, abi.c_f64p), a_value.numel()
+            self.keep.append(a_value)
+        if q_value is not None:
+            check_tensor("q_value", q_value, "float64", None, device)
+            V.q_value, V.num_q_nz = pointer(q_value, abi.c_f64p), q_value.numel()
+            self.keep.append(q_value)
+        V.u = self.update.struct
+        if iter_limit is not None:
+            V.u.reserved = int(iter_limit)
+        self.struct = V
+
+
+def stacked(**two_d):
+    """Stacked tensors -> the list of variants DeviceBatch.run_tensors takes: stacked(col_cost=C, a_value=A) with C of
+    shape [K, num_col] and A of shape [K, num_nz] is [dict(col_cost=C[0], a_value=A[0]), ..., dict(col_cost=C[K-1], ...)].
+    Every tensor is two-dimensional with the same first dimension (ValueError otherwise); None entries are left out."""
+    import torch
+
+    K = None
+    for name, t in two_d.items():
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name}: a torch tensor is needed, got {type(t).__name__}")
+        if t.dim() != 2:
+            raise ValueError(f"{name}: a two-dimensional tensor [K, n] is needed, got {t.dim()} dimensions")
+        if K is not None and t.shape[0] != K:
+            raise ValueError(f"{name}: {K} rows are needed as in the other arrays, got {t.shape[0]}")
+        K = t.shape[0]
+    if K is None:
+        raise ValueError("stacked: no tensor given")
+    return [{name: t[k] for name, t in two_d.items() if t is not None} for k in range(K)]
+
+
 class TensorResult:
     """What run_tensors returns: the four vectors as tensors on the solver's device and the scalars of pdlp_result_t
-    (attribute access falls through to the struct: term_code, num_iter, primal_obj, setup_seconds, ...)."""
+    (attribute access falls through to the struct: term_code, num_iter, primal_obj, setup_seconds, ...).  A vector named
+    in `skip` is not asked for: its pointer is NULL and its tensor None."""
 
     VECTORS = ("col_value", "col_dual", "row_value", "row_dual")
 
-    def __init__(self, num_col, num_row, device, out=None):
+    def __init__(self, num_col, num_row, device, out=None, skip=()):
         import torch
 
         sizes = dict(col_value=num_col, col_dual=num_col, row_value=num_row, row_dual=num_row)
         out = dict(out or {})
-        unknown = set(out) - set(self.VECTORS)
+        unknown = (set(out) | set(skip)) - set(self.VECTORS)
         if unknown:
             raise ValueError(f"out: unknown vectors {sorted(unknown)}; the four are {self.VECTORS}")
         R = abi.PdlpResult()
         self.tensors = {}
         for name in self.VECTORS:
             t = out.get(name)
+            if name in skip:
+                self.tensors[name] = None
+                continue
             if t is None:
                 t = torch.empty(sizes[name], dtype=torch.float64, device=device)
             else:

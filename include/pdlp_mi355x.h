@@ -505,6 +505,30 @@ int pdlp_mi355x_create_device(const pdlp_problem_t* P_dev, const pdlp_params_t* 
 int pdlp_mi355x_update_device(pdlp_mi355x_solver_t* s, const double* a_value_dev, int64_t num_nz, const double* q_value_dev,
                               int64_t num_q_nz, const pdlp_update_t* u_dev, void* stream);
 int pdlp_mi355x_run_device(pdlp_mi355x_solver_t* s, pdlp_result_t* R_dev);
+/* pdlp_mi355x_batch_run_device: pdlp_mi355x_batch_run_values with the variants' arrays and the solutions' vectors in HBM on
+ * the batch's device — for callers that hold K cost vectors or K sets of matrix / Hessian values as a [K, n] tensor and want
+ * [K, n] solutions back on the device.  v_dev[k] and R_dev[k] are host structs; every array pointer
+ * inside them follows the rule above.  `stream` has update_device's meaning: every lane's stream is ordered behind ONE event
+ * recorded there, and it is never synchronised; NULL is the default stream.  R_dev follows run_device's rule: a NULL vector
+ * is skipped, whatever the caller has queued that still READS the vectors of R_dev must have completed before the call,
+ * counts and scalars go to the host structs.  A hot start inside a variant is taken as update_device takes it (downloaded).
+ *
+ * THE CONTRACT: R_dev[k] holds, bit for bit — every solution vector, every count, every scalar except setup_seconds and
+ * solve_seconds — what pdlp_mi355x_batch_run_values gives for the same arrays in host memory on the same batch; for every
+ * K, every lane count, every finishing order, where the lanes share launches and where they do not.  pdlp_batch_info_t
+ * describes the call as it does a batch_run_values.  "Unchanged" means P's values here too: the batch uploads a copy of
+ * P's data at its first device run and restores from there.  Host and device runs mix freely on one batch.
+ *
+ * REFUSALS are all-or-nothing (the batch stays as it was) and come in a fixed order:
+ *   1. without any device call: null arguments and K < 1; then, for k = 0..K-1, what the entry variant k maps to refuses
+ *      without looking at a value (shape, counts, updatable bits, partial start): "variant k: " + that entry's words;
+ *   2. THE POINTER CHECK on every array of every variant, then on every vector of every result, before any launch or copy
+ *      touches a caller's array: "variant 5: col_cost is not device memory on device 0", "result 2: row_dual is not ...";
+ *   3. the value checks, on the device, for all K variants in ONE launch: the lowest k with a finding is refused; within
+ *      it the order is row-kind change, all-zero matrix, negative diagonal: "variant k: " + the words the update entries
+ *      use (for the kind-change message that one row's two bounds are downloaded). */
+int pdlp_mi355x_batch_run_device(pdlp_mi355x_batch_t* B, int32_t K, const pdlp_variant_t* v_dev, pdlp_result_t* R_dev,
+                                 void* stream);
 /* ONE HIP RUNTIME PER PROCESS: the caller's arrays and this library must live in the same copy of the HIP runtime.  A
  * process that holds two — a PyTorch wheel bundles its own libamdhip64 — has the GPU in whichever started first; the other
  * finds no device ("no HIP device available").  highs_amd.solver.lib() registers the system's copy under the name a later

@@ -4,7 +4,9 @@
 // the launch counts, the refills and the failure rule.  A canned lane also plays the held solver of a value variant
 // (pdlp_mi355x_batch_run_values): it follows which array its "solver" holds through the one update call the lane plans
 // (planLaneUpdate), and checks after every update that it holds variant k = P with v[k] applied — whatever it solved
-// before, and also after an update that threw half-way.
+// before, and also after an update that threw half-way.  In DEVICE mode (pdlp_mi355x_batch_run_device) the driver sets the
+// mode on every lane, asks lane 0 ONCE for the validation of all variants and results, and the lanes restore from the
+// batch's second copy of P — the one that stands for P's data in HBM —, never from the host's: a call never mixes the two.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -43,16 +45,36 @@ const double kTorn = 0.0;  // what an array holds after an update that threw: ne
 struct Held { const double *cost, *rows, *a, *q; };
 struct CannedLane : BatchLane {
   const Script& sc;
-  const BaseData& base;
+  const BaseView base[2];  // P's data where a host call restores from, and where a device call does
+  LaneMode mode = kLaneHost;
+  int modeSets = 0, hostValidations = 0, deviceValidations = 0, deviceFinishes = 0;
   int id, variant = -1, left = 0, updates = 0, alone = 0, shared = 0, differs = 0, plain = 0, matrix = 0, values = 0;
   bool threw = false, disqualified = false;
   Held held;
   std::vector<int> solved;
-  CannedLane(const Script& s, const BaseData& b, int i)
-      : sc(s), base(b), id(i), held{b.cost.data(), b.rowLower.data(), b.aValue.data(), b.qValue.data()} {}
+  CannedLane(const Script& s, const BaseView& host, const BaseView& device, int i)
+      : sc(s), base{host, device}, id(i), held{host.cost, host.rowLower, host.aValue, host.qValue} {}
+  const BaseView& mine() const { return base[mode == kLaneDevice ? 1 : 0]; }
+  void setMode(LaneMode m) override { mode = m; ++modeSets; }
   std::string sequentialReason() override { return disqualified ? "canned: no longer shareable" : sc.sequential; }
   int32_t workBlocks() override { return 21; }
+  void validateDevice(int32_t K, const Variant* v, const pdlp_result_t* R) override {
+    CHECK(mode == kLaneDevice && id == 0 && K >= 1 && v && R);
+    ++deviceValidations;
+    for (int32_t k = 0; k < K; ++k) {
+      try {
+        refusals(v[k]);
+      } catch (const std::exception& e) {
+        throw std::runtime_error("variant " + std::to_string(k) + ": " + e.what());
+      }
+    }
+  }
   void validate(const Variant& v) override {
+    CHECK(mode == kLaneHost);
+    ++hostValidations;
+    refusals(v);
+  }
+  void refusals(const Variant& v) {
     if (v.u.reserved == -7) throw std::runtime_error("pdlp_mi355x_update: row 5 would change its kind");
     if (v.u.reserved == -8) throw std::runtime_error("pdlp_mi355x_update_values: the Hessian is not positive semidefinite");
   }
@@ -60,7 +82,7 @@ struct CannedLane : BatchLane {
   // SolverLane::update, with a solver that only remembers whose array it holds
   void update(const Variant& v) override {
     ++updates;
-    const LaneUpdatePlan plan = planLaneUpdate(v, differs, base);
+    const LaneUpdatePlan plan = planLaneUpdate(v, differs, mine());
     const Variant& w = plan.v;
     differs |= plan.now;
     CHECK(plan.call == (w.q_value ? kCallUpdateValues : w.a_value ? kCallUpdateMatrix : kCallUpdate));
@@ -80,10 +102,18 @@ struct CannedLane : BatchLane {
     differs = plan.now;
     (plan.call == kCallUpdate ? plain : plan.call == kCallUpdateMatrix ? matrix : values)++;
     // variant k = P with v[k] applied
-    CHECK(held.cost == (v.u.col_cost ? v.u.col_cost : base.cost.data()));
-    CHECK(held.rows == (v.u.row_lower ? v.u.row_lower : base.rowLower.data()));
-    CHECK(held.a == (v.a_value ? v.a_value : base.aValue.data()));
-    CHECK(held.q == (v.q_value ? v.q_value : base.qValue.data()));
+    // ... P's data being the copy that lives where this call's arrays do; what the variant leaves alone and the lane did
+    // not differ in stays whichever copy of P it held (both are P)
+    auto isP = [&](const double* h, const double* BaseView::*f) { return h == base[0].*f || h == base[1].*f; };
+    CHECK(v.u.col_cost ? held.cost == v.u.col_cost : isP(held.cost, &BaseView::cost));
+    CHECK(v.u.row_lower ? held.rows == v.u.row_lower : isP(held.rows, &BaseView::rowLower));
+    CHECK(v.a_value ? held.a == v.a_value : isP(held.a, &BaseView::aValue));
+    CHECK(v.q_value ? held.q == v.q_value : isP(held.q, &BaseView::qValue));
+    // a restore made in this call took the copy of this call's side
+    if (w.u.col_cost && !v.u.col_cost) CHECK(w.u.col_cost == mine().cost);
+    if (w.u.row_lower && !v.u.row_lower) CHECK(w.u.row_lower == mine().rowLower && w.u.row_upper == mine().rowUpper);
+    if (w.a_value && !v.a_value) CHECK(w.a_value == mine().aValue && w.num_nz == mine().nnz);
+    if (w.q_value && !v.q_value) CHECK(w.q_value == mine().qValue && w.num_q_nz == mine().qSlots);
     if (variant == sc.disqualifyVariant) disqualified = true;
   }
   void runAlone(pdlp_result_t* R) override { R->num_iter = variant; R->num_trials = -1 - id; ++alone; solved.push_back(variant); }
@@ -98,7 +128,10 @@ struct CannedLane : BatchLane {
     if (variant == sc.failVariant) return kLaneFailed;
     return --left <= 0 ? kLaneOver : kLaneGoOn;
   }
-  void finish(pdlp_result_t* R) override { R->num_iter = variant; R->num_trials = id; solved.push_back(variant); }
+  void finish(pdlp_result_t* R) override {
+    R->num_iter = variant; R->num_trials = id; solved.push_back(variant);
+    deviceFinishes += mode == kLaneDevice ? 1 : 0;
+  }
   int32_t xcc() override { return id; }
 };
 struct CountingBackend : BatchBackend {
@@ -113,14 +146,18 @@ struct CountingBackend : BatchBackend {
   }
 };
 
-void scenario(int nLanes, const Script& sc, int K, bool oldEntry = true) {
+void scenario(int nLanes, const Script& sc, int K, bool oldEntry = true, bool device = false) {
   const Arrays p;
   const pdlp_problem_t P = problemOf(p);
-  const BaseData base(P);
+  const BaseData base(P), baseInHbm(P);  // (the second stands for the batch's copy of P in HBM: other addresses, never read)
   CHECK(base.aValue.size() == 3 && base.qValue.size() == 2 && base.aValue.data() != p.a.data());  // (a copy: P's arrays may go)
+  CHECK(base.view().nnz == 3 && base.view().qSlots == 2 && base.view().cost != baseInHbm.view().cost);
   std::vector<std::unique_ptr<CannedLane>> own;
   std::vector<BatchLane*> lanes;
-  for (int l = 0; l < nLanes; ++l) { own.emplace_back(new CannedLane(sc, base, l)); lanes.push_back(own.back().get()); }
+  for (int l = 0; l < nLanes; ++l) {
+    own.emplace_back(new CannedLane(sc, base.view(), baseInHbm.view(), l));
+    lanes.push_back(own.back().get());
+  }
   CountingBackend be;
   BatchDriver d(lanes, &be);
   std::vector<Arrays> mine((size_t)K);
@@ -138,12 +175,13 @@ void scenario(int nLanes, const Script& sc, int K, bool oldEntry = true) {
     if (kind == 'D') { v.u.col_cost = m.cost.data(); v.u.row_lower = m.rowLo.data(); v.u.row_upper = m.rowUp.data(); }
     nValue += hasValues(v) ? 1 : 0;
   }
-  const char* entry = oldEntry ? kEntryBatchRun : kEntryBatchRunValues;
+  const char* entry = device ? kEntryBatchRunDevice : oldEntry ? kEntryBatchRun : kEntryBatchRunValues;
+  const LaneMode mode = device ? kLaneDevice : kLaneHost;
   for (auto& r : R) r.num_iter = -1;
   if (sc.badVariant >= 0) {
     u[(size_t)sc.badVariant].u.reserved = oldEntry ? -7 : -8;
     bool threw = false;
-    try { d.run(K, u.data(), R.data(), entry); } catch (const std::exception& e) {
+    try { d.run(K, u.data(), R.data(), entry, mode); } catch (const std::exception& e) {
       threw = true;
       const char* words = oldEntry ? ": pdlp_mi355x_update: row 5" : ": pdlp_mi355x_update_values: the Hessian is not";
       CHECK(std::string(e.what()).find("variant " + std::to_string(sc.badVariant) + words) == 0);
@@ -155,12 +193,12 @@ void scenario(int nLanes, const Script& sc, int K, bool oldEntry = true) {
   }
   {  // K < 1 and null arrays, by the entry's name
     bool threw = false;
-    try { d.run(0, u.data(), R.data(), entry); } catch (const std::exception& e) {
+    try { d.run(0, u.data(), R.data(), entry, mode); } catch (const std::exception& e) {
       threw = std::string(e.what()) == std::string(entry) + ": K = 0 variants (at least 1)";
     }
     CHECK(threw);
     threw = false;
-    try { d.run(K, nullptr, R.data(), entry); } catch (const std::exception& e) {
+    try { d.run(K, nullptr, R.data(), entry, mode); } catch (const std::exception& e) {
       threw = std::string(e.what()) == std::string(entry) + ": null argument";
     }
     CHECK(threw);
@@ -169,15 +207,32 @@ void scenario(int nLanes, const Script& sc, int K, bool oldEntry = true) {
     // an update that throws in the middle of a run ends the call; the lanes then differ from P in whatever they were
     // asked to change, so the next call (below) still gives every variant its own arrays
     bool threw = false;
-    try { d.run(K, u.data(), R.data(), entry); } catch (const std::exception& e) {
+    try { d.run(K, u.data(), R.data(), entry, mode); } catch (const std::exception& e) {
       threw = std::string(e.what()).find("canned: the update of variant") == 0;
     }
     CHECK(threw);
     for (auto& l : own) { l->solved.clear(); l->alone = l->shared = 0; }
     for (auto& r : R) r.num_iter = -1;
   }
-  d.run(K, u.data(), R.data(), entry);
+  d.run(K, u.data(), R.data(), entry, mode);
   const pdlp_batch_info_t& I = d.info();
+  if (device) {
+    // a host call first, so that lanes differ from P through HOST arrays when the device call restores them; then the device
+    // call again: every lane was told the mode, lane 0 alone validated, once per call, and no lane validated the host's way
+    auto again = [&] {
+      for (auto& l : own) { l->solved.clear(); l->alone = l->shared = 0; l->disqualified = false; }
+    };
+    again();
+    for (auto& l : own) l->hostValidations = l->deviceValidations = l->deviceFinishes = 0;
+    d.run(K, u.data(), R.data(), kEntryBatchRunValues, kLaneHost);
+    for (auto& l : own) CHECK(l->mode == kLaneHost && l->deviceValidations == 0 && l->deviceFinishes == 0);
+    again();
+    CHECK(own[0]->hostValidations == K);
+    for (auto& r : R) r.num_iter = -1;
+    own[0]->hostValidations = 0;
+    d.run(K, u.data(), R.data(), entry, mode);
+    for (auto& l : own) CHECK(l->mode == kLaneDevice && l->hostValidations == 0 && l->deviceValidations == (l->id == 0 ? 1 : 0));
+  }
   for (int k = 0; k < K; ++k) CHECK(R[(size_t)k].num_iter == k);  // every variant solved, each into its own result
   int solved = 0, plain = 0, valued = 0;
   for (auto& l : own) { solved += (int)l->solved.size(); plain += l->plain; valued += l->matrix + l->values; }
@@ -208,7 +263,7 @@ void scenario(int nLanes, const Script& sc, int K, bool oldEntry = true) {
     }
     CHECK(I.trial_launches == I.check_launches && I.trial_launches > 0);
   }
-  printf("ok: %d lanes, K = %d%s: %s; %d shared launches, %d alone; %d plain and %d value updates\n", nLanes, K,
+  printf("ok: %s%d lanes, K = %d%s: %s; %d shared launches, %d alone; %d plain and %d value updates\n", device ? "device mode, " : "", nLanes, K,
          sc.kinds.empty() ? "" : (" [" + sc.kinds + "]").c_str(), I.reason, I.trial_launches, I.fallback_variants, plain, valued);
 }
 }  // namespace
@@ -251,6 +306,17 @@ int main() {
   scenario(3, vd, 8, false);
   Script vf = v; vf.failVariant = 1;
   scenario(3, vf, 8, false);
+  // device mode: the same driver, the lanes told so per call; restores come from the copy of P that stands for HBM
+  scenario(1, v, 8, false, true);
+  scenario(2, v, 8, false, true);
+  scenario(8, v, 8, false, true);
+  scenario(3, v, 12, false, true);
+  scenario(8, vs, 8, false, true);
+  scenario(4, vb, 8, false, true);
+  scenario(2, vt, 8, false, true);
+  scenario(3, vd, 8, false, true);
+  scenario(3, vf, 8, false, true);
+  scenario(3, a, 7, false, true);
   printf("batch driver: all scenarios passed\n");
   return 0;
 }
